@@ -7,8 +7,6 @@ gci_dev_* exports of libgci_hip.so).  torch is imported only by the ranks of a `
 import os
 import sys
 
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")      # (gci_amd/__init__.py says why; here as well: the runtime is woken below, before that import)
-
 
 def _wake_the_gpu():
     """The HIP runtime's own start (driver, device, primary context: a few tenths of a second) on a thread of its own while the

@@ -33,7 +33,6 @@ import time
 
 import numpy as np
 
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")       # (gci_amd/__init__.py: streams that share a hardware queue run one after the other)
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
@@ -113,7 +112,15 @@ def parse_args():
                          "8-GPU node takes, on one GPU")
     ap.add_argument("--force-replicated", action="store_true",
                     help="with the exchange: always take the replicated-join fallback (all-gather of records + names)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64 / float32, at most 64 MB: "
+                         "a fixed, seeded sample of the depth tracks and text); rank 0's outputs; not with --workload paf")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload == "paf":
+        ap.error("--dump-outputs covers the filter+depth workloads, not --workload paf")
+    return args
 
 
 def _p(t):
@@ -1658,6 +1665,77 @@ def paf_number(args):
             "h2d_seconds_outside_the_pass": t_h2d, "generation_seconds": t_gen}
 
 
+# ---- --dump-outputs: what the last timed step computed, for comparing two builds output for output ---------------------------
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE = 1 << 20          # positions of a depth track, and bytes of the depth text, written by --dump-outputs
+DUMP_SEED = 20260401
+
+
+def _sample_positions(n, k, seed):
+    """Sorted positions in [0, n): all of them when n <= k, else a fixed sample of at most k drawn with `seed`."""
+    if n <= k:
+        return np.arange(n, dtype=np.int64)
+    return np.unique(np.random.default_rng(seed).integers(0, n, size=k, dtype=np.int64))
+
+
+def _runs_rows(runs):
+    """Per-window [k, 2] (start, end) runs -> float64 [K, 3] rows (window, start, end)."""
+    rows = [np.column_stack([np.full(len(r), c, dtype=np.int64), r]) for c, r in enumerate(runs) if len(r)]
+    return np.concatenate(rows).astype(np.float64) if rows else np.zeros((0, 3), dtype=np.float64)
+
+
+def dump_outputs(w, out_dir):
+    """The arrays the timed step hands its caller, from its last run, as DIR/<name>.npy in float64 (float32 for text bytes).
+    Depth tracks and the depth text are too large to write whole: their values at a fixed, seeded sample of positions are
+    written beside those positions (depth_sample_pos: along the contigs laid end to end in header order).  Issue runs are
+    (contig, start, end) rows in sorted order.  Every other array is written whole."""
+    import torch
+    torch.cuda.synchronize()
+    dev = w.eng.device
+    starts = np.concatenate([[0], np.cumsum(np.asarray(w.own_lengths, dtype=np.int64))])
+    pos = _sample_positions(int(starts[-1]), DUMP_SAMPLE, DUMP_SEED)
+    c = np.searchsorted(starts, pos, side="right") - 1
+    d_idx = torch.from_numpy(np.asarray(w.eng.offsets, dtype=np.int64)[c] + (pos - starts[c])).to(dev)
+
+    def depth_at(track):
+        return track[d_idx].cpu().numpy().astype(np.float64)
+
+    def f64(t):
+        return t.cpu().numpy().astype(np.float64)
+
+    arrays = {"depth_sample_pos": pos.astype(np.float64)}
+    if isinstance(w, TwoTypeWorkload):
+        for tag, d in zip(("hifi", "nano"), w.types):
+            arrays["depth_sample_" + tag] = depth_at(d["track"])
+            arrays["contig_depth_sums_" + tag] = f64(d["sums"])
+            arrays["join_intervals_" + tag] = f64(d["count"])
+        arrays["depth_sample_max"] = depth_at(w.two)
+        for tag, runs in zip(("hifi", "nano", "max"), w.last["runs"]):
+            arrays["issue_runs_" + tag] = _runs_rows(runs)
+        for tag, runs in zip(("hifi", "nano", "max"), w.last["regions"] or ()):
+            arrays["region_runs_" + tag] = _runs_rows(runs)
+    else:
+        from gci_amd.device import Engine
+        nc = len(w.own)
+        arrays["depth_sample"] = depth_at(w.track)
+        arrays["contig_depth_sums"] = f64(w.sums)
+        keys = w.keys[:int(w.nkeys.item())].cpu().numpy().view(np.uint64)
+        arrays["issue_runs"] = _runs_rows(Engine._keys_to_runs(keys, nc))
+        text_off = w.text_off.cpu().numpy()
+        tpos = _sample_positions(int(text_off[nc]), DUMP_SAMPLE, DUMP_SEED + 1)
+        arrays["depth_text_offsets"] = text_off.astype(np.float64)
+        arrays["depth_text_sample_pos"] = tpos.astype(np.float64)
+        arrays["depth_text_sample"] = w.text[torch.from_numpy(tpos).to(dev)].cpu().numpy().astype(np.float32)
+        if not w.sharded:
+            arrays["join_intervals"] = f64(w.count)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        sys.exit("bench.py --dump-outputs: %d bytes of outputs, more than the %d allowed" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     args = parse_args()
     if args.paf_published_gb:
@@ -1815,6 +1893,8 @@ def main():
     else:
         aligned_total = w.aligned_bases
     ms_per_step = dt / args.steps * 1e3
+    if args.dump_outputs and rank == 0:
+        dump_outputs(lanes[(args.steps - 1) % len(lanes)][1], args.dump_outputs)
 
     # ---- roofline of the dominant kernel: k_tile_build writes the int32 track (4 B/base) and the decimal text; it
     # reads only the event buckets.  Average launch time from HIP events on the ctx stream over the timed region.

@@ -1025,10 +1025,9 @@ int gci_inflate_wave_run(gci_ctx* ctx, const uint8_t* d_raw, const uint64_t* d_m
     // scratch of its own: a wave takes a millisecond per member, so the last members of a batch leave most of the chip idle -- the
     // other stream's kernels move in as CUs fall free (and the copy kernel of one batch runs beside the decode of the next).
     static const bool copy_persistent = [] { const char* e = getenv("GCI_INFLATE_COPY_GRID"); return !(e && !strcmp(e, "members")); }();   // (A/B)
-    // (two streams only when the HOST says its runtime has hardware queues to spare -- gci_bgzf_inflate_streams(ctx, 2), which
-    // gci_amd calls when it placed GPU_MAX_HW_QUEUES=8 in the environment BEFORE the runtime started --: with the default four, the
-    // second stream came to share a queue with the host's copy stream and every upload waited for an inflate.  The environment
-    // string alone proves nothing: a runtime that was already running when the variable was set has four queues all the same.)
+    // (two streams only when the HOST asks for them -- gci_bgzf_inflate_streams(ctx, 2) --: a second stream that shares a hardware
+    // queue with the host's copy stream makes every upload wait for an inflate, and only the host knows how many queues its
+    // runtime was given.  gci_amd leaves the default of one.)
     static const int env_streams = [] { const char* e = getenv("GCI_INFLATE_STREAMS"); return e ? atoi(e) : 0; }();   // (A/B)
     const int n_streams = env_streams >= 1 ? (env_streams > 2 ? 2 : env_streams) : ctx->inflate_streams;
     const uint32_t batch = n_members < batch_max ? n_members : batch_max;

@@ -177,9 +177,6 @@ class Engine:
         if st != 0:
             raise GciError(st, "gci_ctx_create: %s" % self.lib.gci_strerror(st).decode())
         self.ctx = h
-        from . import HW_QUEUES_OK
-        if HW_QUEUES_OK:                          # (the runtime has hardware queues to spare: the inflate may take a second stream)
-            self.lib.gci_bgzf_inflate_streams(h, 2)
         self.lengths: List[int] = []
         self.offsets: List[int] = []
         self.total = 0

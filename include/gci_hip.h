@@ -573,9 +573,9 @@ int gci_stage_free(gci_stage* stage);
  * verified.  d_raw must be readable for 8 bytes past its last member (the decoders fetch whole aligned words).
  * *d_status: min over failing members of (member << 8 | -status), UINT64_MAX if none (decode with gci_decode_status).
  * gci_bgzf_inflate_streams(ctx, 2): every other batch of members runs on a second stream of the context's own.  For a host
- * whose HIP runtime has hardware queues to spare -- GPU_MAX_HW_QUEUES >= 8 in the environment BEFORE the runtime started; the
- * default four are shared by all streams of a process, and a copy stream that shares one with the inflate waits for it (uploads
- * at 26 instead of 58 GB/s) -- and only the host knows whether the variable was there in time: the default is 1.
+ * whose HIP runtime has hardware queues to spare: the queues are shared by all streams of a process, and a copy stream that
+ * shares one with the inflate waits for it (uploads at 26 instead of 58 GB/s); only the host knows how many queues its runtime
+ * was given: the default is 1.
  * GCI_INFLATE_STREAMS=1|2 in the environment overrides (measurements).
  * gci_bgzf_inflate_last_stats (synchronises): how the members of the context's LAST gci_bgzf_inflate_device call fared with the
  * wave decoder -- h_counts[0] decoded, [1] header not taken, [2] no meeting point, [3] end-of-block codes on wrong paths,

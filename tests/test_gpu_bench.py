@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -55,3 +56,29 @@ def test_bench_line_contract():
     assert 0 < sw["ms_per_step"] and sw["gbases_per_s"] > 0 and sw["k_tile_build_avg_launch_ms"] > 0 and 0 < sw["hbm_frac"] < 1
     two = d["two_steps_in_flight"]
     assert two["status_ok"] and two["same_track_as_one_in_flight"]
+
+
+def test_bench_dump_outputs_repeat_from_run_to_run(tmp_path):
+    """--dump-outputs: the arrays of the last timed step as float32 / float64 .npy files, 64 MB at most, the same from one run to
+    the next (the inputs are seeded) and consistent with one another."""
+    runs = []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--scale", "0.02", "--steps", "2", "--warmup", "1", "--only-step",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, timeout=900, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        assert json.loads(r.stdout.strip().splitlines()[-1])["steps"] == 2
+        runs.append({f[:-4]: np.load(d / f) for f in sorted(os.listdir(d))})
+    a, b = runs
+    assert sorted(a) == sorted(b)
+    assert {"depth_sample", "depth_sample_pos", "contig_depth_sums", "issue_runs", "depth_text_offsets", "depth_text_sample",
+            "depth_text_sample_pos", "join_intervals"} <= set(a)
+    assert sum(x.nbytes for x in a.values()) <= 64 << 20
+    for name in a:
+        assert a[name].dtype in (np.float32, np.float64), name
+        assert np.array_equal(a[name], b[name]), name
+    pos, dep = a["depth_sample_pos"], a["depth_sample"]
+    assert pos.shape == dep.shape and np.all(np.diff(pos) > 0) and dep.min() >= 0 and dep.max() > 0
+    assert a["issue_runs"].shape[1] == 3 and a["join_intervals"][0] > 0
+    assert np.isin(a["depth_text_sample"], np.frombuffer(b"0123456789\n", dtype=np.uint8)).all()
+    assert a["depth_text_sample_pos"].max() < a["depth_text_offsets"][-1]
