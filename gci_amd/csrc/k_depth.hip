@@ -773,16 +773,6 @@ __global__ __launch_bounds__(BLOCK) void k_tile_pass1(
 // SPARSE_MAX events, or with a depth of four or more digits when text is wanted, is done densely by a whole
 // workgroup (k_tile_dense).
 
-#ifdef GCI_TILE_TRACE           // tools/exp_tile_trace.py: shader-clock stamps per tile
-#define TT(i) do { if ((threadIdx.x & 63) == 0) g_tt[(i)] = clock64(); } while (0)
-#define TT_PARAM , unsigned long long* g_tt
-#define TT_ARG , g_tt
-#else
-#define TT(i) do {} while (0)
-#define TT_PARAM
-#define TT_ARG
-#endif
-
 __device__ __forceinline__ uint32_t mod_w(uint32_t x, uint32_t w)        // x mod w for x < 2^16, w in {2, 3, 4}
 {
     const uint32_t m3 = x - 3u * ((x * 43691u) >> 17);
@@ -819,13 +809,11 @@ __device__ __forceinline__ uint32_t cut_dword(uint32_t a, uint32_t b, int32_t cu
 __device__ __forceinline__ bool tile_sparse2(
     int64_t tile, uint32_t e0, uint32_t n_ev, const uint16_t* __restrict__ events, int32_t carry_in, int32_t valid,
     int32_t* __restrict__ depth, uint64_t T0, uint8_t* __restrict__ text, uint64_t text_cap, int lane, uint32_t wi,
-    uint32_t nw, int2* __restrict__ run_list TT_PARAM)
+    uint32_t nw, int2* __restrict__ run_list)
 {
     // wi / nw: this wave is one of nw that share the tile: every one derives the segments, wave 0 writes the groups
     // that hold boundaries, and the whole groups of segment r go to wave r mod nw
-    TT(1);
     Seg sg = sparse_segments(e0, n_ev, events, carry_in, valid, lane);
-    TT(2);
     // want_runs: the segments -- {depth, length}, in order, possibly empty, neighbours possibly of equal depth -- are what the
     // .depth.gz encoder (k_deflate.hip) wants to know about this tile: one coalesced store of 8 bytes per lane instead of a
     // second read of the tile's 16 KB
@@ -885,7 +873,6 @@ __device__ __forceinline__ bool tile_sparse2(
             }
         }
     }
-    TT(3);
     if (!text) return true;
 
     // ---- text ----------------------------------------------------------------------------------------------------
@@ -963,7 +950,6 @@ __device__ __forceinline__ bool tile_sparse2(
         const bool own = lane < 16 && y >= ru1 && y < ru2, prv = lane < 16 && q_covers && y < ru1;
         if ((own || prv) && y < capu) TB[y] = own ? (uint8_t)(rX >> (8u * mod_w(y - ru1, rw))) : (uint8_t)(qX >> (8u * mod_w(y - qu1, qw)));
     }
-    TT(4);
     // whole groups of every segment.  The pattern of a segment is wave-uniform, and so is its phase at a group start
     // when w divides 16 (w = 2, 4): the group is four copies of one scalar dword.  For w = 3 the phase moves by one
     // per group (16 = 1 mod 3) and the group is a rotation of three scalar dwords.
@@ -1024,11 +1010,7 @@ __global__ __launch_bounds__(BLOCK) void k_tile_build(
     const int32_t* __restrict__ tile_valid, int64_t n_tiles, int32_t* __restrict__ depth,
     const uint64_t* __restrict__ tile_text_off, uint8_t* __restrict__ text, uint64_t text_cap,
     uint8_t* __restrict__ dense_flag, uint32_t* __restrict__ dense_list, int32_t sparse_max, uint32_t* __restrict__ cd_words,
-    uint32_t* __restrict__ run_n, int2* __restrict__ run_list
-#ifdef GCI_TILE_TRACE
-    , unsigned long long* __restrict__ trace
-#endif
-    )
+    uint32_t* __restrict__ run_n, int2* __restrict__ run_list)
 {
     const int lane = threadIdx.x & 63;
     // the wave index is uniform: say so, and everything per tile (bounds, carry, offsets, loop counts) lives in SGPRs
@@ -1043,22 +1025,17 @@ __global__ __launch_bounds__(BLOCK) void k_tile_build(
     const uint32_t wi = (uint32_t)(gw % SHARE);
     if (tile >= n_tiles) return;
     if (gw == 0 && lane == 0) dense_list[0] = 0u;                             // k_dense_list (next on the stream) counts from here
-#ifdef GCI_TILE_TRACE
-    unsigned long long* g_tt = trace + tile * 8;
-    TT(0);
-#endif
     const uint32_t e0 = evt_off[tile], e1 = evt_off[tile + 1];
     const int32_t carry_in = tile_carry[tile], valid = tile_valid[tile];
     const uint64_t T0 = text ? tile_text_off[tile] : 0ull;
     bool done = false;
     if ((int64_t)(e1 - e0) <= sparse_max)
-        done = tile_sparse2(tile, e0, e1 - e0, events, carry_in, valid, depth, T0, text, text_cap, lane, wi, SHARE, run_list TT_ARG);
+        done = tile_sparse2(tile, e0, e1 - e0, events, carry_in, valid, depth, T0, text, text_cap, lane, wi, SHARE, run_list);
     if (lane == 0 && wi == 0) {
         dense_flag[tile] = done ? 0 : 1;                                     // k_tile_dense takes the rest
         if (run_n) run_n[tile] = done ? (e1 - e0) + 1u : GCI_RUNS_WALK;      // (a dense tile: the encoder reads the track)
         cd_words[2 * tile + 1] = 0u;                                         // the coarse difference has been consumed: table clean again
     }
-    TT(7);
 }
 
 // The dense tiles: those k_tile_build flagged (more than sparse_max events, or a shape its sparse path declined).
@@ -1098,12 +1075,6 @@ __global__ __launch_bounds__(BLOCK) void k_tile_dense(
 
 // ---- host -----------------------------------------------------------------------------------------
 
-#ifdef GCI_TILE_TRACE
-#define TILE_TRACE_ARG , (unsigned long long*)strtoull(getenv("GCI_TILE_TRACE_PTR") ? getenv("GCI_TILE_TRACE_PTR") : "0", nullptr, 0)
-#else
-#define TILE_TRACE_ARG
-#endif
-
 static int launch_tile_build(gci_ctx* ctx, int pass, IssueArgs iss, int32_t* d_depth, uint8_t* d_text, uint64_t text_cap)
 {
     const dim3 block(BLOCK);
@@ -1133,7 +1104,7 @@ static int launch_tile_build(gci_ctx* ctx, int pass, IssueArgs iss, int32_t* d_d
             hipLaunchKernelGGL(k_tile_build, grid2, block, 0, ctx->stream, ev, eo, tc, tv, ctx->n_tiles, d_depth,
                                (const uint64_t*)ctx->tile_u64.p, d_text, text_cap, flag, list, ctx->sparse_max,
                                (uint32_t*)ctx->tile_cd.p, ctx->build_runs_wanted ? (uint32_t*)ctx->build_nruns.p : nullptr,
-                               ctx->build_runs_wanted ? (int2*)ctx->build_runs.p : nullptr TILE_TRACE_ARG);
+                               ctx->build_runs_wanted ? (int2*)ctx->build_runs.p : nullptr);
             LAUNCHCHK("k_tile_build");
         }
         ProfScope _ps(ctx, GCI_PROF_TILE_DENSE);

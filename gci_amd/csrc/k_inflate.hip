@@ -503,16 +503,9 @@ extern "C" int gci_bgzf_inflate_device(gci_ctx* ctx, const uint8_t* d_raw, const
             d_done = (const uint32_t*)ctx->inflate_wstatus.p;
             ctx->inflate_last_n = n_members;
         }
-        // members per wave: fewer = more waves per SIMD to overlap the memory round trips, more = fewer instructions issued
-        static const int lanes = [] { const char* e = getenv("GCI_INFLATE_LANES"); return e ? atoi(e) : 8; }();
-        auto launch = [&](auto kern, int per) {
-            hipLaunchKernelGGL(kern, dim3((n_members + per - 1) / per), dim3(64), 0, ctx->stream, d_raw, d_member_pos, d_out_off, n_members,
-                               d_out, out_cap, (unsigned long long*)d_status, d_done);
-        };
-        if (lanes == 4) launch(k_bgzf_inflate<4>, 4);
-        else if (lanes == 16) launch(k_bgzf_inflate<16>, 16);
-        else if (lanes == 32) launch(k_bgzf_inflate<32>, 32);
-        else launch(k_bgzf_inflate<8>, 8);
+        // eight members per wave (gci_bgzf_inflate_round assumes the same)
+        hipLaunchKernelGGL(k_bgzf_inflate<8>, dim3((n_members + 7) / 8), dim3(64), 0, ctx->stream, d_raw, d_member_pos, d_out_off, n_members,
+                           d_out, out_cap, (unsigned long long*)d_status, d_done);
         LAUNCHCHK("k_bgzf_inflate");
         if (check_crc) {
             if (!ctx->crc_tabs_ready) {                                      // (ready only once the launch went through)

@@ -346,20 +346,18 @@ using namespace iw;
 // members [m0, m0 + n_batch) of the run; sym: n_batch x SYM_STRIDE entries; n_sym, wstatus: one word per member of the RUN;
 // lists: per workgroup 64 x MAXS entries, entry i of lane k at [i * 64 + k] (a step's stores are one 256-byte row)
 // entry: bit 31 set = literal (low 8 bits); else (length - 3) << 15 | (distance - 1)
-// MEASURE = false (what runs): the phase counters and the cuts do not exist -- they cost registers both kernels are short of.
+// MEASURE = false (what runs): the phase counters do not exist -- they cost registers both kernels are short of.
 template <bool MEASURE>
 __global__ __launch_bounds__(64, 4) void k_inflate_symbols(const uint8_t* __restrict__ raw, const uint64_t* __restrict__ member_pos,
                                                                    const uint64_t* __restrict__ out_off, uint64_t out_cap, uint32_t m0, uint32_t n_batch,
                                                                    uint32_t* __restrict__ sym, uint32_t* __restrict__ n_sym,
                                                                    uint32_t* __restrict__ wstatus, uint32_t* __restrict__ lists, uint32_t* __restrict__ next,
-                                                                   uint32_t cut_arg, unsigned long long* __restrict__ prof_arg)
+                                                                   unsigned long long* __restrict__ prof_arg)
 {
     unsigned long long* const prof = MEASURE ? prof_arg : nullptr;
-    const uint32_t cut = MEASURE ? cut_arg : 0u;
     // (prof: measurements only -- cycles per phase, summed over the waves: GCI_IW_PROF=1, tools/hwtests/inflate_product.py)
     unsigned long long t_hdr = 0, t_stage = 0, t_p1 = 0, t_st = 0, t_ch = 0, t_ga = 0, n_chunks = 0, t_all0 = prof ? __builtin_amdgcn_s_memtime() : 0;
 #define IW_T(acc, t0) do { if (prof) { const unsigned long long _n = __builtin_amdgcn_s_memtime(); acc += _n - t0; t0 = _n; } } while (0)
-    // (cut: measurements only -- 1 leaves a block behind its tables, 2 behind pass 1, 3 behind the stitch; 0 = the kernel)
     __shared__ Lds S;
     const int lane = threadIdx.x;
     uint32_t* const list = lists + (size_t)blockIdx.x * (64u * (MAXS + 1u)) + (uint32_t)lane;     // entry i at list[64 i]; row MAXS: writes that are none
@@ -465,7 +463,6 @@ __global__ __launch_bounds__(64, 4) void k_inflate_symbols(const uint8_t* __rest
                 C.lit_lim = (uint32_t)__builtin_amdgcn_readfirstlane((int)S.lit_cn.limit[LIT_BITS]);
                 C.dist_lim = (uint32_t)__builtin_amdgcn_readfirstlane((int)S.dist_cn.limit[DIST_BITS]);
             }
-            if (cut == 1u) { st = ST_LANES; break; }
             IW_T(t_hdr, tt);
             // ---- the block's body, chunk by chunk ----------------------------------------------------------------------------
             uint32_t cpos = body0;                                        // a symbol begins here
@@ -476,7 +473,6 @@ __global__ __launch_bounds__(64, 4) void k_inflate_symbols(const uint8_t* __rest
                 for (uint32_t i = lane; i < 64u * NCK; i += 64) S.ckpt[i] = NONE;
                 __syncthreads();
                 const uint32_t nb = nbits - 64u * cbU;                    // end of the stream, in bits of the chunk
-                if (cut == 4u) { st = ST_LANES; break; }
                 IW_T(t_stage, tt); n_chunks++;
                 // ---- pass 1: every lane over its own piece, its symbols into its list -------------------------------------------
                 const uint32_t start = lane == 0 ? cpos - 64u * cbU : (uint32_t)lane * PIECE;
@@ -518,7 +514,6 @@ __global__ __launch_bounds__(64, 4) void k_inflate_symbols(const uint8_t* __rest
                 }
                 __syncthreads();
                 IW_T(t_p1, tt);
-                if (cut == 2u || cut == 6u) { st = __ballot(os == NONE) ? ST_LANES : ST_LENGTH; break; }
                 // ---- stitch: on behind the piece until, first behind a boundary, the lane stands where the lane of THAT piece stood ------
                 // (normally within a few symbols; a lane that never falls into step with its neighbour inside the neighbour's piece
                 // has decoded that piece itself by then -- the neighbour is void -- and goes on into the piece after it)
@@ -578,7 +573,7 @@ __global__ __launch_bounds__(64, 4) void k_inflate_symbols(const uint8_t* __rest
                     const int e = ends_mask ? __ffsll((long long)ends_mask) - 1 : 63;
                     const unsigned long long upto = e >= 63 ? ~0ull : ((1ull << (e + 1)) - 1ull), below = upto >> 1;
                     const bool odd = (lane < e && (meet_lane != (uint32_t)lane + 1u || x_fail)) || (lane <= e && (!active || own == NONE - 1u));
-                    if (cut != 7u && ends_mask && (__ballot(odd) & upto) == 0ull && !(bool)__shfl((int)(x_fail && own == NONE), e, 64)) {
+                    if (ends_mask && (__ballot(odd) & upto) == 0ull && !(bool)__shfl((int)(x_fail && own == NONE), e, 64)) {
                         fast = true; E = e; (void)below;
                         live = lane <= e; ss = ss_f;
                         if (live) {
@@ -637,7 +632,6 @@ __global__ __launch_bounds__(64, 4) void k_inflate_symbols(const uint8_t* __rest
                 }
                 if (chain_bad) break;
                 if (__ballot(live && undecodable)) { st = ST_UNDECODABLE; break; }
-                if (cut == 3u) { st = __ballot(ss == NONE - 3u) ? ST_LANES : ST_LENGTH; break; }
                 if (__ballot(live && (ss + cs > MAXS || ss + cs < ss))) { st = 9u; break; }   // (a share the list did not hold)
                 IW_T(t_ch, tt);
                 uint32_t tot_s = 0;
@@ -706,14 +700,8 @@ __device__ __forceinline__ CpMeta cp_meta(uint32_t mb, uint32_t n_batch, uint32_
 #ifndef IW_CP_PF
 #define IW_CP_PF 2
 #endif
-#ifndef IW_CP_FILL_LEAN
-#define IW_CP_FILL_LEAN 0                // (see the fill loop: a variant waiting for its measurement)
-#endif
 #ifndef IW_CP_FILL_STEPS
 #define IW_CP_FILL_STEPS 4
-#endif
-#ifndef IW_CP_CUT
-#define IW_CP_CUT 0                      // (measurements: 1 = the copy kernel leaves a member behind its place phase, 2 = behind the resolve phase)
 #endif
 struct CpTiles { uint4 t[IW_CP_PF]; };
 __device__ __forceinline__ uint4 cp_load4(const uint32_t* __restrict__ msym, uint32_t i0, uint32_t ns)
@@ -764,11 +752,10 @@ template <bool MEASURE>
 __device__ __forceinline__ void copy_member(uint16_t* __restrict__ W, uint32_t* __restrict__ SB, uint32_t (*wsum)[CP_WAVES], uint32_t& s_bad, uint32_t mb,
                                             const uint32_t* __restrict__ sym, const uint32_t* __restrict__ n_sym,
                                             uint32_t* __restrict__ wstatus, const uint64_t* __restrict__ out_off,
-                                            uint32_t m0, uint8_t* __restrict__ out, uint32_t cut_arg,
+                                            uint32_t m0, uint8_t* __restrict__ out,
                                             unsigned long long* __restrict__ prof_arg, CpMeta& meta, CpTiles& first, uint32_t mb_next, uint32_t n_batch)
 {
     unsigned long long* const prof = MEASURE ? prof_arg : nullptr;
-    const uint32_t cut = MEASURE ? cut_arg : (uint32_t)IW_CP_CUT;
     unsigned long long tb = prof ? __builtin_amdgcn_s_memtime() : 0, t_place = 0, t_res = 0, n_ur = 0, n_rounds = 0;
     unsigned long long t_scan = 0, t_cells = 0, t_long = 0;
     const unsigned long long t_begin = tb;
@@ -848,12 +835,12 @@ __device__ __forceinline__ void copy_member(uint16_t* __restrict__ W, uint32_t* 
             for (int w = 0; w < CP_WAVES; w++) { const uint32_t v = wsum[par][w]; if (w < wave) woff += v; total += v; }
             if (run + total > isize) { bad = true; break; }               // (uniform)
             if (prof) { const unsigned long long n = __builtin_amdgcn_s_memtime(); t_scan += n - tb; tb = n; }
-            if (cut != 4u) mark4(ev, len, run + woff + inc - tl);          // (4: the scans and their barriers alone)
+            mark4(ev, len, run + woff + inc - tl);
             run += total;
         }
     }
     __syncthreads();                                                       // (every symbol's first cell and bit are there)
-    if (run == isize && isize && cut != 4u && cut != 5u) {                 // (5: without the fill)
+    if (run == isize && isize) {
         // fill_cells: wave w takes cells [4096 w, 4096 (w + 1)), 64 per step, a cell per lane.  The symbol a cell belongs to begins at
         // the highest set bit at or below it -- in the step's own 64 bits, else where the last step's (or, for the wave's first step,
         // a look backwards) says; cell x of a match of distance d points d (x / d + 1) back (past the match, to the cell in front
@@ -867,9 +854,6 @@ __device__ __forceinline__ void copy_member(uint16_t* __restrict__ W, uint32_t* 
             while (SB[p] == 0u) p--;                                           // (word 0 holds bit 0: the member's first symbol)
             carry = 32u * p + 31u - (uint32_t)__clz((int)SB[p]);
         }
-#if IW_CP_FILL_LEAN
-        carry = (uint32_t)__builtin_amdgcn_readfirstlane((int)carry);
-#endif
         const uint32_t c_end = min(isize, c0 + 4096u);
         constexpr uint32_t FS = IW_CP_FILL_STEPS;                              // steps (64 cells each) in flight: their LDS round trips overlap
         for (; c0 < c_end; c0 += 64u * FS) {
@@ -878,15 +862,7 @@ __device__ __forceinline__ void copy_member(uint16_t* __restrict__ W, uint32_t* 
 #pragma unroll
             for (uint32_t f = 0; f < FS; f++) {
                 const uint32_t w0 = min((c0 >> 5) + 2u * f, 2048u);              // (behind the member's cells: the two zero words)
-#if IW_CP_FILL_LEAN
-                // (NOT MEASURED YET -- built on the round's last day without a device to run it on; tools/hwtests/build_iw_variants.sh
-                //  lean="-DIW_CP_FILL_LEAN=1": the step's start bits as scalars, so that what depends on them alone -- the start
-                //  carried into the next step -- is scalar code)
-                m[f] = ((unsigned long long)(uint32_t)__builtin_amdgcn_readfirstlane((int)SB[w0 + 1u]) << 32) |
-                       (uint32_t)__builtin_amdgcn_readfirstlane((int)SB[w0]);
-#else
                 m[f] = ((unsigned long long)SB[w0 + 1u] << 32) | SB[w0];
-#endif
             }
 #pragma unroll
             for (uint32_t f = 0; f < FS; f++) {
@@ -919,7 +895,6 @@ __device__ __forceinline__ void copy_member(uint16_t* __restrict__ W, uint32_t* 
     if (meta.status == ST_OK) cp_first_tiles(first, sym + (size_t)mb_next * SYM_STRIDE, (uint32_t)tid, meta.ns);
     __syncthreads();
     if (s_bad || run != isize) { if (tid == 0) wstatus[m] = s_bad ? 17u : run < isize ? 16u : 18u; return; }
-    if (cut == 1u || cut == 4u || cut == 5u) { if (W[tid] == 0xFFFFu) wstatus[m] = ST_LANES; return; }
     if (prof) { const unsigned long long n = __builtin_amdgcn_s_memtime(); t_place = n - t_begin; tb = n; }
     // ---- resolve: pointer jumping; unit u (256 cells) is wave u % 16's, four stretches of 64 cells in flight per step ------------------------
     // (plain LDS accesses; the compiler may keep nothing of W in registers from one look at a cell to the next: the barrier below)
@@ -947,7 +922,6 @@ __device__ __forceinline__ void copy_member(uint16_t* __restrict__ W, uint32_t* 
         //  whatever its length; two units per step in flight -- 6 - 10 % slower.  profiles/r05h_inflate_copy_place_ab.txt)
     }
     __asm__ volatile("" ::: "memory");
-    if (cut == 2u) { if (W[tid] == 0xFFFFu) wstatus[m] = ST_LANES; return; }
     if (prof) { const unsigned long long n = __builtin_amdgcn_s_memtime(); t_res = n - tb; tb = n; }
     // ---- write: the wave's units, 16 bytes per lane and step (a unit = 16 lanes' worth: four units per step) -----------------------------
     uint8_t* const dst = out + o0;
@@ -979,7 +953,7 @@ __device__ __forceinline__ void copy_member(uint16_t* __restrict__ W, uint32_t* 
 template <bool MEASURE>
 __global__ __launch_bounds__(CP_THREADS) void k_inflate_copy(const uint32_t* __restrict__ sym, const uint32_t* __restrict__ n_sym,
                                                                         uint32_t* __restrict__ wstatus, const uint64_t* __restrict__ out_off,
-                                                                        uint32_t m0, uint32_t n_batch, uint8_t* __restrict__ out, uint32_t cut,
+                                                                        uint32_t m0, uint32_t n_batch, uint8_t* __restrict__ out,
                                                                         unsigned long long* __restrict__ prof)
 {
     __shared__ uint16_t W[65536];
@@ -993,11 +967,11 @@ __global__ __launch_bounds__(CP_THREADS) void k_inflate_copy(const uint32_t* __r
     if (meta.status == ST_OK) cp_first_tiles(first, sym + (size_t)blockIdx.x * SYM_STRIDE, threadIdx.x, meta.ns);
     for (uint32_t mb = blockIdx.x; mb < n_batch; mb += gridDim.x) {
 #if IW_CP_PREFETCH
-        copy_member<MEASURE>(W, SB, wsum, s_bad, mb, sym, n_sym, wstatus, out_off, m0, out, cut, prof, meta, first, mb + gridDim.x, n_batch);
+        copy_member<MEASURE>(W, SB, wsum, s_bad, mb, sym, n_sym, wstatus, out_off, m0, out, prof, meta, first, mb + gridDim.x, n_batch);
 #else
         meta = cp_meta(mb, n_batch, m0, n_sym, wstatus, out_off);
         if (meta.status == ST_OK) cp_first_tiles(first, sym + (size_t)mb * SYM_STRIDE, threadIdx.x, meta.ns);
-        copy_member<MEASURE>(W, SB, wsum, s_bad, mb, sym, n_sym, wstatus, out_off, m0, out, cut, prof, meta, first, n_batch, n_batch);
+        copy_member<MEASURE>(W, SB, wsum, s_bad, mb, sym, n_sym, wstatus, out_off, m0, out, prof, meta, first, n_batch, n_batch);
 #endif
         __syncthreads();                                                  // (every wave has written its bytes: the cells are the next member's)
     }
@@ -1010,9 +984,6 @@ int gci_inflate_wave_run(gci_ctx* ctx, const uint8_t* d_raw, const uint64_t* d_m
                          uint8_t* d_out, uint64_t out_cap, uint32_t* d_wstatus)
 {
     static const uint32_t batch_max = [] { const char* e = getenv("GCI_INFLATE_BATCH"); const int v = e ? atoi(e) : 16384; return (uint32_t)(v < 64 ? 64 : v); }();
-    static const int waves_per_cu = [] { const char* e = getenv("GCI_INFLATE_WAVES"); return e ? atoi(e) : 0; }();
-    static const uint32_t cut_a = [] { const char* e = getenv("GCI_IW_CUT_A"); return (uint32_t)(e ? atoi(e) : 0); }();   // (measurements)
-    static const uint32_t cut_b = [] { const char* e = getenv("GCI_IW_CUT_B"); return (uint32_t)(e ? atoi(e) : 0); }();
     static const bool want_prof = [] { const char* e = getenv("GCI_IW_PROF"); return e && atoi(e) != 0; }();
     unsigned long long* d_prof = nullptr;
     if (want_prof) {
@@ -1046,9 +1017,7 @@ int gci_inflate_wave_run(gci_ctx* ctx, const uint8_t* d_raw, const uint64_t* d_m
     if (st) return st;
     int cus = 0, per_cu = 0;
     HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
-    const bool measure = want_prof || cut_a || cut_b;
     HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_inflate_symbols<false>, 64, 0));
-    if (waves_per_cu > 0 && waves_per_cu < per_cu) per_cu = waves_per_cu;
     const uint32_t resident = (uint32_t)(cus > 0 && per_cu > 0 ? cus * per_cu : 1024);
     st = gci_ensure(ctx, ctx->inflate_lists, (size_t)resident * 64u * (MAXS + 1u) * sizeof(uint32_t));
     if (st) return st;
@@ -1075,13 +1044,13 @@ int gci_inflate_wave_run(gci_ctx* ctx, const uint8_t* d_raw, const uint64_t* d_m
         hipStream_t sm = second ? ctx->inflate_stream2 : ctx->stream;
         uint32_t* const symk = (uint32_t*)(second ? ctx->inflate_sym2.p : ctx->inflate_sym.p);
         uint32_t* const listk = (uint32_t*)(second ? ctx->inflate_lists2.p : ctx->inflate_lists.p);
-        hipLaunchKernelGGL(measure ? k_inflate_symbols<true> : k_inflate_symbols<false>, dim3(nb < resident ? nb : resident), dim3(64), 0, sm, d_raw,
+        hipLaunchKernelGGL(want_prof ? k_inflate_symbols<true> : k_inflate_symbols<false>, dim3(nb < resident ? nb : resident), dim3(64), 0, sm, d_raw,
                            d_member_pos, d_out_off, out_cap, m0, nb, symk, (uint32_t*)ctx->inflate_nsym.p, d_wstatus, listk,
-                           (uint32_t*)ctx->inflate_next.p + k, cut_a, d_prof);
+                           (uint32_t*)ctx->inflate_next.p + k, d_prof);
         LAUNCHCHK("k_inflate_symbols");
         const uint32_t copy_grid = copy_persistent && cus > 0 ? (nb < (uint32_t)cus ? nb : (uint32_t)cus) : nb;
-        hipLaunchKernelGGL(measure ? k_inflate_copy<true> : k_inflate_copy<false>, dim3(copy_grid), dim3(CP_THREADS), 0, sm, (const uint32_t*)symk,
-                           (const uint32_t*)ctx->inflate_nsym.p, d_wstatus, d_out_off, m0, nb, d_out, cut_b, d_prof);
+        hipLaunchKernelGGL(want_prof ? k_inflate_copy<true> : k_inflate_copy<false>, dim3(copy_grid), dim3(CP_THREADS), 0, sm, (const uint32_t*)symk,
+                           (const uint32_t*)ctx->inflate_nsym.p, d_wstatus, d_out_off, m0, nb, d_out, d_prof);
         LAUNCHCHK("k_inflate_copy");
     }
     if (two) {

@@ -537,7 +537,6 @@ __device__ __forceinline__ bool names_equal16(const uint8_t* __restrict__ pa, co
 struct PartJoinArgs {
     const PartEntry* in; const uint32_t* seg; const uint32_t* off2;
     uint32_t n_seg, n_bins2, slots, slot_shift;
-    uint32_t no_verify;          // GCI_JOIN_NOVERIFY=1 (timing experiments: what the name comparisons cost; results not exact)
 };
 
 // Slot of entry e (index i inside its bucket) in the bucket's LDS table.  CLAIM: take an empty slot for a name not seen yet.
@@ -785,7 +784,7 @@ __global__ __launch_bounds__(JB) __attribute__((amdgpu_waves_per_eu(4, 4))) void
             last[(size_t)slot * Fn + file] = PART_WIN | i;
             pay[(size_t)slot * Fn + file] = make_int4((int)(e.meta & cmask), e.start, e.end, e.qlen);
         }
-        if (!exact && !A.no_verify && ((uint32_t)(meta[slot] >> 1) & 0x7FFFFFu) != i) {
+        if (!exact && ((uint32_t)(meta[slot] >> 1) & 0x7FFFFFu) != i) {
             const unsigned long long cw = cname[slot];
             const uint32_t len = (uint32_t)(e.key >> 48) & 0xFFFu;
             const uint8_t* cn = F.f[(cw >> 48) & 15u].d_name_base + (((cw & 0xFFFFFFFFull) << 4) | ((cw >> 32) & 15ull));
@@ -920,7 +919,6 @@ static int name_join_partitioned(gci_ctx* ctx, const JoinFiles& F, uint64_t tota
     // slots per bucket table: what fits 64 KB of LDS with one order key and one 16-byte payload per file (two 512-thread
     // workgroups per CU, which is what their registers allow anyway)
     uint32_t S = 1024;
-    { const char* e = getenv("GCI_JOIN_SLOTS"); if (e && atoi(e) >= 128 && atoi(e) <= 1024 && !(atoi(e) & (atoi(e) - 1))) S = (uint32_t)atoi(e); }   // (A/B)
     while (S > 128 && (size_t)S * (16 + 24 * (size_t)F.n) > 65536) S >>= 1;
     // buckets: a load of at most 0.63 in the worst case (every name distinct), 0.15 - 0.3 for two files of the same reads
     uint64_t nb = 256;
@@ -974,7 +972,6 @@ static int name_join_partitioned(gci_ctx* ctx, const JoinFiles& F, uint64_t tota
         ProfScope _ps(ctx, GCI_PROF_JOIN_PART);
         PartJoinArgs A;
         A.in = pb; A.seg = seg; A.off2 = hist2; A.n_seg = B1; A.n_bins2 = B2; A.slots = S; A.slot_shift = (uint32_t)slot_shift;
-        { const char* nv = getenv("GCI_JOIN_NOVERIFY"); A.no_verify = nv && nv[0] == '1' ? 1u : 0u; }
         const size_t lds = (size_t)S * (16 + 24 * (size_t)F.n) + (size_t)S * 2;    // + the list of used slots
         const dim3 grid(B1 * B2), block(JB);
         const uint32_t NB = B1 * B2;

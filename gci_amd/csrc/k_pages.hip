@@ -183,7 +183,7 @@ __global__ __launch_bounds__(BLOCK) void k_pg_measure(const uint8_t* __restrict_
 }
 
 // A record's three runs of bytes -- name, CIGAR (kind 0 only), aux -- into the page in LDS, by the PG_LANES lanes of a group.  The
-// kernel is bound by the LATENCY of these loads (tools/hwtests/pages_ab.py: 0.60 of its 0.80 ms per quarter genome were this copy,
+// kernel is bound by the LATENCY of these loads (measured: 0.60 of its 0.80 ms per quarter genome were this copy,
 // and neither fewer load instructions -- one aligned dword per lane, the one behind it from the neighbour lane -- nor 4 / 16 lanes
 // per record changed that: every step of the loop waited for its own loads before the next step's were issued).  So the three runs are
 // ONE flat sequence of output dwords, and a lane asks for PG_UNROLL of them -- two aligned dwords each: the one that holds the first
@@ -249,11 +249,7 @@ __global__ __launch_bounds__(PG_BLOCK) void k_pg_write(const PgArgs A)
     __syncthreads();
     const uint32_t gl = t % PG_LANES, grp = t / PG_LANES;
     uint32_t used = rec0;
-#ifdef PG_CUT_RECORDS                  // (measurement builds: zero fill + write-out only)
-    for (uint32_t m0 = 0; m0 < 0; m0 += PG_META_MAX) {
-#else
     for (uint32_t m0 = 0; m0 < cnt; m0 += PG_META_MAX) {
-#endif
         const uint32_t mc = cnt - m0 < PG_META_MAX ? cnt - m0 : PG_META_MAX;
         // ---- phase A: one thread per record measures it (offset -> 10 aligned dwords: the only dependent trips to memory of the
         // page), leaves what the copy needs in LDS and writes the patched 36-byte core and the directory entry
@@ -282,7 +278,6 @@ __global__ __launch_bounds__(PG_BLOCK) void k_pg_write(const PgArgs A)
         }
         __syncthreads();
         // ---- phase B: PG_LANES lanes per record copy its name, CIGAR and aux bytes; nothing here waits for anything but its own loads
-#ifndef PG_CUT_COPY                    // (measurement builds, tools/hwtests/pages_ab.py: the kernel without its copy phase)
         for (uint32_t j0 = 0; j0 < mc; j0 += PG_BLOCK / PG_LANES) {
             const uint32_t jj = j0 + grp;
             if (jj >= mc) continue;
@@ -299,7 +294,6 @@ __global__ __launch_bounds__(PG_BLOCK) void k_pg_write(const PgArgs A)
             r2.at = c + (mt.kind == 0 ? a16(4u * mt.n_cig) : 16u);
             pg_copy_runs(A.bam, end, r0, r1, r2, dst, gl);
         }
-#endif
         __syncthreads();                                           // (s_meta is reused by the next pass)
     }
     if (cnt) used = rec0 + (uint32_t)(A.S[first + cnt] - S0) - 2u * cnt;

@@ -67,7 +67,7 @@ def _forget_pages(raw, lo: int, hi: int) -> None:
     (profiles/r04j_forget_pages_ab.txt).  pipeline._RunUploads therefore stages the file's bytes through pinned memory itself."""
     import mmap as _mmap
     mm = getattr(raw, "_mmap", None)
-    if mm is None or hi <= lo or not hasattr(mm, "madvise") or os.environ.get("GCI_FORGET_PAGES", "1") == "0":
+    if mm is None or hi <= lo or not hasattr(mm, "madvise"):
         return
     a = lo // _mmap.PAGESIZE * _mmap.PAGESIZE
     try:
@@ -91,22 +91,15 @@ class _Staging:
     def __init__(self, engine):
         # the loop over the slots is the library's (staging.cpp: gci_stage_send)
         self.engine = engine
-        self._fds = {}
         h = ctypes.c_void_p()
         engine._chk(engine.lib.gci_stage_create(engine.ctx, self.SLOT, self.SLOTS, self.THREADS, ctypes.byref(h)), "gci_stage_create")
         self.native = h
 
     def close(self):
-        """The ring's threads, pinned slots and events (gci_stage_free), and the descriptors the pread path kept open."""
+        """The ring's threads, pinned slots and events (gci_stage_free)."""
         if self.native is not None:
             self.engine.lib.gci_stage_free(self.native)
             self.native = None
-        for fd in self._fds.values():
-            try:
-                os.close(fd)
-            except OSError:
-                pass
-        self._fds.clear()
 
     def send(self, raw, p0: int, p1: int, dst: Buffer, stream, urgent: bool = True) -> None:
         """raw[p0:p1] -> dst[:p1 - p0] (device), enqueued on `stream`; returns when the last piece is enqueued.  A sender that is not
@@ -115,23 +108,8 @@ class _Staging:
         if self.native is not None:
             if p1 <= p0:
                 return
-            path = getattr(raw, "filename", None)
-            if path is not None and os.environ.get("GCI_STAGING_READ", "mmap") == "pread":
-                # the file's bytes by pread() into the slots (one descriptor per file, kept): no page faults on the mapping
-                fd = self._fds.get(path)
-                if fd is None:
-                    fd = self._fds[path] = os.open(path, os.O_RDONLY)
-                # where raw[0] lies in the file: a SLICE of a memmap keeps its parent's .offset (numpy: m[50:].offset == 0), so the
-                # position comes from the addresses -- first byte of this array minus first byte of the mapping's own array
-                whole = raw
-                while isinstance(getattr(whole, "base", None), np.ndarray):
-                    whole = whole.base
-                base = int(getattr(whole, "offset", 0)) + (raw.ctypes.data - whole.ctypes.data)
-                self.engine._chk(self.engine.lib.gci_stage_send_fd(self.engine.ctx, self.native, fd, base + p0, p1 - p0, ctypes.c_void_p(dst.data_ptr()),
-                                                                   ctypes.c_void_p(stream.cuda_stream), 1 if urgent else 0), "gci_stage_send_fd")
-                return
             src = raw.ctypes.data + p0                      # (a numpy array / memmap of uint8: its bytes as they lie)
-            forget = 1 if (getattr(raw, "_mmap", None) is not None and os.environ.get("GCI_FORGET_PAGES", "1") != "0") else 0
+            forget = 1 if getattr(raw, "_mmap", None) is not None else 0
             self.engine._chk(self.engine.lib.gci_stage_send(self.engine.ctx, self.native, ctypes.c_void_p(src), p1 - p0, ctypes.c_void_p(dst.data_ptr()),
                                                             ctypes.c_void_p(stream.cuda_stream), forget, 1 if urgent else 0), "gci_stage_send")
             return
@@ -185,12 +163,16 @@ class Engine:
         self._members_host = None                 # pinned staging buffer of depth_deflate()
         self._staging = None
         self._copy_stream = None
+        self._walk = None
         self._lock = threading.Lock()
         m = os.environ.get("GCI_JOIN", "")
         self.join_mode = 1 if m.startswith("c") else 2 if m.startswith("p") else 0    # what gci_ctx_create read
 
     def close(self) -> None:
         if getattr(self, "ctx", None):
+            walk, self._walk = getattr(self, "_walk", None), None
+            if walk is not None:
+                walk.close()
             st, self._staging = getattr(self, "_staging", None), None
             if st is not None and getattr(st, "engine", None) is self:     # (a side engine borrows the main engine's ring)
                 st.close()                                # before the context it was made with goes
@@ -235,7 +217,7 @@ class Engine:
         staging, copy = self.staging(), self.copy_stream()
         dst = self.T.empty(max(n, 1), self.T.uint8, self.device)
         copy.wait_stream(self.stream)
-        staging.send(a, 0, n, dst, copy, urgent=os.environ.get("GCI_FASTA_URGENT", "0") == "1")
+        staging.send(a, 0, n, dst, copy, urgent=False)
         self.stream.wait_stream(copy)
         return dst[:n]
 
@@ -251,6 +233,15 @@ class Engine:
             if self._copy_stream is None:
                 self._copy_stream = self.T.Stream(self.device)
             return self._copy_stream
+
+    def walk_engine(self) -> "Engine":
+        """The context that walks, pages and filters a run of a large file while this one inflates the next (pipeline.
+        _bam_join_input_gpu): a stream and scratch of its own (a gci_ctx is one stream and is not shared between streams), the same
+        provider and device.  Made on first use; close() closes it."""
+        with self._lock:
+            if self._walk is None:
+                self._walk = Engine(self.device.index or 0, stream=self.T.Stream(self.device))
+            return self._walk
 
     # ---- per-kernel HIP-event timing (library side, on the ctx stream) -------------------------
     def profile_enable(self, mask: int) -> None:
@@ -302,7 +293,7 @@ class Engine:
     def bam_pages(self, d_stream: Buffer, d_rec_off: Buffer, has_seq: bool, page_bytes: int = 0) -> "Pages":
         """The records of an inflated BAM stream (has_seq) or of a heads stream laid out as record pages: the bytes read_sam
         looks at, 16-byte aligned, no offset table -- what the record filter is fastest on."""
-        page_bytes = int(page_bytes or os.environ.get("GCI_PAGE_BYTES", 0) or _lib.PAGE_BYTES_DEFAULT)
+        page_bytes = int(page_bytes or _lib.PAGE_BYTES_DEFAULT)
         n = int(d_rec_off.shape[0])
         h = (ctypes.c_uint64 * 3)()
         self._chk(self.lib.gci_bam_pages_size(self.ctx, self._p(d_stream), int(d_stream.shape[0]), self._p(d_rec_off), n, int(has_seq),

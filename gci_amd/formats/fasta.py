@@ -127,8 +127,8 @@ def indexed(path: str):
         return _INDEXED[1], _INDEXED[2]
     # a large assembly is looked at through a mapping of the file (the title lines are found by threads that fault the page
     # cache's pages in sixteen at a time; the bytes go to the device through the pinned ring straight from it) instead of being
-    # read into 3 GB of fresh memory first (0.34 - 0.55 s of the command line at genome size); GCI_FASTA_LOAD=read: as before
-    if st.st_size >= (64 << 20) and os.environ.get("GCI_FASTA_LOAD", "mmap") == "mmap":
+    # read into 3 GB of fresh memory first (0.34 - 0.55 s of the command line at genome size)
+    if st.st_size >= (64 << 20):
         buf = np.memmap(path, dtype=np.uint8, mode="r")
     else:
         buf = load(path)

@@ -543,12 +543,12 @@ def _bam_join_input_gpu(engine: Engine, path: str, raw, members: _Members, ref_s
         upload = None
     # the bytes of run k + 1 travel while run k is inflated and filtered (the first run may be on its way already:
     # prefetch_member_tables); and (round 6) run k + 1 is INFLATED while run k is walked, paged and filtered: the inflate stays on this
-    # engine's stream, everything behind it runs on a second context with a stream of its own (_walk_engine), two output buffers in
+    # engine's stream, everything behind it runs on a second context with a stream of its own (Engine.walk_engine), two output buffers in
     # turns.  The partial record run k ends in is known only when run k has been walked -- by then run k + 1 is being inflated --, so
     # every run is inflated INGEST_HEADROOM bytes into its buffer and the carried bytes are put in front of it afterwards.
     ahead = uploads if uploads is not None else _RunUploads(engine, raw, members)
     T = engine.T
-    walk = _walk_engine(engine) if INGEST_OVERLAP else engine
+    walk = engine.walk_engine()
     parts: List[JoinInput] = []
     carry, start, n_done = None, hdr.first_record, 0
 
@@ -568,9 +568,8 @@ def _bam_join_input_gpu(engine: Engine, path: str, raw, members: _Members, ref_s
         ahead.release(k)
         ev = T.Event()
         ev.record(engine.stream)
-        if walk is not engine:
-            buf.record_stream(walk.stream)                   # (read over there: not handed out again before that is through)
-            status.record_stream(walk.stream)
+        buf.record_stream(walk.stream)                       # (read over there: not handed out again before that is through)
+        status.record_stream(walk.stream)
         phases.trace("run", k, t_take, t_got, phases.now())
         return dict(buf=buf, status=status, lo=lo, ev=ev)
 
@@ -616,9 +615,8 @@ def _bam_join_input_gpu(engine: Engine, path: str, raw, members: _Members, ref_s
                                 e.rec += n_done
                             raise
                         kept = _keep_part(walk, ji)
-                        if walk is not engine:                # (made in the walk stream's order, joined in the engine's)
-                            for t in (kept.recs, kept.name_base, kept.name_off):
-                                t.record_stream(engine.stream)
+                        for t in (kept.recs, kept.name_base, kept.name_off):    # (made in the walk stream's order, joined in the engine's)
+                            t.record_stream(engine.stream)
                         parts.append(kept)
                         n_done += int(d_off.shape[0])
                         del ji
@@ -629,29 +627,15 @@ def _bam_join_input_gpu(engine: Engine, path: str, raw, members: _Members, ref_s
             k += 1
     finally:
         ahead.close()
-        if walk is not engine:
-            engine.stream.wait_stream(walk.stream)           # (what the join reads was written over there)
+        engine.stream.wait_stream(walk.stream)               # (what the join reads was written over there)
     if carry is not None:
         raise bamfmt.BAMError("truncated BAM: %d trailing bytes do not form a record" % int(carry.shape[0]))
     return _concat_parts(engine, parts)
 
 
-# A large file's runs: run k + 1 is inflated while run k is walked, paged and filtered on a second context (GCI_INGEST_OVERLAP=0: one
-# after the other on one stream, as in rounds 3 - 5); the bytes kept free in front of every run's inflated bytes for the record the run
-# before it ended in (a longer one -- an ONT read of megabases -- is put together in a buffer of its own).
-INGEST_OVERLAP = os.environ.get("GCI_INGEST_OVERLAP", "1") != "0"
-INGEST_HEADROOM = int(os.environ.get("GCI_INGEST_HEADROOM", str(8 << 20)))
-_WALK_ENGINES: Dict[int, Engine] = {}
-
-
-def _walk_engine(engine: Engine) -> Engine:
-    """The context that walks, pages and filters a run while `engine` inflates the next one: a stream and scratch of its own (a gci_ctx is
-    one stream and is not shared between streams), the same provider and device."""
-    with _ENGINE_LOCK:
-        w = _WALK_ENGINES.get(id(engine))
-        if w is None:
-            w = _WALK_ENGINES[id(engine)] = Engine(engine.device.index or 0, stream=engine.T.Stream(engine.device))
-        return w
+# A large file's runs: the bytes kept free in front of every run's inflated bytes for the record the run before it ended in (a longer
+# one -- an ONT read of megabases -- is put together in a buffer of its own).
+INGEST_HEADROOM = 8 << 20
 
 
 _DROP_QUEUE = None
@@ -681,8 +665,7 @@ _TABLES: Dict[str, object] = {}        # path -> (memory map of the file, future
 
 def prefetch_member_tables(paths: Sequence[str]) -> None:
     """Start on the BAM files of a run before anything needs them, on a helper thread, file after file: the BGZF member table
-    (host threads over the mapping of the file; GCI_BGZF_TABLE=pread reads the headers through a descriptor instead -- no page
-    fault per member, but slower on the boxes measured) and, for a file that will go through the device run by run, the upload
+    (host threads over the mapping of the file) and, for a file that will go through the device run by run, the upload
     of its FIRST run.  The first file's table is made in pieces (_Members): its first run leaves as soon as the table of the
     file's beginning is there; a later file's as soon as the file in front of it has put its last run on the copy stream.  The
     command line calls this as soon as it knows its inputs, so what used to sit in front of a file's first byte on the device --
@@ -709,15 +692,12 @@ def prefetch_member_tables(paths: Sequence[str]) -> None:
     # (the first file's table is wanted as soon as the assembly has been scanned; the later ones have the seconds the file before
     # them takes on the device, and their threads would compete with the ones that stage that file's bytes: a quarter as many)
     many = hostio.default_threads()
-    by_fd = os.environ.get("GCI_BGZF_TABLE", "mmap") == "pread"     # (measured at genome size on tmpfs: pread 1.7 - 2.2 s, the mapping 1.2 - 1.4 s)
     first_run = os.environ.get("GCI_FIRST_RUN_AHEAD", "1") != "0"
 
     def table(path, raw, threads, limit=None, known=None):
         """The member table up to byte `limit` (None: all of the file); known = the table of a beginning of the file: only what lies
         behind it is walked."""
         with phases.wall("bgzf_member_table (ahead, on a helper thread)"):
-            if by_fd and limit is None and known is None:
-                return hostio.bgzf_blocks_file(path, threads=threads)
             begin = int(known[0][-1]) if known is not None else 0
             if begin >= int(raw.shape[0]):
                 return known
@@ -1060,7 +1040,7 @@ def filter(paf_files=[], bam_files=[], prefix="GCI", map_qual=30, mq_cutoff=50, 
     # file's last byte, were half a second of the command line with nothing beside them.
     early_track = None
     total_elems = sum((int(targets_length[t]) + _lib.GCI_TILE - 1) // _lib.GCI_TILE * _lib.GCI_TILE for t in targets)
-    if total_elems >= (1 << 26) and os.environ.get("GCI_EARLY_TRACK", "1") != "0":
+    if total_elems >= (1 << 26):
         early_track = engine.T.empty(max(total_elems, 1), engine.T.int32, engine.device)
     # the first file may have been started on already (start_ingest_ahead): its helper thread owns this context until it is done
     first_ahead = None
@@ -1273,8 +1253,8 @@ def _filter_sharded(paf_files, bam_files, prefix, map_qual, mq_cutoff, iden_perc
     by name hash to the rank that owns the name (two all-to-alls per file), joins the names it owns and routes the surviving
     intervals to the owners of their contigs (shard.ShardedJoin; round 2 replicated every record on every rank).
     PAF files are sharded by byte range (shard.paf_by_byte_range: every rank tokenises the lines of its range, the hits travel to
-    the rank that owns their query name and are scored there); GCI_PAF_SHARDING=whole keeps round 2's way (every rank filters the
-    whole files and keeps the names it owns), which is also what runs when a line raises."""
+    the rank that owns their query name and are scored there); when a line raises, every rank filters the whole files and keeps
+    the names it owns (round 2's way)."""
     from . import shard
     first = bamfmt.read_header(bam_files[0])
     pairs = [(r, l) for r, l in zip(first.references, first.lengths) if (len(chrs_list) == 0 or r in chrs_list)]
@@ -1293,10 +1273,8 @@ def _filter_sharded(paf_files, bam_files, prefix, map_qual, mq_cutoff, iden_perc
         if len(paf_files) != 0:
             # every rank tokenises 1 / world of the files' bytes; the hits are scored on the rank that owns their query name
             # (None: a line the reference raises on -- then every rank reads the whole files, and the exception comes out exact)
-            by_range = None
-            if PAF_SHARDING == "range":
-                by_range = shard.paf_by_byte_range(engine, paf_files, targets, map_qual, mq_cutoff, iden_percent, SHARD.world, SHARD.rank,
-                                                   SHARD.all_reduce_max, engine.device, via_host=SHARD.backend != "nccl")
+            by_range = shard.paf_by_byte_range(engine, paf_files, targets, map_qual, mq_cutoff, iden_percent, SHARD.world, SHARD.rank,
+                                               SHARD.all_reduce_max, engine.device, via_host=SHARD.backend != "nccl")
             try:
                 paf_inputs = by_range if by_range is not None else [
                     _own_names_only(engine, ji, SHARD.world, SHARD.rank)
@@ -1401,9 +1379,6 @@ def _reraise_like_reference(e: GciError):
         raise ZeroDivisionError("division by zero") from e
     raise e
 
-
-# Contig-sharded runs: "range" (default) = PAF files by byte range, "whole" = every rank the whole files.
-PAF_SHARDING = os.environ.get("GCI_PAF_SHARDING", "range")
 
 # `{prefix}.depth.gz` is written by the device: gzip members straight from the track or from the run lists the build kept
 # (gci_depth_deflate_*: no text buffer, a few MB cross PCIe).  (Rounds 1 - 5 kept the older way -- text rendered on the device, gzip on

@@ -254,6 +254,31 @@ def test_tables_and_first_runs_made_ahead_give_the_same_join_input(engine, oracl
     assert ji.recs.shape[0] == plain[0].recs.shape[0] and not pipeline._TABLES
 
 
+def test_walk_engine_belongs_to_its_engine(tmp_path, monkeypatch):
+    """Run-by-run ingestion walks its runs on a second context: the engine's own (Engine.walk_engine), made once, closed with
+    the engine -- not looked up by id() in a table that outlives it."""
+    from gci_amd.device import Engine
+    from gci_amd.formats import bam
+    contigs = (("a", 400_000),)
+    rs = synth.simulate_reads(contigs, 8, "hifi", seed=5).sorted()
+    stream, _ = synth.to_bam_stream(rs)
+    p = str(tmp_path / "f.bam")
+    bam.write_bam_stream(p, stream, level=1, threads=4)
+    monkeypatch.setattr(pipeline, "GPU_INFLATE_MAX", 0)          # run by run, in-process
+    eng = Engine(0)
+    try:
+        eng.set_layout([400_000])
+        ji = pipeline.bam_join_input(eng, p, ["a"], (30, 50, 0.1, 0.9), threads=4)
+        assert int(ji.recs.shape[0]) > 0
+        del ji
+        walk = eng._walk
+        assert walk is not None and walk is not eng and walk.ctx and eng.walk_engine() is walk
+        assert walk.T is eng.T and walk.device.index == eng.device.index and walk.stream is not eng.stream
+    finally:
+        eng.close()
+    assert walk.ctx is None
+
+
 @pytest.mark.parametrize("k1", ["pages", "stream"])
 def test_streamed_bam_ingestion_equals_one_shot(engine, oracle, tmp_path, monkeypatch, k1):
     """A BAM larger than the chunk budget is streamed: groups of BGZF members, partial records carried over, K1 per

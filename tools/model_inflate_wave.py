@@ -14,24 +14,100 @@
 Checks the result byte for byte against zlib for every member and prints what a kernel design needs: lanes that had to take a piece
 over, passes per batch of copies.  Usage: model_inflate_wave.py [members]"""
 import os, sys, tempfile, zlib
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
-import exp_inflate_resync as R
 from gci_amd import synth, hostio
 from gci_amd.formats import bam as bamfmt
 
 LANES, WINDOW, MIN_PIECE = 64, 1024, 2048       # (a piece shorter than the window a lane needs to fall into step is no piece)
 
 
+# ---- a bit-by-bit DEFLATE decoder (RFC 1951) ----
+LEN_BASE = [3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258]
+LEN_EXTRA = [0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0]
+DIST_EXTRA = [0, 0, 0, 0, 1, 1, 2, 2, 3, 3, 4, 4, 5, 5, 6, 6, 7, 7, 8, 8, 9, 9, 10, 10, 11, 11, 12, 12, 13, 13]
+DIST_BASE = [1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193, 12289, 16385, 24577]
+CLEN_ORDER = [16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15]
+
+
+class Bits:
+    def __init__(self, data, pos=0):
+        self.v = int.from_bytes(data, "little")
+        self.n = 8 * len(data)
+        self.pos = pos
+
+    def take(self, k):
+        x = (self.v >> self.pos) & ((1 << k) - 1)
+        self.pos += k
+        return x
+
+
+def make_code(lens):
+    """{(length, code): symbol} of a canonical Huffman code (RFC 1951 3.2.2)."""
+    cnt = [0] * 16
+    for l in lens:
+        cnt[l] += 1
+    cnt[0] = 0
+    nxt, code = [0] * 16, 0
+    for l in range(1, 16):
+        code = (code + cnt[l - 1]) << 1
+        nxt[l] = code
+    table = {}
+    for s, l in enumerate(lens):
+        if l:
+            table[(l, nxt[l])] = s
+            nxt[l] += 1
+    return table
+
+
+def decode_sym(b, table):
+    """One symbol, bit by bit (codes are packed most significant bit first); None: no such code within 15 bits / past the end."""
+    code = 0
+    for l in range(1, 16):
+        if b.pos >= b.n:
+            return None
+        code = (code << 1) | b.take(1)
+        s = table.get((l, code))
+        if s is not None:
+            return s
+    return None
+
+
+def read_block_header(b):
+    """-> (last, type, lit table, dist table) with b behind the header; stored blocks: tables None."""
+    last, typ = b.take(1), b.take(2)
+    if typ == 0:
+        return last, 0, None, None
+    if typ == 1:
+        return last, 1, make_code([8] * 144 + [9] * 112 + [7] * 24 + [8] * 8), make_code([5] * 30)
+    hlit, hdist, hclen = b.take(5) + 257, b.take(5) + 1, b.take(4) + 4
+    cl = [0] * 19
+    for i in range(hclen):
+        cl[CLEN_ORDER[i]] = b.take(3)
+    ct = make_code(cl)
+    lens = []
+    while len(lens) < hlit + hdist:
+        s = decode_sym(b, ct)
+        if s < 16:
+            lens.append(s)
+        elif s == 16:
+            lens += [lens[-1]] * (3 + b.take(2))
+        elif s == 17:
+            lens += [0] * (3 + b.take(3))
+        else:
+            lens += [0] * (11 + b.take(7))
+    return last, 2, make_code(lens[:hlit]), make_code(lens[hlit:hlit + hdist])
+
+
+
 def tokens_from(data, pos, lit, dist, stop_at, limit_bits):
     """Decode from bit `pos` until the position reaches stop_at (a symbol that starts in front of it is finished), end of block, or an
     undecodable spot -> [(start bit, kind, a, b)], kind 0 literal (a = byte), 1 match (a = length, b = distance), 2 end of block."""
-    b = R.Bits(data, pos)
+    b = Bits(data, pos)
     out = []
     while b.pos < stop_at and b.pos < limit_bits:
         at = b.pos
-        s = R.decode_sym(b, lit)
+        s = decode_sym(b, lit)
         if s is None or s > 285:
             b.pos = at + 1
             out.append((at, 3, 0, 0))                      # nothing decodable here: one bit on (only ever on a wrong path)
@@ -42,22 +118,22 @@ def tokens_from(data, pos, lit, dist, stop_at, limit_bits):
             out.append((at, 2, 0, 0))
             break
         else:
-            ln = R.LEN_BASE[s - 257] + b.take(R.LEN_EXTRA[s - 257])
-            d = R.decode_sym(b, dist)
+            ln = LEN_BASE[s - 257] + b.take(LEN_EXTRA[s - 257])
+            d = decode_sym(b, dist)
             if d is None or d > 29:
                 b.pos = at + 1
                 out.append((at, 3, 0, 0))
                 continue
-            out.append((at, 1, ln, R.DIST_BASE[d] + b.take(R.DIST_EXTRA[d])))
+            out.append((at, 1, ln, DIST_BASE[d] + b.take(DIST_EXTRA[d])))
     return out, b.pos
 
 
 def inflate_member(data, stats):
     nbits = 8 * len(data)
-    b = R.Bits(data)
+    b = Bits(data)
     toks = []                                              # the member's true token sequence, block after block
     while True:
-        last, typ, lit, dist = R.read_block_header(b)
+        last, typ, lit, dist = read_block_header(b)
         if typ == 0:
             b.pos = (b.pos + 7) & ~7
             ln = b.take(16); b.take(16)
@@ -85,7 +161,7 @@ def inflate_member(data, stats):
                     toks += [(t[1], t[2], t[3]) for t in mine[:eob]]
                     stats["lanes_used"].append(k + 1)
                     # where the block ends: behind the end-of-block code
-                    bb = R.Bits(data, mine[eob][0]); R.decode_sym(bb, lit); block_end = bb.pos
+                    bb = Bits(data, mine[eob][0]); decode_sym(bb, lit); block_end = bb.pos
                     break
                 toks += [(t[1], t[2], t[3]) for t in mine]
                 pos = ends[k]                              # lane k stands here, inside piece k + 1 (or at its start)
@@ -109,7 +185,7 @@ def inflate_member(data, stats):
                 if run and run[-1][1] == 2:                # the block ended in the overrun
                     toks += [(t[1], t[2], t[3]) for t in run[:-1]]
                     stats["lanes_used"].append(k + 1)
-                    bb = R.Bits(data, run[-1][0]); R.decode_sym(bb, lit); block_end = bb.pos
+                    bb = Bits(data, run[-1][0]); decode_sym(bb, lit); block_end = bb.pos
                     break
                 toks += [(t[1], t[2], t[3]) for t in run]
                 if p is None:                              # taken over: go on behind the neighbour's piece
