@@ -128,6 +128,8 @@ EXPORTS = [
     ("gci_depth_sum", c_int, [c_void_p, c_void_p, c_void_p]),
     ("gci_range_sums", c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p]),
     ("gci_fasta_n_scan", c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p]),
+    ("gci_depth_text_index", c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p]),
+    ("gci_depth_text_parse", c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_uint32, c_void_p, c_uint64]),
     ("gci_paf_filter", c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, ctypes.c_double, c_int, c_void_p, c_void_p]),
     ("gci_paf_count", c_uint64, [c_void_p, c_int]),
     ("gci_paf_name_bytes", c_uint64, [c_void_p, c_int]),
@@ -176,6 +178,12 @@ EXPORTS = [
     ("gci_fasta_titles", c_int, [c_void_p, c_uint64, c_int, c_void_p, c_uint64, POINTER(c_uint64)]),
     ("gci_gzip_bound", c_uint64, [c_uint64, c_uint64]),
     ("gci_gzip_members", c_int, [c_void_p, c_uint64, c_uint64, c_int, c_int, c_void_p, c_uint64, POINTER(c_uint64)]),
+    ("gci_gz_inflate", c_int, [c_void_p, c_uint64, c_int, POINTER(c_void_p)]),
+    ("gci_gz_bytes", c_uint64, [c_void_p]),
+    ("gci_gz_members", c_uint64, [c_void_p]),
+    ("gci_gz_serial", c_int, [c_void_p]),
+    ("gci_gz_export", c_int, [c_void_p, c_uint64, c_uint64, c_void_p, c_int]),
+    ("gci_gz_free", c_int, [c_void_p]),
 ]
 
 _lib = None

@@ -73,6 +73,8 @@ EXPORTS = [
     ("gci_depth_deflate_from_build", c_int, [c_void_p, c_void_p]),
     ("gci_depth_deflate_size", c_int, [c_void_p] * 4 + [c_uint32] + [c_void_p] * 4),
     ("gci_depth_deflate_write", c_int, [c_void_p] * 4 + [c_uint32] + [c_void_p] * 5 + [c_uint64]),
+    ("gci_depth_text_index", c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p]),
+    ("gci_depth_text_parse", c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_uint32, c_void_p, c_uint64]),
 ]
 
 
@@ -290,3 +292,27 @@ class CpuEngine:
         s = np.zeros(r.shape[0], dtype=np.int64)
         self._chk(self.lib.gci_range_sums(self.ctx, _p(track), _p(r), r.shape[0], _p(s)), "gci_range_sums")
         return s
+
+    # ---- the depth text back to a track (k_depth_parse.hip's twin)
+    def depth_text_index(self, text: np.ndarray) -> Tuple[np.ndarray, np.ndarray, int]:
+        """-> (uint32 line starts per 4096-byte tile, sorted uint64 header keys (offset << 12 | rank in tile), smallest offset of a
+        data line outside the strict grammar or 2**64 - 1)."""
+        text = np.ascontiguousarray(text, dtype=np.uint8)
+        tiles = np.zeros(max((text.shape[0] + 4095) // 4096, 1), dtype=np.uint32)
+        cap = 1 << 10
+        while True:
+            keys = np.zeros(cap, dtype=np.uint64)
+            nh, bad = np.zeros(1, dtype=np.uint32), np.zeros(1, dtype=np.uint64)
+            self._chk(self.lib.gci_depth_text_index(self.ctx, _p(text), text.shape[0], _p(tiles), _p(keys), cap, _p(nh), _p(bad)),
+                      "gci_depth_text_index")
+            if int(nh[0]) <= cap:
+                return tiles[:(text.shape[0] + 4095) // 4096], np.sort(keys[:int(nh[0])]), int(bad[0])
+            cap = int(nh[0])
+
+    def depth_text_parse(self, text: np.ndarray, tile_line0: np.ndarray, segs: np.ndarray, track: np.ndarray) -> np.ndarray:
+        text = np.ascontiguousarray(text, dtype=np.uint8)
+        line0 = np.ascontiguousarray(tile_line0, dtype=np.uint64)
+        segs = np.ascontiguousarray(segs, dtype=np.int64).reshape(-1, 3)
+        self._chk(self.lib.gci_depth_text_parse(self.ctx, _p(text), text.shape[0], _p(line0), _p(segs), segs.shape[0], _p(track),
+                                                track.shape[0]), "gci_depth_text_parse")
+        return track

@@ -777,3 +777,77 @@ int gci_depth_deflate_write(gci_ctx* ctx, const int32_t* depth, const uint64_t* 
 }
 
 }  // extern "C"
+
+/* ---- depth text -> track (k_depth_parse.hip): the same tiles, line ownership, keys and status word, on host threads ------------ */
+namespace {
+constexpr uint64_t PARSE_TILE = 4096;
+inline bool line_start(const uint8_t* text, uint64_t i) { return i == 0 || text[i - 1] == '\n'; }
+// [0-9]{1,10} then '\n' or the end of the text, value <= INT32_MAX -> value, or -1
+int64_t strict_value(const uint8_t* text, uint64_t i, uint64_t n)
+{
+    uint64_t v = 0, d = 0;
+    for (; d < 11 && i + d < n && text[i + d] >= '0' && text[i + d] <= '9'; d++) v = v * 10 + (uint64_t)(text[i + d] - '0');
+    const bool closed = i + d == n || text[i + d] == '\n';
+    return (d >= 1 && d <= 10 && closed && v <= 0x7FFFFFFFull) ? (int64_t)v : -1;
+}
+}  // namespace
+
+extern "C" {
+
+int gci_depth_text_index(gci_ctx* ctx, const uint8_t* text, uint64_t n, uint32_t* tile_lines, uint64_t* keys, uint32_t cap,
+                         uint32_t* n_hdr, uint64_t* bad)
+{
+    if (!ctx || !n_hdr || !bad || (n && (!text || !tile_lines)) || (cap && !keys)) return GCI_E_INVALID;
+    std::atomic<uint32_t> slots{0};
+    std::atomic<uint64_t> first_bad{~0ull};
+    parallel_blocks(ctx->threads, (n + PARSE_TILE - 1) / PARSE_TILE, 64, [&](uint64_t lo, uint64_t hi) {
+        for (uint64_t t = lo; t < hi; t++) {
+            uint32_t rank = 0;
+            for (uint64_t i = t * PARSE_TILE; i < std::min(n, (t + 1) * PARSE_TILE); i++) {
+                if (!line_start(text, i)) continue;
+                if (text[i] == '>') {
+                    const uint32_t s = slots.fetch_add(1);
+                    if (s < cap) keys[s] = (i << 12) | rank;
+                } else if (strict_value(text, i, n) < 0) {
+                    uint64_t cur = first_bad.load();
+                    while (i < cur && !first_bad.compare_exchange_weak(cur, i)) {}
+                }
+                rank++;
+            }
+            tile_lines[t] = rank;
+        }
+    });
+    *n_hdr = slots.load();
+    *bad = first_bad.load();
+    return GCI_OK;
+}
+
+int gci_depth_text_parse(gci_ctx* ctx, const uint8_t* text, uint64_t n, const uint64_t* tile_line0, const int64_t* segs, uint32_t n_segs,
+                         int32_t* track, uint64_t track_n)
+{
+    if (!ctx || (n && (!text || !tile_line0)) || (n_segs && !segs) || (track_n && !track)) return GCI_E_INVALID;
+    if (!n || !n_segs || !track_n) return GCI_OK;
+    parallel_blocks(ctx->threads, (n + PARSE_TILE - 1) / PARSE_TILE, 64, [&](uint64_t lo, uint64_t hi) {
+        for (uint64_t t = lo; t < hi; t++) {
+            uint64_t g = tile_line0[t];
+            for (uint64_t i = t * PARSE_TILE; i < std::min(n, (t + 1) * PARSE_TILE); i++) {
+                if (!line_start(text, i)) continue;
+                const uint64_t line = g++;
+                if (text[i] == '>') continue;
+                uint32_t a = 0, b = n_segs;                 // the last segment whose first data line is <= line
+                while (a < b) { const uint32_t m = (a + b) / 2; if ((uint64_t)segs[3 * m] <= line) a = m + 1; else b = m; }
+                if (a == 0) continue;
+                const int64_t* s = segs + 3 * (a - 1);
+                if (s[2] < 0 || (int64_t)line >= s[0] + s[1]) continue;
+                const int64_t e = s[2] + ((int64_t)line - s[0]);
+                if ((uint64_t)e >= track_n) continue;
+                uint32_t v = 0;
+                for (uint64_t d = 0; d < 10 && i + d < n && text[i + d] >= '0' && text[i + d] <= '9'; d++) v = v * 10 + (uint32_t)(text[i + d] - '0');
+                track[e] = (int32_t)v;
+            }
+        }
+    });
+    return GCI_OK;
+}
+
+}  // extern "C"

@@ -1122,3 +1122,176 @@ extern "C" int gci_fasta_titles(const uint8_t* h_text, uint64_t n, int threads, 
     for (auto& f : found) for (uint64_t v : f) h_pos[k++] = v;
     return GCI_OK;
 }
+
+// ---- a generic multi-member gzip file (`.depth.gz`), members inflated in parallel -----------------------------------------------
+// Neither writer of a .depth.gz puts the member size in the header (this project: a '>name' member, then members of ~0.8 MB of
+// text from k_deflate.hip; the reference: one member per (contig, thread chunk) from Python's gzip at level 9 with FNAME), so
+// the member starts are not known in advance.  Every byte position that looks like one (1f 8b 08, a flag byte without reserved
+// bits) is a candidate, and the candidates are inflated side by side, each to its end or its first error (a candidate inside a
+// member's payload almost always fails within a few bytes).  The text is the chain of successful members that starts at offset 0,
+// each beginning where the one before it ended (NUL padding skipped).  When no chain closes, one serial pass decides.
+struct gci_gz {
+    struct Member {
+        uint64_t pos = 0, end = 0;                  // compressed bytes [pos, end)
+        uint8_t* data = nullptr;                    // inflated bytes (malloc'd)
+        uint64_t size = 0;
+        bool ok = false;
+    };
+    std::vector<Member> chain;
+    std::vector<uint64_t> out_off;                  // chain.size() + 1
+    bool serial = false;
+    ~gci_gz()
+    {
+        for (auto& m : chain) free(m.data);
+    }
+};
+
+namespace {
+
+// inflate ONE gzip member starting at raw[pos]: on success m.ok, m.end, m.data / m.size (CRC-32 and ISIZE checked by zlib)
+void gz_member(const uint8_t* raw, uint64_t n, uint64_t pos, gci_gz::Member& m)
+{
+    m.pos = pos;
+    z_stream zs;
+    memset(&zs, 0, sizeof zs);
+    if (inflateInit2(&zs, 16 + 15) != Z_OK) return;
+    uint64_t cap = 1u << 16, got = 0, in_at = pos;
+    uint8_t* buf = (uint8_t*)malloc(cap);
+    int r = Z_OK;
+    while (buf) {
+        if (zs.avail_in == 0) {
+            const uint64_t left = n - in_at, take = left < (1ull << 30) ? left : (1ull << 30);
+            if (take == 0) break;                       // the file ends inside the member
+            zs.next_in = const_cast<Bytef*>(raw + in_at);
+            zs.avail_in = (uInt)take;
+            in_at += take;
+        }
+        if (got == cap) {
+            uint8_t* nb = (uint8_t*)realloc(buf, cap * 2);
+            if (!nb) { free(buf); buf = nullptr; break; }
+            buf = nb;
+            cap *= 2;
+        }
+        const uint64_t room = cap - got, give = room < (1ull << 30) ? room : (1ull << 30);
+        zs.next_out = buf + got;
+        zs.avail_out = (uInt)give;
+        r = inflate(&zs, Z_NO_FLUSH);
+        got += give - zs.avail_out;
+        if (r == Z_STREAM_END || (r != Z_OK && r != Z_BUF_ERROR)) break;
+        if (r == Z_BUF_ERROR && zs.avail_in == 0 && in_at == n) break;
+    }
+    if (buf && r == Z_STREAM_END) {
+        m.ok = true;
+        m.end = in_at - zs.avail_in;
+        m.data = buf;
+        m.size = got;
+    } else {
+        free(buf);
+    }
+    inflateEnd(&zs);
+}
+
+inline bool gz_candidate(const uint8_t* p) { return p[0] == 0x1f && p[1] == 0x8b && p[2] == 8 && (p[3] & 0xE0) == 0; }
+
+// the chain from offset 0 over successful candidates; false when it does not close
+bool gz_chain(const uint8_t* raw, uint64_t n, std::vector<gci_gz::Member>& cand, std::vector<gci_gz::Member>& chain)
+{
+    std::vector<uint64_t> at(cand.size());
+    for (size_t k = 0; k < cand.size(); k++) at[k] = cand[k].pos;
+    uint64_t pos = 0;
+    while (pos < n) {
+        const auto it = std::lower_bound(at.begin(), at.end(), pos);
+        if (it == at.end() || *it != pos) return false;
+        gci_gz::Member& m = cand[(size_t)(it - at.begin())];
+        if (!m.ok) return false;
+        chain.push_back(m);
+        m.data = nullptr;                               // (moved into the chain)
+        pos = m.end;
+        while (pos < n && raw[pos] == 0) pos++;         // Python's gzip reader skips NUL padding behind a member
+    }
+    return true;
+}
+
+}  // namespace
+
+extern "C" int gci_gz_inflate(const uint8_t* h_raw, uint64_t n_raw, int threads, gci_gz** out)
+{
+    if (!out || (!h_raw && n_raw)) return GCI_E_INVALID;
+    *out = nullptr;
+    if (threads < 1) threads = 1;
+    auto* g = new (std::nothrow) gci_gz;
+    if (!g) return GCI_E_NOMEM;
+    // candidate member starts, slice by slice
+    const uint64_t slices = n_raw < (1u << 20) ? 1 : (uint64_t)threads * 4;
+    std::vector<std::vector<uint64_t>> found(slices);
+    parallel_for(slices, threads, [&](uint64_t i) {
+        const uint64_t a = n_raw * i / slices, b = n_raw * (i + 1) / slices;
+        const uint8_t* p = h_raw + a;
+        while (p < h_raw + b) {
+            p = (const uint8_t*)memchr(p, 0x1f, (size_t)(h_raw + b - p));
+            if (!p) break;
+            if ((uint64_t)(p - h_raw) + 10 <= n_raw && gz_candidate(p)) found[i].push_back((uint64_t)(p - h_raw));
+            p++;
+        }
+    });
+    std::vector<gci_gz::Member> cand;
+    for (auto& f : found) for (uint64_t v : f) { cand.emplace_back(); cand.back().pos = v; }
+    // every candidate inflated, one at a time per thread (members differ in size by 10^4: no static grain)
+    {
+        std::atomic<uint64_t> next{0};
+        auto worker = [&]() {
+            for (;;) {
+                const uint64_t k = next.fetch_add(1);
+                if (k >= cand.size()) return;
+                gz_member(h_raw, n_raw, cand[k].pos, cand[k]);
+            }
+        };
+        const int nt = (uint64_t)threads < cand.size() ? threads : (int)(cand.size() ? cand.size() : 1);
+        std::vector<std::thread> pool;
+        for (int t = 1; t < nt; t++) pool.emplace_back(worker);
+        worker();
+        for (auto& th : pool) th.join();
+    }
+    bool closed = gz_chain(h_raw, n_raw, cand, g->chain);
+    for (auto& m : cand) free(m.data);
+    cand.clear();
+    if (!closed) {                                      // one serial pass, member after member
+        for (auto& m : g->chain) free(m.data);
+        g->chain.clear();
+        g->serial = true;
+        uint64_t pos = 0;
+        while (pos < n_raw) {
+            gci_gz::Member m;
+            if (n_raw - pos >= 10 && gz_candidate(h_raw + pos)) gz_member(h_raw, n_raw, pos, m);
+            if (!m.ok) { delete g; return GCI_E_MALFORMED; }
+            g->chain.push_back(m);
+            pos = m.end;
+            while (pos < n_raw && h_raw[pos] == 0) pos++;
+        }
+    }
+    g->out_off.assign(g->chain.size() + 1, 0);
+    for (size_t k = 0; k < g->chain.size(); k++) g->out_off[k + 1] = g->out_off[k] + g->chain[k].size;
+    *out = g;
+    return GCI_OK;
+}
+
+extern "C" uint64_t gci_gz_bytes(const gci_gz* g) { return g ? g->out_off.back() : 0; }
+extern "C" uint64_t gci_gz_members(const gci_gz* g) { return g ? g->chain.size() : 0; }
+extern "C" int gci_gz_serial(const gci_gz* g) { return g && g->serial ? 1 : 0; }
+
+// bytes [first, first + n) of the text into h_out, members copied in parallel
+extern "C" int gci_gz_export(const gci_gz* g, uint64_t first, uint64_t n, uint8_t* h_out, int threads)
+{
+    if (!g || (!h_out && n) || first > g->out_off.back() || n > g->out_off.back() - first) return GCI_E_INVALID;
+    const uint64_t last = first + n;
+    const auto& off = g->out_off;
+    const uint64_t k0 = (uint64_t)(std::upper_bound(off.begin(), off.end(), first) - off.begin()) - 1;
+    parallel_for(g->chain.size() - (k0 < g->chain.size() ? k0 : g->chain.size()), threads, [&](uint64_t i) {
+        const uint64_t k = k0 + i;
+        const uint64_t a = off[k] > first ? off[k] : first, b = off[k + 1] < last ? off[k + 1] : last;
+        if (a < b) memcpy(h_out + (a - first), g->chain[k].data + (a - off[k]), (size_t)(b - a));
+    });
+    return GCI_OK;
+}
+
+extern "C" int gci_gz_free(gci_gz* g) { delete g; return GCI_OK; }

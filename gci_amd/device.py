@@ -890,6 +890,37 @@ class Engine:
             cap = nk
         return kept.cpu().numpy().view(np.uint32)[:tiles], np.sort(keys[:nk].cpu().numpy().view(np.uint64))
 
+    def depth_text_index(self, d_text: Buffer) -> Tuple[Buffer, np.ndarray, np.ndarray, int]:
+        """gci_depth_text_index + the exclusive scan of its tile counts (gci_dev_u32_scan_u64) over depth text in HBM
+        -> (device uint64 [n_tiles + 1] first line index of every tile, the same on the host, sorted uint64 header keys
+        (byte offset << 12 | rank in its tile), smallest byte offset of a data line outside the strict grammar or 2**64 - 1)."""
+        n = int(d_text.shape[0])
+        tiles = (n + 4095) // 4096
+        counts = self.T.empty(max(tiles, 1), self.T.int32, self.device)
+        bad = self.T.empty(1, self.T.int64, self.device)
+        cap = 1 << 12
+        while True:
+            keys = self.T.empty(cap, self.T.int64, self.device)
+            self._chk(self.lib.gci_depth_text_index(self.ctx, self._p(d_text), n, self._p(counts), self._p(keys), cap, self._p(self._count),
+                                                    self._p(bad)), "gci_depth_text_index")
+            nk = int(self._count.item())
+            if nk <= cap:
+                break
+            cap = nk
+        line0 = self.T.empty(tiles + 1, self.T.int64, self.device)
+        self._chk(self.lib.gci_dev_u32_scan_u64(self.device.index or 0, self._p(counts), tiles, self._p(line0),
+                                                ctypes.c_void_p(self.stream.cuda_stream)), "gci_dev_u32_scan_u64")
+        h_line0 = line0.cpu().numpy().view(np.uint64)
+        return line0, h_line0, np.sort(keys[:nk].cpu().numpy().view(np.uint64)), int(bad.cpu().numpy().view(np.uint64)[0])
+
+    def depth_text_parse(self, d_text: Buffer, d_line0: Buffer, segs: np.ndarray, track: Buffer) -> Buffer:
+        """gci_depth_text_parse: segs = int64 [n, 3] (first data line, data lines, track element of the first or -1), sorted."""
+        segs = np.ascontiguousarray(segs, dtype=np.int64).reshape(-1, 3)
+        d_segs = self.to_device(segs) if segs.shape[0] else None
+        self._chk(self.lib.gci_depth_text_parse(self.ctx, self._p(d_text), int(d_text.shape[0]), self._p(d_line0), self._p(d_segs),
+                                                int(segs.shape[0]), self._p(track), int(track.shape[0])), "gci_depth_text_parse")
+        return track
+
     def range_sums(self, track: Buffer, ranges: np.ndarray) -> np.ndarray:
         """Sum of the depths in each [begin, end) of track element indices (int64 [n, 2]) -> int64 [n]."""
         ranges = np.ascontiguousarray(ranges, dtype=np.int64).reshape(-1, 2)

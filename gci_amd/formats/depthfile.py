@@ -78,3 +78,76 @@ def read_depth_gz(path: str) -> Dict[str, np.ndarray]:
         name = bytes(data[starts[a] + 1:nl[a]]).decode()
         out[name] = vals[a + 1:b].copy()
     return out
+
+
+# ---- reading a .depth.gz back (GCI_score.py): host halves of the device parse (k_depth_parse.hip) ----------------------------------
+
+INT32_MIN, INT32_MAX = -(1 << 31), (1 << 31) - 1
+
+
+def header_name(line: bytes) -> str:
+    """The contig a header line names, by the reference's own expression (utility/GCI_score.py:26-31)."""
+    return line.decode("utf-8").strip().split(">")[-1]
+
+
+def _line_at(text: np.ndarray, at: int) -> bytes:
+    """The line of `text` that begins at byte `at`, with its '\\n'."""
+    k = 256
+    while True:
+        piece = text[at:at + k].tobytes()
+        j = piece.find(b"\n")
+        if j >= 0:
+            return piece[:j + 1]
+        if at + k >= text.shape[0]:
+            return piece
+        k *= 4
+
+
+def header_segments(text: np.ndarray, keys: np.ndarray, tile_line0: np.ndarray):
+    """The header lines of a text found by gci_depth_text_index -> (names in first-appearance order, their lengths, a callback
+    segs(offsets) -> int64 [n_headers, 3] (first data line, data lines, track element of the first or -1)), or None when the text
+    does not begin with a header line (the reference then raises: the slow path reproduces that).  A name that appears again
+    restarts its contig: its last segment wins and it keeps its first place (parse_depth's dict)."""
+    total_lines = int(tile_line0[-1])
+    if keys.shape[0] == 0:
+        return None
+    keys = keys.astype(np.uint64)
+    off = (keys >> np.uint64(12)).astype(np.int64)
+    line = tile_line0[off >> 12].astype(np.int64) + (keys & np.uint64(0xFFF)).astype(np.int64)
+    if int(line[0]) != 0:
+        return None
+    names = [header_name(_line_at(text, int(o))) for o in off.tolist()]
+    if any(nm == "" for nm in names):
+        return None                        # (a header naming '' is kept apart by parse_depth's `target != ''`: the slow path)
+    n_data = np.diff(np.concatenate([line, [total_lines]])) - 1
+    last = {nm: k for k, nm in enumerate(names)}
+    order = list(dict.fromkeys(names))
+    lengths = [int(n_data[last[nm]]) for nm in order]
+
+    def segs(offsets) -> np.ndarray:
+        base = {nm: int(o) for nm, o in zip(order, offsets)}
+        out = np.empty((len(names), 3), dtype=np.int64)
+        out[:, 0] = line + 1
+        out[:, 1] = n_data
+        out[:, 2] = [base[nm] if last[nm] == k else -1 for k, nm in enumerate(names)]
+        return out
+    return order, lengths, segs
+
+
+def parse_depth_lines(lines) -> Dict[str, object]:
+    """utility/GCI_score.py:23-37 statement for statement over an iterable of byte lines (a gzip file object or the inflated text):
+    the slow path for text outside the strict grammar (CRLF, blanks, '+7', ...) and the way a damaged file raises what the
+    reference raises.  -> {contig: int64 array}, in the reference's dict order."""
+    depths = {}
+    target = ""
+    for line in lines:
+        item = line.decode("utf-8").strip()
+        if item.startswith(">"):
+            if target != "":
+                depths[target] = np.array(depths[target])
+            target = item.split(">")[-1]
+            depths[target] = []
+        else:
+            depths[target].append(int(item))
+    depths[target] = np.array(depths[target])
+    return depths

@@ -155,16 +155,17 @@ def record_ids_indexed(path: str) -> List[str]:
     return [rid for rid, _, _ in indexed(path)[1]]
 
 
-def n_runs_device(engine, path: str) -> Tuple[List[str], Dict[str, List[Tuple[int, int]]]]:
+def n_runs_device(engine, path: str, lengths: bool = False):
     """n_runs() with the scan on the GPU (gci_fasta_n_scan): the file's bytes are uploaded as they are; the device
     returns the byte offsets where runs of N / n begin and end and how many bytes of every 4096-byte tile count as
-    sequence; the handful of offsets is turned into sequence coordinates here."""
+    sequence; the handful of offsets is turned into sequence coordinates here.  lengths: a third result, {id: sequence length}
+    (`len(record)` of SeqIO, a later record of the same id replacing the earlier one, as a dict does), from the same tile counts."""
     global _INDEXED
     buf, spans = indexed(path)
     _INDEXED = None
     ids = [rid for rid, _, _ in spans]
     if not spans:
-        return ids, {}
+        return (ids, {}, {}) if lengths else (ids, {})
     bodies = np.array([(b, e) for _, b, e in spans], dtype=np.int64)
     kept, keys = engine.fasta_n_scan(buf, bodies)
     before_tile = np.concatenate(([0], np.cumsum(kept, dtype=np.int64)))
@@ -196,6 +197,8 @@ def n_runs_device(engine, path: str) -> Tuple[List[str], Dict[str, List[Tuple[in
         if len(pos) & 1:                                   # the run reaches the end of the record
             pos.append(coord(e, r) - base)
         runs.setdefault(rid, []).extend((pos[i], pos[i + 1]) for i in range(0, len(pos), 2))
+    if lengths:
+        return ids, runs, {rid: coord(e, r) - coord(b, r) for r, (rid, b, e) in enumerate(spans)}
     return ids, runs
 
 

@@ -233,3 +233,50 @@ def paf_filter(paths, targets, map_qual: int, mq_cutoff: int, iden_percent: floa
         return out
     finally:
         lib.gci_paf_free(handle)
+
+
+class GzipText:
+    """The inflated text of a multi-member gzip file, held by the library (gci_gz_inflate): members found and inflated in
+    parallel on host threads.  export() copies a byte range of it; close() frees it."""
+
+    def __init__(self, raw, threads: int = 0):
+        lib = _lib.load()
+        buf = np.frombuffer(raw, dtype=np.uint8) if not isinstance(raw, np.ndarray) else np.ascontiguousarray(raw, dtype=np.uint8)
+        self._threads = int(threads or default_threads())
+        h = ctypes.c_void_p(None)
+        _chk(lib.gci_gz_inflate(buf.ctypes.data_as(ctypes.c_void_p), buf.shape[0], self._threads, ctypes.byref(h)), "gci_gz_inflate")
+        self._h = h
+        self.nbytes = int(lib.gci_gz_bytes(h))
+        self.members = int(lib.gci_gz_members(h))
+        self.serial = bool(lib.gci_gz_serial(h))
+
+    def export(self, first: int = 0, n: Optional[int] = None, out: Optional[np.ndarray] = None) -> np.ndarray:
+        n = self.nbytes - first if n is None else int(n)
+        if out is None:
+            out = np.empty(n, dtype=np.uint8)
+        _chk(_lib.load().gci_gz_export(self._h, int(first), n, out.ctypes.data_as(ctypes.c_void_p), self._threads), "gci_gz_export")
+        return out[:n]
+
+    def close(self) -> None:
+        if self._h is not None and self._h.value:
+            _lib.load().gci_gz_free(self._h)
+        self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:                                  # noqa: BLE001
+            pass
+
+
+def gzip_inflate(raw, threads: int = 0) -> np.ndarray:
+    """The whole text of a multi-member gzip byte string (GzipText, exported and freed).  GciError(GCI_E_MALFORMED): not a
+    valid gzip stream."""
+    with GzipText(raw, threads) as g:
+        return g.export()

@@ -1693,3 +1693,75 @@ def compute_index(targets_length={}, prefix="GCI", directory=".", force=False, m
             with open(reg_path, "w") as f:
                 f.write(text)
         print("Computing GCI scores for regions done!!!\n\n")
+
+
+# ==============================================================================================
+# GCI_score.py: a saved .depth.gz back to a track in HBM (utility/GCI_score.py:11-39)
+# ==============================================================================================
+
+def _upload_depths(engine: Engine, depths: Dict[str, np.ndarray]) -> Tuple[DepthTracks, Dict[str, int]]:
+    targets_length = {t: int(a.shape[0]) for t, a in depths.items()}
+    engine.set_layout(list(targets_length.values()))
+    host = np.zeros(max(engine.total, 1), dtype=np.int32)
+    for o, a in zip(engine.offsets, depths.values()):
+        host[o:o + a.shape[0]] = a
+    return DepthTracks(engine, targets_length, engine.to_device(host)), targets_length
+
+
+def read_depth_tracks(engine: Engine, path: str, ref_lengths: Optional[Dict[str, int]] = None
+                      ) -> Tuple[Optional[DepthTracks], Dict[str, int]]:
+    """parse_depth of the reference's GCI_score.py for a `.depth.gz` file -> (DepthTracks, {contig: length}).  The file is inflated
+    on host threads (hostio.GzipText), its text goes to HBM through the staging ring, the device checks the grammar and ranks the
+    lines (gci_depth_text_index), the host resolves the header lines into contigs and the device writes the track
+    (gci_depth_text_parse).  Text outside the strict grammar, and a file the native inflate refuses, take the reference's own
+    statements on the host (rare: hand-made files).  ref_lengths: when a contig of the file is not among them nothing is
+    uploaded and the tracks are None (the caller refuses the file)."""
+    from . import hostio
+    from .formats import depthfile
+    raw = np.fromfile(path, dtype=np.uint8)
+    try:
+        with phases.wall("depth_gz_inflate"):
+            gz = hostio.GzipText(raw, hostio.pick_threads(1))
+    except GciError:
+        import gzip
+        with gzip.open(path, "rb") as f:                 # raises what the reference's read raises (BadGzipFile, EOFError, zlib.error)
+            depths = depthfile.parse_depth_lines(f)
+        return _checked_upload(engine, depths, ref_lengths)
+    del raw
+    with phases.wall("depth_gz_export"), gz:                 # (the members' text into one host array; the members freed)
+        text = gz.export()
+    with phases.wall("depth_text_upload"):
+        d_text = engine.upload_staged(text) if text.shape[0] >= (256 << 20) else engine.to_device(text)
+    with phases.wall("depth_text_parse"):
+        d_line0, line0, keys, bad = engine.depth_text_index(d_text)
+        found = depthfile.header_segments(text, keys, line0) if bad == (1 << 64) - 1 else None
+        if found is None:
+            del d_text, d_line0
+            import io
+            return _checked_upload(engine, depthfile.parse_depth_lines(io.BytesIO(text.tobytes())), ref_lengths)
+        names, lengths, segs = found
+        targets_length = dict(zip(names, lengths))
+        if ref_lengths is not None and any(t not in ref_lengths for t in targets_length):
+            return None, targets_length
+        if any(L > depthfile.INT32_MAX for L in lengths):
+            sys.exit("ERROR!!! A contig of the depth file is longer than 2^31 - 1 bases, which is not supported")
+        engine.set_layout(lengths)
+        track = engine.T.zeros(max(engine.total, 1), engine.T.int32, engine.device)     # (the padding behind every contig too)
+        engine.depth_text_parse(d_text, d_line0, segs(engine.offsets), track)
+        del d_text, d_line0
+    return DepthTracks(engine, targets_length, track), targets_length
+
+
+def _checked_upload(engine: Engine, depths: Dict[str, np.ndarray], ref_lengths) -> Tuple[Optional[DepthTracks], Dict[str, int]]:
+    """The slow path's dict to the device, after the contig check -- and the one thing an int32 track cannot hold refused: a depth
+    outside the int32 range (GCI_score.py)."""
+    from .formats import depthfile
+    targets_length = {t: len(a) for t, a in depths.items()}
+    if ref_lengths is not None and any(t not in ref_lengths for t in targets_length):
+        return None, targets_length
+    for target, arr in depths.items():
+        if not isinstance(arr, np.ndarray):
+            sys.exit('ERROR!!! A header line of the depth file names the contig "" and is not the last one, which is not supported')
+        if arr.size and (int(arr.min()) < depthfile.INT32_MIN or int(arr.max()) > depthfile.INT32_MAX):
+            sys.exit(f'ERROR!!! The depth file holds a depth of "{target}" outside the 32-bit range (-2^31 .. 2^31 - 1), which is not supported')
+    return _upload_depths(engine, depths)

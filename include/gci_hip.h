@@ -419,6 +419,23 @@ int gci_range_sums(gci_ctx* ctx, const int32_t* d_depth, const int64_t* d_ranges
 int gci_fasta_n_scan(gci_ctx* ctx, const uint8_t* d_text, uint64_t n_bytes, const int64_t* d_body, uint32_t n_records,
                      uint32_t* d_tile_kept, uint64_t* d_keys, uint32_t cap, uint32_t* d_n_keys);
 
+/* ---- depth text -> track: the parse of utility/GCI_score.py:11-39 (k_depth_parse.hip) -------------------------------------
+ * d_text: inflated `.depth.gz` text, ('>' name '\n' (decimal '\n')^L)*.  Tiles of 4096 bytes; a line belongs to the tile that
+ * holds its first byte (offset 0 and every byte behind a '\n'; a last line without '\n' counts).  Two passes, no chain between
+ * workgroups:
+ *   gci_depth_text_index  d_tile_lines[k] = line starts in tile k; keys = (byte offset << 12) | rank of the line within its tile
+ *                         for every line whose first byte is '>' (*d_n_hdr may exceed cap: nothing is written beyond it, call
+ *                         again with more room); *d_bad = smallest byte offset of a data line outside [0-9]{1,10} followed by
+ *                         '\n' or the end of the text, or with a value above INT32_MAX -- UINT64_MAX if none.
+ *   gci_depth_text_parse  d_tile_line0 = exclusive scan of d_tile_lines (gci_dev_u32_scan_u64); d_segs = n_segs triples of int64
+ *                         (first data line index, data lines, track element of the first or -1 = skip), sorted by first line;
+ *                         every data line g of segment s goes to d_track[base + g - first] (element indices >= track_n are not
+ *                         written).  Only for text that gci_depth_text_index found valid. */
+int gci_depth_text_index(gci_ctx* ctx, const uint8_t* d_text, uint64_t n_bytes, uint32_t* d_tile_lines, uint64_t* d_hdr_keys,
+                         uint32_t cap, uint32_t* d_n_hdr, uint64_t* d_bad);
+int gci_depth_text_parse(gci_ctx* ctx, const uint8_t* d_text, uint64_t n_bytes, const uint64_t* d_tile_line0, const int64_t* d_segs,
+                         uint32_t n_segs, int32_t* d_track, uint64_t track_n);
+
 /* ---- host-side container helpers (no GPU work) ---------------------------------
  * The reference reaches BGZF / BAM through pysam/htslib (GCI.py:150-151) and writes gzip through Python's gzip
  * module (GCI.py:111).  All pointers are HOST pointers.
@@ -478,6 +495,19 @@ int gci_bam_record_offsets(const uint8_t* h_stream, uint64_t n, uint64_t* h_offs
 uint64_t gci_gzip_bound(uint64_t n, uint64_t chunk);
 int gci_gzip_members(const uint8_t* h_text, uint64_t n, uint64_t chunk, int level, int threads, uint8_t* h_out,
                      uint64_t cap, uint64_t* n_out);
+/* A generic multi-member gzip file (a `.depth.gz` of this project or of the reference: members without BSIZE, so not BGZF)
+ * inflated on `threads` host threads.  Candidate member starts (1f 8b 08 + a flag byte without reserved bits) are inflated
+ * speculatively side by side; the members accepted are the chain that starts at offset 0, each ending where the next begins
+ * (NUL padding between members and at the end is skipped, as Python's gzip reader does), CRC-32 and ISIZE checked by zlib.
+ * A chain that does not close falls back to ONE serial pass.  GCI_E_MALFORMED: the file is not a valid gzip stream (the caller
+ * reproduces the reference's exception).  The text stays with the handle: _export copies bytes [first, first + n) of it. */
+typedef struct gci_gz gci_gz;
+int gci_gz_inflate(const uint8_t* h_raw, uint64_t n_raw, int threads, gci_gz** out);
+uint64_t gci_gz_bytes(const gci_gz* g);                    /* inflated length */
+uint64_t gci_gz_members(const gci_gz* g);                  /* members of the chain */
+int gci_gz_serial(const gci_gz* g);                        /* 1: the parallel chain did not close, the serial pass made the text */
+int gci_gz_export(const gci_gz* g, uint64_t first, uint64_t n, uint8_t* h_out, int threads);
+int gci_gz_free(gci_gz* g);
 
 /* ---- N4 (second half, host): the PAF filter of filter(), GCI.py:211-254 --------------------------------------------
  * h_files[i] / n_bytes[i]: the bytes of PAF file i, in command-line order.  targets: the selected contigs (index =

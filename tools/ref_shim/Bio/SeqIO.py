@@ -7,6 +7,9 @@ class _Rec:
     def __init__(self, rid, seq):
         self.id, self.seq = rid, seq
 
+    def __len__(self):                       # len(record), as SeqRecord (utility/GCI_score.py reads the contig lengths so)
+        return len(self.seq)
+
 
 def parse(path, fmt):
     assert fmt == "fasta"
