@@ -20,7 +20,10 @@ contigs from both files.
 
 Launch:  python bench.py --gpus N --steps K --warmup W      (N > 1: re-launches itself under torch.distributed.run, one process per GPU)
          python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line.  A plain run does only what that line's headline needs: it generates the workload, warms up,
+times the K steps, writes --dump-outputs and prints.  `--full` adds everything else the benchmark measures or checks: the
+full-size parity against the oracle, the CPU baselines, the per-kernel breakdown, the fill ceiling, the rocm-smi samples
+and the other numbers of SURVEY 8(d).
 """
 from __future__ import annotations
 
@@ -69,9 +72,9 @@ def parse_args():
                     help="skip numbers (2) and (3) of SURVEY.md 8(d): the device pipeline incl. H2D / D2H and the "
                          "command-line wall time on a chr19 BAM with realistic SEQ / QUAL entropy")
     ap.add_argument("--only-step", action="store_true",
-                    help="genome workload: the timed step, its roofline and the full-size parity check only -- no window / command-line-"
-                         "shaped / in-flight legs (their k_tile_build launches write no text and would blur a profiler's per-kernel "
-                         "averages), no end-to-end numbers, no CPU baseline: what tools/round_profile.sh wraps in rocprofv3")
+                    help="with --full, genome workload: the timed step, its roofline and the full-size parity check only -- no window / "
+                         "command-line-shaped / in-flight legs (their k_tile_build launches write no text and would blur a profiler's "
+                         "per-kernel averages), no end-to-end numbers, no CPU baseline")
     ap.add_argument("--cli", action="store_true",
                     help="genome4 / diploid: also run the two-read-type COMMAND LINE on real files (BGZF BAMs + PAFs on tmpfs) and hold its "
                          "files against the oracle (SURVEY 8(d) number 3 for configs[3]); kept out of the default run")
@@ -115,11 +118,19 @@ def parse_args():
     ap.add_argument("--dump-outputs", metavar="DIR", default="",
                     help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64 / float32, at most 64 MB: "
                          "a fixed, seeded sample of the depth tracks and text); rank 0's outputs; not with --workload paf")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: the full-size parity against the oracle, the CPU "
+                         "baselines, the per-kernel breakdown, the kernels-only number (n1), the fill ceiling, the rocm-smi samples and the "
+                         "legs of SURVEY 8(d) (window / command-line-shaped / in-flight steps, n2, n3); --no-e2e, --no-cpu-baseline, "
+                         "--no-cli-genome and --only-step trim that.  Without it a run sets up, warms up, times the steps, writes "
+                         "--dump-outputs and prints the result line")
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
     if args.dump_outputs and args.workload == "paf":
         ap.error("--dump-outputs covers the filter+depth workloads, not --workload paf")
+    if args.cli and not args.full:
+        ap.error("--cli is one of the legs of --full (it holds the command line's files against the full-size parity's contigs)")
     return args
 
 
@@ -1638,13 +1649,20 @@ def paf_number(args):
             del out
     torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.steps
-    # ---- parity: chunk 0 (and the last chunk) against the oracle over the chunk's own text
+    recs = out[0].recs.cpu().numpy().reshape(-1).view(REC_DTYPE)
+    n_lines = K * int(nl.shape[0])
+    r = {"seconds_per_pass": dt, "pass_seconds": [round(x, 4) for x in passes], "paf_bytes": n_bytes, "lines": n_lines, "queries_out": int(recs.shape[0]), "chunks": K,
+         "ms_per_gb_of_text": dt * 1e3 / (n_bytes / 1e9), "text_gb_per_s": n_bytes / dt / 1e9, "lines_per_s": n_lines / dt,
+         "aligned_bases": K * aligned_chunk, "parity_vs_oracle_chunks": None, "parity": None,
+         "h2d_seconds_outside_the_pass": t_h2d, "generation_seconds": t_gen}
+    if not args.full:
+        return r
+    # ---- parity (--full): chunk 0 (and the last chunk) against the oracle over the chunk's own text
     with tempfile.TemporaryDirectory() as tmp:
         p = os.path.join(tmp, "chunk0.paf")
         chunk.tofile(p)
         want, want_hq = O.paf_filter([p], names, FILTER[0], FILTER[1], FILTER[3])
     want = want[0]
-    recs = out[0].recs.cpu().numpy().reshape(-1).view(REC_DTYPE)
     noff = out[0].name_off.cpu().numpy()
     ok = True
     for k in sorted({0, K - 1}):
@@ -1658,11 +1676,8 @@ def paf_number(args):
             ok = ok and nm[:5] == "c%04d" % k
         exp = {q: (s[0], s[1], s[2], s[3], q in want_hq) for q, s in want.items()}
         ok = ok and got == exp
-    n_lines = K * int(nl.shape[0])
-    return {"seconds_per_pass": dt, "pass_seconds": [round(x, 4) for x in passes], "paf_bytes": n_bytes, "lines": n_lines, "queries_out": int(recs.shape[0]), "chunks": K,
-            "ms_per_gb_of_text": dt * 1e3 / (n_bytes / 1e9), "text_gb_per_s": n_bytes / dt / 1e9, "lines_per_s": n_lines / dt,
-            "aligned_bases": K * aligned_chunk, "parity_vs_oracle_chunks": sorted({0, K - 1}), "parity": bool(ok),
-            "h2d_seconds_outside_the_pass": t_h2d, "generation_seconds": t_gen}
+    r.update(parity_vs_oracle_chunks=sorted({0, K - 1}), parity=bool(ok))
+    return r
 
 
 # ---- --dump-outputs: what the last timed step computed, for comparing two builds output for output ---------------------------
@@ -1737,6 +1752,7 @@ def dump_outputs(w, out_dir):
 
 
 def main():
+    t_start = time.perf_counter()
     args = parse_args()
     if args.paf_published_gb:
         h, n = (float(x) for x in args.paf_published_gb.split(","))
@@ -1756,7 +1772,7 @@ def main():
                             "algorithmic_bytes_per_launch": r["paf_bytes"]},
                "cpu_baseline": None, "paf": r}
         print(json.dumps(out), flush=True)
-        if not r["parity"]:
+        if r["parity"] is False:
             sys.exit("PARITY FAILURE: the PAF filter differs from the oracle")
         return
     import torch
@@ -1854,6 +1870,7 @@ def main():
     # on the device -> record pages -> K1 -> join -> depth build (+ decimal text) -> the issue-run boundaries on the host.
     for _, w_k, _ in [(eng, w, None)]:
         w_k.keys_to_host = not two_type
+    t_warm = time.perf_counter()
     for _ in range(max(1, args.warmup)):
         w.step()
     fence()
@@ -1868,13 +1885,13 @@ def main():
     for e_k, _, _ in lanes:
         e_k.profile_enable(1 << _lib.PROF_DEPTH_SCAN)      # HIP events around the dominant kernel only
         e_k.profile_read(reset=True)
-    smi_before = smi_sample() if rank == 0 else None
+    smi_before = smi_sample() if rank == 0 and args.full else None
     fence()
     t0 = time.perf_counter()
     run_steps(args.steps)
     fence()
     dt = time.perf_counter() - t0
-    smi_after = smi_sample() if rank == 0 else None
+    smi_after = smi_sample() if rank == 0 and args.full else None
     prof = {}
     for e_k, _, _ in lanes:
         for name, (ms, n) in e_k.profile_read(reset=True).items():
@@ -1925,15 +1942,17 @@ def main():
     except Exception:
         traffic = None
 
-    eng.profile_enable((1 << _lib.PROF_COUNT) - 1)
-    for _ in range(3):
-        w.step()
-    breakdown = {k: round(ms / n * 1e3, 2) for k, (ms, n) in eng.profile_read(reset=True).items()}   # us / launch
-    eng.profile_enable(0)
+    # ---- --full: the figures below take steps or launches of their own
+    breakdown, n1_ms, fill_gbs = None, None, None
+    if args.full:
+        eng.profile_enable((1 << _lib.PROF_COUNT) - 1)
+        for _ in range(3):
+            w.step()
+        breakdown = {k: round(ms / n * 1e3, 2) for k, (ms, n) in eng.profile_read(reset=True).items()}   # us / launch
+        eng.profile_enable(0)
     # number (1) of SURVEY 8(d) as rounds 3 - 5 reported it as `value`: the kernels alone over record pages made in front of the clock,
     # nothing copied to the host inside the step
-    n1_ms = None
-    if world == 1 and not two_type and getattr(w, "pages_in_step", False):
+    if args.full and world == 1 and not two_type and getattr(w, "pages_in_step", False):
         w.pages_in_step, w.keys_to_host = False, False
         w.step()
         fence()
@@ -1943,8 +1962,7 @@ def main():
         fence()
         n1_ms = (time.perf_counter() - t1) / max(3, args.steps // 2) * 1e3
         w.pages_in_step, w.keys_to_host = True, True
-    fill_gbs = None
-    if world == 1 and rank == 0 and algo_bytes > 0:
+    if args.full and world == 1 and rank == 0 and algo_bytes > 0:
         try:
             fill_gbs = fill_ceiling_gbs(eng, algo_bytes)
         except Exception:
@@ -1988,7 +2006,8 @@ def main():
                             if w.sharded else "local" if not w.exchange else
                             "local, validated by the exact cross-rank name check (hash all-to-all)" if not w.replicated_steps else
                             "replicated (all-gather of records + names)")},
-        "roofline": {"bound": "hbm", "kernel": "k_tile_build (depth + text write)", "achieved": achieved, "peak": HBM_PEAK_GBS,
+        "roofline": {"bound": "hbm", "kernel": "k_tile_build (depth write; no text in this workload)" if two_type else
+                     "k_tile_build (depth + text write)", "achieved": achieved, "peak": HBM_PEAK_GBS,
                      "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_source,
                      "algorithmic_bytes_per_launch": algo_bytes, "avg_launch_ms": scan_avg_ms, "launches": scan_n,
                      # what a plain fill of as many bytes reaches on this box in this process, and the kernel against THAT
@@ -2013,6 +2032,8 @@ def main():
             if w.sharded else "all_to_all_single (name-check hashes) + all_reduce of the per-contig sums"
             + (" + all_gather_into_tensor x 3 per file (replicated join)" if w.replicated_steps else ""))}
         out["cpu_baseline"] = None
+    elif not args.full:
+        out["cpu_baseline"] = None
     elif rank == 0 and world == 1 and two_type:
         names = w.inp.names
         chosen = ["chr14", "chr22", "chrM"] if args.workload == "genome4" else ["mat_chr14", "pat_chr21", "pat_chr22"]
@@ -2021,7 +2042,6 @@ def main():
         ok, chosen = parity_two_type(w, chosen)
         out["parity_vs_oracle_full_size"] = ok
         out["parity_contigs"] = chosen
-        out["roofline"]["kernel"] = "k_tile_build (depth write; no text in this workload)"
         out["cpu_baseline"] = None
         if ok and args.cli:
             inp2 = w.inp
@@ -2147,6 +2167,9 @@ def main():
     if rank == 0:
         sys.stdout.flush()
         print(json.dumps(out), flush=True)
+        print("bench: %.1f s set-up, %.1f s warm-up, %.2f s timed steps, %.1f s after them%s" % (
+            t_warm - t_start, t0 - t_warm, dt, time.perf_counter() - t0 - dt, "" if args.full else " (--full adds the other legs)"),
+            file=sys.stderr, flush=True)
     if dist.is_initialized():
         dist.destroy_process_group()
 

@@ -1,6 +1,6 @@
 """The driver's contract of bench.py on one GPU, at a scale that takes seconds: ONE JSON line on stdout with the metric of
-BASELINE.json, the roofline of the dominant kernel from HIP events over the timed region, the step-level roofline, the CPU
-baseline object, the three numbers of SURVEY.md 8(d) and the full-size parity verdict."""
+BASELINE.json, the roofline of the dominant kernel from HIP events over the timed region, the step-level roofline and, with
+--full, the CPU baseline object, the three numbers of SURVEY.md 8(d) and the full-size parity verdict."""
 import json
 import os
 import subprocess
@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_line_contract():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--scale", "0.02", "--steps", "4", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--scale", "0.02", "--steps", "4", "--warmup", "1", "--full"],
                        capture_output=True, text=True, timeout=1500, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -56,6 +56,24 @@ def test_bench_line_contract():
     assert 0 < sw["ms_per_step"] and sw["gbases_per_s"] > 0 and sw["k_tile_build_avg_launch_ms"] > 0 and 0 < sw["hbm_frac"] < 1
     two = d["two_steps_in_flight"]
     assert two["status_ok"] and two["same_track_as_one_in_flight"]
+
+
+def test_plain_bench_line():
+    """Without --full a run times its steps and prints the headline, as the full run states it, and nothing that takes runs of
+    its own: no parity, no CPU baseline, no per-kernel breakdown, no fill ceiling, no SURVEY 8(d) legs."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--scale", "0.02", "--steps", "4", "--warmup", "1"],
+                       capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["metric"] == "aligned Gbases/s through filter+depth pipeline (CHM13, 40x HiFi)" and d["unit"] == "Gbases/s"
+    assert d["higher_is_better"] is True and d["dtype"] == "int32" and d["steps"] == 4 and d["warmup"] == 1 and d["n_gpus"] == 1
+    assert abs(d["value"] - d["config"]["aligned_bases_per_step"] / (d["ms_per_step"] * 1e-3) / 1e9) < 1e-6 * d["value"]
+    assert d["roofline"]["launches"] == 4 and d["roofline"]["fill_ceiling_gbs"] is None
+    assert d["cpu_baseline"] is None and d["kernel_us_per_launch"] is None and d["config"]["n1_kernels_only_ms_per_step"] is None
+    for k in ("parity_vs_oracle_full_size", "survey_8d", "survey_window_step", "cli_shaped_step", "two_steps_in_flight"):
+        assert k not in d, k
 
 
 def test_bench_dump_outputs_repeat_from_run_to_run(tmp_path):

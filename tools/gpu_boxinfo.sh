@@ -9,7 +9,7 @@ tag=$(date +%H%M%S)
   rocm-smi --showmemorypartition --showcomputepartition 2>&1 | grep -v "^$" | head -20
   rocm-smi --showclocks 2>&1 | grep -E "sclk|mclk|fclk" | head -8
   rocm-smi --showpower --showtemp 2>&1 | grep -E "Power|Temp" | head -6
-  timeout 600 python bench.py --steps 10 --warmup 2 --no-e2e --no-cpu-baseline 2>/dev/null | python -c "
+  timeout 600 python bench.py --full --steps 10 --warmup 2 --no-e2e --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('ms_per_step', round(d['ms_per_step'],3), 'k_tile_build', d['roofline']['avg_launch_ms'], 'kernels', d['kernel_us_per_launch'])"
