@@ -84,8 +84,10 @@ struct gci_ctx {
     uint32_t conflict_parity = 0;           // which one the next call inserts into (the other one is clean by then)
     DevBuf text_lut;                        // uint32[TEXT_LUT]: decimal characters of 0..999
     DevBuf long_items;                      // K1: queue of long-CIGAR records + its counter
-    DevBuf pg_cost, pg_scan, pg_first;      // record pages: per-record cost / blob bytes, their scans, first record of a page
+    DevBuf pg_scan, pg_first;               // record pages: scans of the records' costs and blob bytes, start and first record of a page
     uint32_t pg_n_rec = 0, pg_page_bytes = 0, pg_n_pages = 0;
+    uint32_t pg_cus = 0;                    // compute units of the device (k_pg_write's grid; asked for once)
+    uint32_t pg_per_cu = 0, pg_per_cu_page_bytes = 0;   // ... and workgroups of k_pg_write a CU holds, for pages of that size
     uint64_t pg_blob_off = 0;
     uint64_t pg_blob_bytes = 0;               // total size of the blob the size call measured (without its 16 guard bytes)
     std::vector<DevBuf> paf_pool;           // K2's scratch, in the order a call asks for it (k_paf.hip: PafScratch)

@@ -77,17 +77,25 @@ __device__ __forceinline__ PgRec pg_measure(const uint8_t* __restrict__ bam, uin
     return r;
 }
 
-// page_first[k] = first record whose cost offset is >= k * Q (k = n_pages: n_rec)
-__global__ __launch_bounds__(BLOCK) void k_pg_first(const unsigned long long* __restrict__ S, uint32_t n_rec, uint32_t n_pages, uint32_t Q,
-                                                    uint32_t* __restrict__ page_first)
+// The two levels of the size pass's sums (k_pg_measure, below)
+struct PgSums { const uint32_t* S_loc; const unsigned long long* B_loc; const unsigned long long* blk; uint32_t nb; };   // blk: [0, nb) costs, [nb, 2 nb) blob
+__device__ __forceinline__ unsigned long long pg_S(const PgSums& s, uint32_t i) { return s.S_loc[i] + s.blk[i / TILE]; }
+__device__ __forceinline__ unsigned long long pg_B(const PgSums& s, uint32_t i) { return s.B_loc[i] + s.blk[s.nb + i / TILE]; }
+
+// page_first[k] = first record whose cost offset is >= k * Q (k = n_pages: n_rec); page_off[k] = where that record starts in the
+// stream (k = n_pages: n_bytes), which is all the page writer needs to ask for a page's bytes
+__global__ __launch_bounds__(BLOCK) void k_pg_first(const PgSums S, uint32_t n_rec, uint32_t n_pages, uint32_t Q,
+                                                    const uint64_t* __restrict__ rec_off, uint64_t n_bytes,
+                                                    uint32_t* __restrict__ page_first, uint64_t* __restrict__ page_off)
 {
     const uint32_t k = blockIdx.x * BLOCK + threadIdx.x;
     if (k > n_pages) return;
-    if (k == n_pages) { page_first[k] = n_rec; return; }
+    if (k == n_pages) { page_first[k] = n_rec; page_off[k] = n_bytes; return; }
     const unsigned long long want = (unsigned long long)k * Q;
     uint32_t lo = 0, hi = n_rec;                                 // first i in [0, n_rec] with S[i] >= want
-    while (lo < hi) { const uint32_t mid = lo + ((hi - lo) >> 1); if (S[mid] >= want) hi = mid; else lo = mid + 1; }
+    while (lo < hi) { const uint32_t mid = lo + ((hi - lo) >> 1); if (pg_S(S, mid) >= want) hi = mid; else lo = mid + 1; }
     page_first[k] = lo;
+    page_off[k] = lo < n_rec ? rec_off[lo] : n_bytes;
 }
 
 // the naturally aligned dword at address q of the stream [bam, end); bytes past the end read as zero
@@ -114,13 +122,10 @@ __device__ __forceinline__ uint32_t pg_src_dword(const uint8_t* __restrict__ bam
     return w;
 }
 
-#ifndef PG_LANES
-#define PG_LANES 8                     // lanes that copy one record into the page
-#endif
 struct PgArgs {
     const uint8_t* bam; uint64_t n_bytes; const uint64_t* rec_off; uint32_t n_rec; int has_seq;
-    const unsigned long long* S; const unsigned long long* B; const uint32_t* page_first;
-    uint32_t page_bytes; uint64_t blob_off; uint8_t* out;
+    PgSums sums; const uint32_t* page_first; const uint64_t* page_off;
+    uint32_t n_pages, page_bytes; uint64_t blob_off; uint8_t* out;
 };
 
 // What the copy phase needs of a record, left in LDS by the thread that measured it: where its three runs of bytes lie in the stream
@@ -128,28 +133,19 @@ struct PgArgs {
 struct PgMeta {
     uint64_t off, aux_off;
     uint16_t n_cig, aux_len, at;       // (aux_len <= 1024 for the kinds that are copied, n_cig is 16 bits in BAM, at < page_bytes <= 32768)
-    uint8_t lrn, kind;
+    uint8_t lrn, kind;                 // kind | PG_IN_* : which of the runs lie in the window
 };
+#define PG_IN_NAME 0x10u
+#define PG_IN_CIGAR 0x20u
+#define PG_IN_AUX 0x40u
 static_assert(sizeof(PgMeta) == 24, "PgMeta");
 #define PG_META_MAX 128                // records measured at a time (a page of 24 KiB holds ~58 HiFi records; tiny records: several passes)
 
-// pg_measure() from naturally aligned dword loads (the byte loads of the generic form are a dozen memory instructions per record):
-// the 36 core bytes as 10 aligned dwords re-aligned in registers.
-__device__ __forceinline__ PgRec pg_measure_fast(const uint8_t* __restrict__ bam, uint64_t n_bytes, uint64_t off, bool has_seq, uint32_t core[9])
+// What pg_measure() says of a record, from its 36 core bytes already in registers as nine dwords.
+__device__ __forceinline__ PgRec pg_classify(const uint32_t core[9], uint64_t n_bytes, uint64_t off, bool has_seq)
 {
     PgRec r;
     r.kind = PG_MALFORMED; r.size = 48; r.blob = 0; r.lrn = r.n_cig = r.aux_len = 0; r.aux_off = 0; r.short_core = false;
-#pragma unroll
-    for (int d = 0; d < 9; d++) core[d] = 0u;
-    if (off + 36 > n_bytes) { r.short_core = true; return r; }
-    const uint8_t* p = bam + off;
-    const uint32_t sh = (uint32_t)((uintptr_t)p & 3u);
-    const uint8_t* end = bam + n_bytes;
-    uint32_t w[10];
-#pragma unroll
-    for (int d = 0; d < 10; d++) w[d] = (d < 9 || sh) ? pg_ldw(p - sh + 4 * d, end) : 0u;
-#pragma unroll
-    for (int d = 0; d < 9; d++) core[d] = __builtin_amdgcn_alignbyte(w[d + 1], w[d], sh);
     const int32_t block_size = (int32_t)core[0];
     const uint32_t lrn = core[3] & 0xFFu, n_cig = core[4] & 0xFFFFu;
     const int32_t l_seq = (int32_t)core[5];
@@ -170,170 +166,437 @@ __device__ __forceinline__ PgRec pg_measure_fast(const uint8_t* __restrict__ bam
     return r;
 }
 
-__global__ __launch_bounds__(BLOCK) void k_pg_measure(const uint8_t* __restrict__ bam, uint64_t n_bytes, const uint64_t* __restrict__ rec_off,
-                                                      uint32_t n_rec, int has_seq, uint32_t* __restrict__ cost, uint32_t* __restrict__ blob)
+// The 36 core bytes of the record at stream offset off (off + 36 <= n_bytes) from naturally aligned dword loads (the byte loads of
+// pg_measure() are a dozen memory instructions per record): 10 aligned dwords re-aligned in registers.
+__device__ __forceinline__ void pg_core_gather(const uint8_t* __restrict__ bam, uint64_t n_bytes, uint64_t off, uint32_t core[9])
 {
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n_rec) return;
-    // (byte loads: pg_measure_fast's ten aligned dwords were measured SLOWER here -- 0.181 against 0.155 ms per quarter genome for the size
-    //  pass: one lane per record, every lane its own cache line, and the dozen byte loads of a lane hit that one line)
-    const PgRec r = pg_measure(bam, n_bytes, rec_off[i], has_seq != 0);
-    cost[i] = r.size + 2u;
-    blob[i] = r.blob;
+    const uint8_t* p = bam + off;
+    const uint32_t sh = (uint32_t)((uintptr_t)p & 3u);
+    const uint8_t* end = bam + n_bytes;
+    uint32_t w[10];
+#pragma unroll
+    for (int d = 0; d < 10; d++) w[d] = (d < 9 || sh) ? pg_ldw(p - sh + 4 * d, end) : 0u;
+#pragma unroll
+    for (int d = 0; d < 9; d++) core[d] = __builtin_amdgcn_alignbyte(w[d + 1], w[d], sh);
 }
 
-// A record's three runs of bytes -- name, CIGAR (kind 0 only), aux -- into the page in LDS, by the PG_LANES lanes of a group.  The
-// kernel is bound by the LATENCY of these loads (measured: 0.60 of its 0.80 ms per quarter genome were this copy,
-// and neither fewer load instructions -- one aligned dword per lane, the one behind it from the neighbour lane -- nor 4 / 16 lanes
-// per record changed that: every step of the loop waited for its own loads before the next step's were issued).  So the three runs are
-// ONE flat sequence of output dwords, and a lane asks for PG_UNROLL of them -- two aligned dwords each: the one that holds the first
-// byte and the one behind it -- BEFORE it uses any: sixteen loads in flight per lane where there were two, a typical HiFi record
-// (9 + 70 + 10 dwords) in two steps instead of thirteen (0.74 -> 0.44 ms).
-#ifndef PG_UNROLL
-#define PG_UNROLL 8
-#endif
-struct PgRun { uint64_t src; uint32_t len, n, at; };     // stream offset, bytes, dwords, offset in the record's page image
+// a dword at any byte address of LDS (gfx950 serves an unaligned ds_read_b32: tools/hwtests/lds_unaligned.hip)
+__device__ __forceinline__ uint32_t pg_lds32(const uint8_t* p) { uint32_t v; __builtin_memcpy(&v, p, 4); return v; }
 
-__device__ __forceinline__ void pg_copy_runs(const uint8_t* __restrict__ bam, const uint8_t* end, const PgRun r0, const PgRun r1, const PgRun r2,
-                                             uint8_t* dst, uint32_t gl)
+// The size pass: S = exclusive sums of the costs (size + 2), B = exclusive sums of the blob bytes, over all records and with the totals
+// at index n_rec.  Kept in two levels, never added up in memory: k_pg_measure measures TILE records per workgroup and leaves the sums
+// LOCAL to the workgroup (the cost sums fit 32 bits) and both totals of it, k_pg_blk_scan -- one workgroup -- turns the totals into what
+// lies in front of every workgroup; pg_S / pg_B add the two.  (Before: the costs and blob bytes written out as arrays, a two-kernel
+// scan over each, 64-bit sums read and written once more to add the block prefixes: 5 launches and ~0.5 GB of traffic per HiFi file.)
+// grid: n_rec / TILE + 1 workgroups (index n_rec, the totals, is an entry like any other: a record that costs nothing)
+__global__ __launch_bounds__(BLOCK) void k_pg_measure(const uint8_t* __restrict__ bam, uint64_t n_bytes, const uint64_t* __restrict__ rec_off,
+                                                      uint32_t n_rec, int has_seq, uint32_t* __restrict__ S_loc,
+                                                      unsigned long long* __restrict__ B_loc, unsigned long long* __restrict__ blk_tot, uint32_t nb)
 {
-    const uint32_t total = r0.n + r1.n + r2.n;
-    for (uint32_t f0 = 0; f0 < total; f0 += PG_UNROLL * PG_LANES) {
-        uint32_t lo[PG_UNROLL], hi[PG_UNROLL], sh[PG_UNROLL], left[PG_UNROLL], where[PG_UNROLL];
-#pragma unroll
-        for (int u = 0; u < PG_UNROLL; u++) {
-            const uint32_t f = f0 + u * PG_LANES + gl;
-            const bool in0 = f < r0.n, in1 = f < r0.n + r1.n;
-            const uint64_t src = in0 ? r0.src : in1 ? r1.src : r2.src;
-            const uint32_t len = in0 ? r0.len : in1 ? r1.len : r2.len;
-            const uint32_t d = in0 ? f : in1 ? f - r0.n : f - r0.n - r1.n;
-            const uint32_t at = in0 ? r0.at : in1 ? r1.at : r2.at;
-            const uint8_t* p = bam + src + 4ull * d;
-            sh[u] = (uint32_t)((uintptr_t)p & 3u);
-            left[u] = f < total ? len - 4u * d : 0u;
-            where[u] = at + 4u * d;
-            lo[u] = f < total ? pg_ldw(p - sh[u], end) : 0u;
-            hi[u] = (f < total && sh[u]) ? pg_ldw(p - sh[u] + 4, end) : 0u;
+    __shared__ uint16_t s_cost[TILE];                                       // (a cost is at most 1026)
+    __shared__ uint32_t s_blob[TILE];
+    __shared__ unsigned long long wtot[2][BLOCK / 64];
+    const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const uint32_t base0 = blockIdx.x * TILE;
+    // a lane per record, neighbours in neighbouring lanes
+    // (byte loads: pg_core_gather's ten aligned dwords were measured SLOWER here -- 0.181 against 0.155 ms per quarter genome for the size
+    //  pass: every lane its own cache line, and the dozen byte loads of a lane hit that one line)
+    for (uint32_t r = 0; r < TILE / BLOCK; r++) {
+        const uint32_t e = r * BLOCK + t, i = base0 + e;
+        uint32_t c = 0, b = 0;
+        if (i < n_rec) {
+            const PgRec rec = pg_measure(bam, n_bytes, rec_off[i], has_seq != 0);
+            c = rec.size + 2u; b = rec.blob;
         }
-#pragma unroll
-        for (int u = 0; u < PG_UNROLL; u++) {
-            if (left[u]) {
-                uint32_t w = __builtin_amdgcn_alignbyte(hi[u], lo[u], sh[u]);
-                if (left[u] < 4u) w &= (1u << (8u * left[u])) - 1u;
-                *reinterpret_cast<uint32_t*>(dst + where[u]) = w;
-            }
-        }
+        s_cost[e] = (uint16_t)c; s_blob[e] = b;
     }
+    __syncthreads();
+    // the exclusive sums inside the workgroup: TILE / BLOCK consecutive records per thread
+    constexpr int PER = TILE / BLOCK;
+    uint32_t c[PER], b[PER];
+    uint32_t run_c = 0;
+    unsigned long long run_b = 0;
+#pragma unroll
+    for (int i = 0; i < PER; i++) { c[i] = s_cost[t * PER + i]; b[i] = s_blob[t * PER + i]; run_c += c[i]; run_b += b[i]; }
+    const uint32_t inc_c = wave_inclusive<uint32_t>(run_c, lane);
+    const unsigned long long inc_b = wave_inclusive<unsigned long long>(run_b, lane);
+    if (lane == 63) { wtot[0][wave] = inc_c; wtot[1][wave] = inc_b; }
+    __syncthreads();
+    uint32_t pre_c = inc_c - run_c, all_c = 0;
+    unsigned long long pre_b = inc_b - run_b, all_b = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < BLOCK / 64; w++) {
+        if (w < wave) { pre_c += (uint32_t)wtot[0][w]; pre_b += wtot[1][w]; }
+        all_c += (uint32_t)wtot[0][w]; all_b += wtot[1][w];
+    }
+    const uint32_t base = base0 + t * PER;
+#pragma unroll
+    for (int i = 0; i < PER; i++) {
+        if (base + i <= n_rec) { S_loc[base + i] = pre_c; B_loc[base + i] = pre_b; }
+        pre_c += c[i]; pre_b += b[i];
+    }
+    if (t == 0) { blk_tot[blockIdx.x] = all_c; blk_tot[nb + blockIdx.x] = all_b; }
+}
+
+// One workgroup: both rows of workgroup totals into exclusive sums, in place; then what the host reads back:
+// tot[0] = S[n_rec - 1], tot[1] = S[n_rec], tot[2] = B[n_rec].
+__global__ __launch_bounds__(BLOCK) void k_pg_blk_scan(unsigned long long* __restrict__ blk, uint32_t nb, const uint32_t* __restrict__ S_loc,
+                                                       const unsigned long long* __restrict__ B_loc, uint32_t n_rec,
+                                                       unsigned long long* __restrict__ tot)
+{
+    __shared__ unsigned long long wtot[2][BLOCK / 64];
+    const uint32_t t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    unsigned long long carry_c = 0, carry_b = 0;
+    for (uint32_t k0 = 0; k0 < nb; k0 += BLOCK) {
+        const uint32_t k = k0 + t;
+        const unsigned long long vc = k < nb ? blk[k] : 0ull, vb = k < nb ? blk[nb + k] : 0ull;
+        const unsigned long long ic = wave_inclusive<unsigned long long>(vc, lane), ib = wave_inclusive<unsigned long long>(vb, lane);
+        if (lane == 63) { wtot[0][wave] = ic; wtot[1][wave] = ib; }
+        __syncthreads();
+        unsigned long long pc = carry_c + ic - vc, pb = carry_b + ib - vb;
+#pragma unroll
+        for (uint32_t w = 0; w < BLOCK / 64; w++) {
+            if (w < wave) { pc += wtot[0][w]; pb += wtot[1][w]; }
+            carry_c += wtot[0][w]; carry_b += wtot[1][w];
+        }
+        if (k < nb) { blk[k] = pc; blk[nb + k] = pb; }
+        __syncthreads();                                           // (wtot is written again; the sums are read below)
+    }
+    if (t == 0) {
+        const PgSums s = {S_loc, B_loc, blk, nb};
+        tot[0] = pg_S(s, n_rec - 1); tot[1] = pg_S(s, n_rec); tot[2] = pg_B(s, n_rec);
+    }
+}
+
+// The window: the piece of the stream a workgroup staged in LDS with coalesced 16-byte loads (k_pg_write, below).
+struct PgWin { const uint8_t* lds; const uint8_t* lo; const uint8_t* hi; };     // LDS copy of the stream addresses [lo, hi); lo 16-byte aligned
+
+__device__ __forceinline__ bool pg_in_win(const PgWin& W, const uint8_t* p, uint32_t len) { return p >= W.lo && p + len <= W.hi; }
+
+// Sixteen bytes of the run of `len` bytes at stream offset src, from byte roff of it on (a multiple of 4); bytes beyond the run are
+// zero.  From the window, four ds_read_b32 at any byte alignment (up to 15 bytes behind the run are read and dropped: the window has
+// that much slack), or gathered from memory: two naturally aligned dwords per dword, re-aligned in registers.
+__device__ __forceinline__ uint4 pg_piece(const uint8_t* __restrict__ bam, uint64_t n_bytes, const PgWin& W, bool in_win, uint64_t src,
+                                          uint32_t len, uint32_t roff)
+{
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+    if (roff >= len) return make_uint4(0, 0, 0, 0);
+    if (in_win) {
+        const uint8_t* q = W.lds + (uint32_t)(bam + src - W.lo) + roff;
+        const uint32_t left = len - roff;
+#pragma unroll
+        for (int d = 0; d < 4; d++) {
+            w[d] = pg_lds32(q + 4 * d);
+            if (left < 4u * d + 4u) w[d] = left > 4u * d ? w[d] & ((1u << (8u * (left - 4u * d))) - 1u) : 0u;
+        }
+    } else {
+#pragma unroll
+        for (int d = 0; d < 4; d++) if (roff + 4u * d < len) w[d] = pg_src_dword(bam, n_bytes, src, len, roff / 4u + d);
+    }
+    return make_uint4(w[0], w[1], w[2], w[3]);
 }
 
 #ifndef PG_BLOCK
 #define PG_BLOCK BLOCK                 // threads of a k_pg_write workgroup
 #endif
-__global__ __launch_bounds__(PG_BLOCK) void k_pg_write(const PgArgs A)
+// The window: in a heads stream the records of a page are one contiguous piece of the stream, never longer than the page (the page
+// image of an inline record is not smaller than its source), so the workgroup copies that piece into LDS with one round of coalesced
+// 16-byte loads and takes cores, names, CIGARs and aux blocks from there.  Its capacity is page_bytes / PG_WIN_DIV.  A page takes as
+// many fills as it needs: each starts at its first record that is still to do and ends before the first record that starts behind
+// what was loaded.
+#ifndef PG_WIN_DIV
+#define PG_WIN_DIV 1
+#endif
+#define PG_WIN_SLACK 16u               // readable bytes behind the window (the dropped tail of a run's last piece)
+#define PG_WIN_REGS (8 / PG_WIN_DIV)   // 16-byte pieces of a window per thread
+static_assert(GCI_PAGE_MAX_BYTES / PG_WIN_DIV <= PG_WIN_REGS * PG_BLOCK * 16, "a thread holds its share of a whole window in registers");
+static inline __host__ __device__ uint32_t pg_win_cap(uint32_t page_bytes) { return (page_bytes / PG_WIN_DIV) & ~15u; }
+
+// the window for records from stream offset off0 on, none of them expected behind span_end (<= n_bytes): empty when that lies below
+// off0.  Whole 16-byte pieces that lie inside the stream only -- no load touches a byte outside [bam, end) -- so what a record has in
+// the stream's first or last, partial, piece is not in the window and is gathered.
+__device__ __forceinline__ PgWin pg_win_of(const uint8_t* lds, const uint8_t* bam, const uint8_t* end, uint64_t off0, uint64_t span_end, uint32_t cap)
 {
-    extern __shared__ __attribute__((aligned(16))) uint8_t page[];
+    PgWin W;
+    W.lds = lds; W.lo = W.hi = bam;
+    if (off0 < span_end) {
+        const uint8_t* p0 = bam + off0;
+        const uint8_t* lo = p0 - ((uintptr_t)p0 & 15u);            // (the ADDRESS rounded down: the stream pointer need not be aligned)
+        if (lo < bam) lo += 16;
+        const uint8_t* last = bam + span_end + 15;
+        const uint8_t* hi = last - ((uintptr_t)last & 15u);
+        if (hi > end) hi = end - ((uintptr_t)end & 15u);
+        if (hi > lo) { W.lo = lo; W.hi = (uint64_t)(hi - lo) < cap ? hi : lo + cap; }
+    }
+    return W;
+}
+// a thread's pieces of the window: all of them requested before any is used ...
+__device__ __forceinline__ void pg_win_load(const PgWin& W, uint32_t t, uint4 v[PG_WIN_REGS])
+{
+    const uint32_t pieces = (uint32_t)(W.hi - W.lo) / 16u;
+#pragma unroll
+    for (int u = 0; u < PG_WIN_REGS; u++) {
+        const uint32_t i = u * PG_BLOCK + t;
+        v[u] = i < pieces ? reinterpret_cast<const uint4*>(W.lo)[i] : make_uint4(0, 0, 0, 0);
+    }
+}
+// ... and put into LDS
+__device__ __forceinline__ void pg_win_store(uint8_t* win, const PgWin& W, uint32_t t, const uint4 v[PG_WIN_REGS])
+{
+    const uint32_t pieces = (uint32_t)(W.hi - W.lo) / 16u;
+#pragma unroll
+    for (int u = 0; u < PG_WIN_REGS; u++) {
+        const uint32_t i = u * PG_BLOCK + t;
+        if (i < pieces) reinterpret_cast<uint4*>(win)[i] = v[u];
+    }
+}
+
+// What a workgroup must know of a page before it can ask for the page's bytes (k_pg_first left it in two tables).
+struct PgPage { uint32_t first, cnt; uint64_t off0, span_end; };
+__device__ __forceinline__ PgPage pg_page_of(const PgArgs& A, uint32_t k)
+{
+    PgPage p;
+    p.first = A.page_first[k]; p.cnt = A.page_first[k + 1] - p.first;
+    p.off0 = A.page_off[k];
+    // the stream offset no record of this page is expected behind: it only bounds the window (the table need not be ascending)
+    p.span_end = A.page_off[k + 1];
+    if (p.span_end > A.n_bytes) p.span_end = A.n_bytes;
+    return p;
+}
+// ... and of its records before it can measure them: offset and cost offset of record t of the page, the cost offsets of its first
+// record and behind its last
+struct PgMine { uint64_t off; unsigned long long S, S0, S_end; };
+__device__ __forceinline__ PgMine pg_mine_of(const PgArgs& A, const PgPage& p, uint32_t t)
+{
+    PgMine m;
+    m.off = 0; m.S = 0;
+    if (t < p.cnt && t < PG_META_MAX) { m.off = A.rec_off[p.first + t]; m.S = pg_S(A.sums, p.first + t); }
+    m.S0 = p.cnt ? pg_S(A.sums, p.first) : 0ull;
+    m.S_end = p.cnt ? pg_S(A.sums, p.first + p.cnt) : 0ull;
+    return m;
+}
+
+// A workgroup writes pages blockIdx.x, + gridDim.x, ... and is one page ahead with its loads: while it composes page k out of LDS, the
+// window of page k + gridDim.x and that page's offsets are on their way into registers, and the two table entries of the page behind
+// it are being fetched -- a page's three dependent trips to memory (page tables -> offsets and window -> bytes) are each one page old
+// when their result is needed.
+//
+// There is no image of the page in LDS: the page is composed 16 bytes at a time, a thread per PIECE, and stored straight to memory.
+// Everything in a record's image from byte 48 on is a 16-byte aligned copy of sixteen bytes of ONE of its runs (the CIGAR and the aux
+// block start at multiples of 16, the name at 36), so a piece is: which record (a byte per piece, left by the thread that measured
+// the record), which run, four dwords out of the window.  A record's first 48 bytes -- the patched core and the first twelve bytes of
+// the name -- are put together by the thread that measures it.  (Composed dword by dword by eight lanes per record into an image in
+// LDS, the kernel was bound by the instructions it issued: ~60 per dword.)
+#ifndef PG_PERSIST
+#define PG_PERSIST 1                   // 0: a workgroup per page, nothing fetched ahead
+#endif
+#ifndef PG_WAVES
+#define PG_WAVES 4                     // waves per SIMD the registers are cut to: 4 workgroups per CU, what the LDS allows too (3 without: 146 VGPRs)
+#endif
+__global__ __launch_bounds__(PG_BLOCK) __attribute__((amdgpu_waves_per_eu(PG_WAVES, PG_WAVES))) void k_pg_write(const PgArgs A)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t win[];              // the window
     // which records of the page leave something in the blob (nearly none of a HiFi file): the pass over the blob below looks
     // at those only -- measuring every record again there, one after the other by the whole workgroup, was 60 dependent trips
     // to memory per page and most of this kernel's time
     __shared__ uint16_t s_blob_rec[GCI_PAGE_MAX_BYTES / 48];
-    __shared__ uint32_t s_n_blob;
+    __shared__ uint32_t s_n_blob, s_take, s_sparse;
     __shared__ PgMeta s_meta[PG_META_MAX];
-    const uint32_t t = threadIdx.x, k = blockIdx.x;
+    __shared__ __attribute__((aligned(16))) uint32_t s_core[PG_META_MAX][12];           // a record's first 48 bytes in the page
+    __shared__ uint8_t s_map[GCI_PAGE_MAX_BYTES / 16];                                  // piece of the page -> record of the fill
+    __shared__ __attribute__((aligned(16))) uint8_t s_head[16 + ((2 * ((GCI_PAGE_MAX_BYTES - 16) / 50) + 15) & ~15)];   // header and directory
+    const uint32_t t = threadIdx.x, G = gridDim.x;
     const uint32_t P = A.page_bytes;
-    for (uint32_t i = t; i < P / 16; i += PG_BLOCK) reinterpret_cast<uint4*>(page)[i] = make_uint4(0, 0, 0, 0);
-    if (t == 0) s_n_blob = 0;
-    const uint32_t first = A.page_first[k], cnt = A.page_first[k + 1] - first;
-    const unsigned long long S0 = cnt ? A.S[first] : 0ull;
-    const uint32_t rec0 = 16u + a16(2u * cnt);
+    const uint32_t win_cap = pg_win_cap(P);
     const uint8_t* end = A.bam + A.n_bytes;
-    __syncthreads();
-    const uint32_t gl = t % PG_LANES, grp = t / PG_LANES;
-    uint32_t used = rec0;
-    for (uint32_t m0 = 0; m0 < cnt; m0 += PG_META_MAX) {
-        const uint32_t mc = cnt - m0 < PG_META_MAX ? cnt - m0 : PG_META_MAX;
-        // ---- phase A: one thread per record measures it (offset -> 10 aligned dwords: the only dependent trips to memory of the
-        // page), leaves what the copy needs in LDS and writes the patched 36-byte core and the directory entry
-        if (t < mc) {
-            const uint32_t j = m0 + t, i = first + j;
-            const uint64_t off = A.rec_off[i];
-            const unsigned long long Si = A.S[i];
-            uint32_t core[9];
-            const PgRec r = pg_measure_fast(A.bam, A.n_bytes, off, A.has_seq != 0, core);
-            const uint32_t at = rec0 + (uint32_t)(Si - S0) - 2u * j;
-            const uint64_t blob_at = r.blob ? A.blob_off + A.B[i] : 0ull;
-            if (r.blob) s_blob_rec[atomicAdd(&s_n_blob, 1u)] = (uint16_t)j;
-            *reinterpret_cast<uint16_t*>(page + 16 + 2 * j) = (uint16_t)(at >> 4);
-            core[0] = r.size;
-            core[3] = (core[3] & 0xFFFFu) | (r.kind << 16);
-            core[6] = r.aux_len; core[7] = (uint32_t)blob_at; core[8] = (uint32_t)(blob_at >> 32);
-            if (r.kind == PG_MALFORMED) core[6] = core[7] = core[8] = 0u;
-            uint32_t* dst = reinterpret_cast<uint32_t*>(page + at);
+    const PgPage none = {0u, 0u, 0ull, 0ull};
+
+    uint32_t k = blockIdx.x;                                       // (< n_pages: the grid is no larger)
+    PgPage p_next = pg_page_of(A, k);
+    PgPage p_after = k + G < A.n_pages ? pg_page_of(A, k + G) : none;
+    PgWin W_next = pg_win_of(win, A.bam, end, p_next.off0, p_next.span_end, win_cap);
+    uint4 v[PG_WIN_REGS];
+    pg_win_load(W_next, t, v);
+    PgMine m_next = pg_mine_of(A, p_next, t);
+
+    for (; k < A.n_pages; k += G) {
+        const PgPage pg = p_next;
+        const PgMine mine = m_next;
+        const PgWin W0 = W_next;
+        const uint32_t first = pg.first, cnt = pg.cnt;
+        const unsigned long long S0 = mine.S0;
+        const uint32_t rec0 = 16u + a16(2u * cnt);
+        const uint32_t used = cnt ? rec0 + (uint32_t)(mine.S_end - S0) - 2u * cnt : 16u;
+        uint4* const g = reinterpret_cast<uint4*>(A.out + (uint64_t)k * P);
+        pg_win_store(win, W0, t, v);
+        if (t < sizeof(s_head) / 16) reinterpret_cast<uint4*>(s_head)[t] = make_uint4(0, 0, 0, 0);
+        if (t == 0) {
+            s_n_blob = 0;
+            uint32_t* h = reinterpret_cast<uint32_t*>(s_head);
+            h[0] = cnt; h[1] = first; h[2] = used; h[3] = PG_MAGIC;
+        }
+        // ---- the loads of the pages behind this one
+        p_next = p_after;
+        if (k + G < A.n_pages) {
+            W_next = pg_win_of(win, A.bam, end, p_next.off0, p_next.span_end, win_cap);
+            pg_win_load(W_next, t, v);
+            m_next = pg_mine_of(A, p_next, t);
+        }
+        p_after = (uint64_t)k + 2ull * G < A.n_pages ? pg_page_of(A, k + 2 * G) : none;
+
+        if (cnt == 0) __syncthreads();
+        for (uint32_t m0 = 0; m0 < cnt;) {
+            const uint32_t mc = cnt - m0 < PG_META_MAX ? cnt - m0 : PG_META_MAX;
+            // ---- the window of this fill: from the address of record m0 rounded down to 16 bytes.  The page's first fill came with
+            // the page; a later one is loaded here and waited for.
+            uint64_t off0 = pg.off0, off = mine.off;
+            unsigned long long Si = mine.S;
+            PgWin W = W0;
+            if (m0) {
+                off0 = A.rec_off[first + m0];
+                W = pg_win_of(win, A.bam, end, off0, pg.span_end, win_cap);
+                uint4 w[PG_WIN_REGS];
+                pg_win_load(W, t, w);
+                if (t < mc) { off = A.rec_off[first + m0 + t]; Si = pg_S(A.sums, first + m0 + t); }
+                pg_win_store(win, W, t, w);
+            }
+            if (t == 0) { s_take = mc; s_sparse = 0u; }
+            __syncthreads();
+            // ---- phase A: one thread per record measures it (its core from the window, or 10 aligned dwords from memory), leaves
+            // what the pieces need in LDS: the record's first 48 bytes, its directory entry, where its runs lie, its pieces in the map
+            uint32_t my_blob = 0;
+            if (t < mc) {
+                const uint32_t j = m0 + t, i = first + j;
+                uint32_t core[12];
+                PgRec r;
+                bool core_in = false;
+                if (off + 36 > A.n_bytes) {
 #pragma unroll
-            for (int d = 0; d < 9; d++) dst[d] = core[d];
-            PgMeta mt;
-            mt.off = off; mt.aux_off = r.aux_off; mt.lrn = (uint8_t)r.lrn; mt.n_cig = (uint16_t)r.n_cig;
-            mt.aux_len = (uint16_t)(r.aux_len <= PG_MAX_REC ? r.aux_len : 0u);
-            mt.at = (uint16_t)at; mt.kind = (uint8_t)r.kind;
-            s_meta[t] = mt;
-        }
-        __syncthreads();
-        // ---- phase B: PG_LANES lanes per record copy its name, CIGAR and aux bytes; nothing here waits for anything but its own loads
-        for (uint32_t j0 = 0; j0 < mc; j0 += PG_BLOCK / PG_LANES) {
-            const uint32_t jj = j0 + grp;
-            if (jj >= mc) continue;
-            const PgMeta mt = s_meta[jj];
-            if (mt.kind == PG_MALFORMED || mt.kind == PG_OVERSIZE) continue;
-            uint8_t* dst = page + mt.at;
-            const uint32_t c = a16(36u + mt.lrn);
-            PgRun r0, r1, r2;
-            r0.src = mt.off + 36; r0.len = mt.lrn; r0.n = (mt.lrn + 3u) >> 2; r0.at = 36;
-            r1.src = mt.off + 36 + mt.lrn; r1.at = c;
-            if (mt.kind == 0) { r1.len = 4u * mt.n_cig; r1.n = mt.n_cig; }
-            else { r1.len = mt.n_cig ? 4u : 0u; r1.n = mt.n_cig ? 1u : 0u; }       // kind 1: the first operation stays visible in the page
-            r2.src = mt.aux_off; r2.len = mt.aux_len; r2.n = (mt.aux_len + 3u) >> 2;
-            r2.at = c + (mt.kind == 0 ? a16(4u * mt.n_cig) : 16u);
-            pg_copy_runs(A.bam, end, r0, r1, r2, dst, gl);
-        }
-        __syncthreads();                                           // (s_meta is reused by the next pass)
-    }
-    if (cnt) used = rec0 + (uint32_t)(A.S[first + cnt] - S0) - 2u * cnt;
-    if (t == 0) {
-        uint32_t* h = reinterpret_cast<uint32_t*>(page);
-        h[0] = cnt; h[1] = first; h[2] = cnt ? used : 16u; h[3] = PG_MAGIC;
-    }
-    __syncthreads();
-    uint4* g = reinterpret_cast<uint4*>(A.out + (uint64_t)k * P);
-    for (uint32_t i = t; i < P / 16; i += PG_BLOCK) g[i] = reinterpret_cast<const uint4*>(page)[i];
-    // what the page leaves in the blob: CIGAR words (kind 1) or heads-form records (kind 2), record after record, all threads
-    const uint32_t n_blob = s_n_blob;                            // (written before the barrier above)
-    for (uint32_t b = 0; b < n_blob; b++) {
-        const uint32_t i = first + s_blob_rec[b];
-        const uint64_t off = A.rec_off[i];
-        const PgRec r = pg_measure(A.bam, A.n_bytes, off, A.has_seq != 0);         // (uniform over the workgroup)
-        if (!r.blob) continue;
-        uint32_t* o = reinterpret_cast<uint32_t*>(A.out + A.blob_off + A.B[i]);
-        if (r.kind == PG_EXT) {
-            for (uint32_t d = t; d < r.blob / 4; d += PG_BLOCK)
-                o[d] = d < r.n_cig ? pg_src_dword(A.bam, A.n_bytes, off + 36 + r.lrn, 4 * r.n_cig, d) : 0u;
-        } else {
-            // heads form: core (block_size shortened), name + CIGAR (contiguous in the stream), aux (behind SEQ / QUAL there)
-            const uint32_t head = 36 + r.lrn + 4 * r.n_cig, total = head + r.aux_len;
-            for (uint32_t d = t; d < r.blob / 4; d += PG_BLOCK) {
-                uint32_t w = 0;
-                const uint32_t b0 = 4 * d;
-                if (b0 + 4 <= head) w = pg_src_dword(A.bam, A.n_bytes, off, head, d);
-                else if (b0 >= head) { if (b0 < total) w = pg_src_dword(A.bam, A.n_bytes, r.aux_off + (b0 - head), total - b0, 0); }
-                else {                                             // the dword that holds the seam
-                    for (uint32_t b = 0; b < 4 && b0 + b < total; b++) {
-                        const uint32_t x = b0 + b;
-                        w |= (uint32_t)(x < head ? A.bam[off + x] : A.bam[r.aux_off + (x - head)]) << (8 * b);
+                    for (int d = 0; d < 9; d++) core[d] = 0u;
+                    r.kind = PG_MALFORMED; r.size = 48; r.blob = 0; r.lrn = r.n_cig = r.aux_len = 0; r.aux_off = 0; r.short_core = true;
+                    core_in = true;
+                } else {
+                    const uint8_t* p = A.bam + off;
+                    core_in = pg_in_win(W, p, 36);
+                    if (core_in) {
+#pragma unroll
+                        for (int d = 0; d < 9; d++) core[d] = pg_lds32(win + (uint32_t)(p - W.lo) + 4 * d);
+                    } else {
+                        pg_core_gather(A.bam, A.n_bytes, off, core);
                     }
+                    r = pg_classify(core, A.n_bytes, off, A.has_seq != 0);
                 }
-                if (d == 0) w = total - 4;
-                o[d] = w;
+                const bool copied = r.kind == 0 || r.kind == PG_EXT;
+                const uint32_t cig_len = r.kind == 0 ? 4u * r.n_cig : r.n_cig ? 4u : 0u;    // kind 1: the first operation stays visible in the page
+                uint32_t in = 0;
+                if (copied) {
+                    if (pg_in_win(W, A.bam + off + 36, r.lrn)) in |= PG_IN_NAME;
+                    if (pg_in_win(W, A.bam + off + 36 + r.lrn, cig_len)) in |= PG_IN_CIGAR;
+                    if (pg_in_win(W, A.bam + r.aux_off, r.aux_len)) in |= PG_IN_AUX;
+                }
+                // where the fill ends: a fill's first record that reaches out of its window says that the stream is not a run of
+                // small records (ONT, SEQ / QUAL in between, a table out of order): the whole batch is then done from this one fill,
+                // by the gather.  Otherwise the fill ends before the first record whose core lies behind the window.
+                if (t == 0) { if (!core_in || (copied && in != (PG_IN_NAME | PG_IN_CIGAR | PG_IN_AUX))) s_sparse = 1u; }
+                else if (off >= off0 && A.bam + off + 36 > W.hi) atomicMin(&s_take, t);
+                const uint32_t at = rec0 + (uint32_t)(Si - S0) - 2u * j;
+                const uint64_t blob_at = r.blob ? A.blob_off + pg_B(A.sums, i) : 0ull;
+                my_blob = r.blob;
+                *reinterpret_cast<uint16_t*>(s_head + 16 + 2 * j) = (uint16_t)(at >> 4);
+                core[0] = r.size;
+                core[3] = (core[3] & 0xFFFFu) | (r.kind << 16);
+                core[6] = r.aux_len; core[7] = (uint32_t)blob_at; core[8] = (uint32_t)(blob_at >> 32);
+                if (r.kind == PG_MALFORMED) core[6] = core[7] = core[8] = 0u;
+                // the first twelve bytes of the name
+                const uint4 nm = copied ? pg_piece(A.bam, A.n_bytes, W, (in & PG_IN_NAME) != 0, off + 36, r.lrn, 0) : make_uint4(0, 0, 0, 0);
+                core[9] = nm.x; core[10] = nm.y; core[11] = nm.z;
+#pragma unroll
+                for (int d = 0; d < 12; d += 4) *reinterpret_cast<uint4*>(&s_core[t][d]) = make_uint4(core[d], core[d + 1], core[d + 2], core[d + 3]);
+                for (uint32_t q = 0; q < r.size / 16u; q++) s_map[(at >> 4) + q] = (uint8_t)t;
+                PgMeta mt;
+                mt.off = off; mt.aux_off = r.aux_off; mt.lrn = (uint8_t)r.lrn; mt.n_cig = (uint16_t)r.n_cig;
+                mt.aux_len = (uint16_t)(r.aux_len <= PG_MAX_REC ? r.aux_len : 0u);
+                mt.at = (uint16_t)at; mt.kind = (uint8_t)(r.kind | in);
+                s_meta[t] = mt;
+            }
+            __syncthreads();
+            // (records from `take` on are measured again by the next fill)
+            const uint32_t take = __builtin_amdgcn_readfirstlane(s_sparse ? mc : s_take);
+            if (t < take && my_blob) s_blob_rec[atomicAdd(&s_n_blob, 1u)] = (uint16_t)(m0 + t);
+            // ---- phase B: the pieces of the records of this fill, a thread per piece, straight to memory
+            const uint32_t piece_lo = s_meta[0].at >> 4;
+            const uint32_t piece_hi = m0 + take == cnt ? used >> 4 : take < mc ? s_meta[take].at >> 4
+                                                                               : (rec0 + (uint32_t)(pg_S(A.sums, first + m0 + take) - S0) - 2u * (m0 + take)) >> 4;
+            for (uint32_t piece = piece_lo + t; piece < piece_hi; piece += PG_BLOCK) {
+                const uint32_t jj = s_map[piece];
+                const PgMeta mt = s_meta[jj];
+                const uint32_t q = 16u * piece - mt.at, kind = mt.kind & 0xFu;
+                uint4 o;
+                if (q < 48u) o = *reinterpret_cast<const uint4*>(&s_core[jj][q / 4u]);
+                else {
+                    const uint32_t c = a16(36u + mt.lrn), c2 = c + (kind == 0 ? a16(4u * mt.n_cig) : 16u);
+                    if (q < c) o = pg_piece(A.bam, A.n_bytes, W, (mt.kind & PG_IN_NAME) != 0, mt.off + 36, mt.lrn, q - 36u);
+                    else if (q < c2) o = pg_piece(A.bam, A.n_bytes, W, (mt.kind & PG_IN_CIGAR) != 0, mt.off + 36 + mt.lrn,
+                                                  kind == 0 ? 4u * mt.n_cig : mt.n_cig ? 4u : 0u, q - c);
+                    else o = pg_piece(A.bam, A.n_bytes, W, (mt.kind & PG_IN_AUX) != 0, mt.aux_off, mt.aux_len, q - c2);
+                }
+                g[piece] = o;
+            }
+            __syncthreads();                                       // (the tables and the window are reused by the next fill)
+            m0 += take;
+        }
+        // ---- header and directory; zeros behind the last record
+        for (uint32_t piece = t; piece < rec0 / 16u; piece += PG_BLOCK) g[piece] = reinterpret_cast<const uint4*>(s_head)[piece];
+        for (uint32_t piece = (used >> 4) + t; piece < P / 16u; piece += PG_BLOCK) g[piece] = make_uint4(0, 0, 0, 0);
+        // what the page leaves in the blob: CIGAR words (kind 1) or heads-form records (kind 2), record after record, all threads
+        const uint32_t n_blob = s_n_blob;                            // (written before the last barrier)
+        for (uint32_t b = 0; b < n_blob; b++) {
+            const uint32_t i = first + s_blob_rec[b];
+            const uint64_t off = A.rec_off[i];
+            const PgRec r = pg_measure(A.bam, A.n_bytes, off, A.has_seq != 0);         // (uniform over the workgroup)
+            if (!r.blob) continue;
+            uint32_t* o = reinterpret_cast<uint32_t*>(A.out + A.blob_off + pg_B(A.sums, i));
+            if (r.kind == PG_EXT) {
+                for (uint32_t d = t; d < r.blob / 4; d += PG_BLOCK)
+                    o[d] = d < r.n_cig ? pg_src_dword(A.bam, A.n_bytes, off + 36 + r.lrn, 4 * r.n_cig, d) : 0u;
+            } else {
+                // heads form: core (block_size shortened), name + CIGAR (contiguous in the stream), aux (behind SEQ / QUAL there)
+                const uint32_t head = 36 + r.lrn + 4 * r.n_cig, total = head + r.aux_len;
+                for (uint32_t d = t; d < r.blob / 4; d += PG_BLOCK) {
+                    uint32_t w = 0;
+                    const uint32_t b0 = 4 * d;
+                    if (b0 + 4 <= head) w = pg_src_dword(A.bam, A.n_bytes, off, head, d);
+                    else if (b0 >= head) { if (b0 < total) w = pg_src_dword(A.bam, A.n_bytes, r.aux_off + (b0 - head), total - b0, 0); }
+                    else {                                             // the dword that holds the seam
+                        for (uint32_t x0 = 0; x0 < 4 && b0 + x0 < total; x0++) {
+                            const uint32_t x = b0 + x0;
+                            w |= (uint32_t)(x < head ? A.bam[off + x] : A.bam[r.aux_off + (x - head)]) << (8 * x0);
+                        }
+                    }
+                    if (d == 0) w = total - 4;
+                    o[d] = w;
+                }
             }
         }
+        __syncthreads();                                           // (the next page's header, directory and list)
     }
+}
+
+// The scratch of the size pass, all of it in pg_scan -- gci_bam_pages_write reads it in a later call, and the context's shared scan
+// scratch does not last that long: three totals (what the host reads back) | B_loc (n_rec + 1, u64) | the two rows of workgroup
+// totals (2 nb, u64) | S_loc (n_rec + 1, u32).
+static inline PgSums pg_sums_of(gci_ctx* ctx, uint32_t n_rec)
+{
+    PgSums s;
+    s.nb = n_rec / TILE + 1;
+    s.B_loc = (const unsigned long long*)ctx->pg_scan.p + 3;
+    s.blk = s.B_loc + (size_t)n_rec + 1;
+    s.S_loc = (const uint32_t*)(s.blk + 2 * (size_t)s.nb);
+    return s;
+}
+static inline int pg_sums_ensure(gci_ctx* ctx, uint32_t n_rec)
+{
+    return gci_ensure(ctx, ctx->pg_scan, (3 + 2 * ((size_t)n_rec / TILE + 1)) * 8 + ((size_t)n_rec + 1) * (8 + 4));
 }
 
 extern "C" int gci_bam_pages_size(gci_ctx* ctx, const uint8_t* d_stream, uint64_t n_bytes, const uint64_t* d_rec_off, uint32_t n_rec,
@@ -345,33 +608,28 @@ extern "C" int gci_bam_pages_size(gci_ctx* ctx, const uint8_t* d_stream, uint64_
     ctx->pg_n_rec = n_rec; ctx->pg_page_bytes = page_bytes; ctx->pg_n_pages = 0; ctx->pg_blob_off = 0; ctx->pg_blob_bytes = 0;
     if (n_rec == 0) { h_out[1] = 16; return GCI_OK; }
     const uint32_t Q = page_bytes - PG_MAX_REC - 48;
-    GCI_TRY(gci_ensure(ctx, ctx->pg_cost, ((size_t)n_rec + 1) * 4 * 2));
-    GCI_TRY(gci_ensure(ctx, ctx->pg_scan, ((size_t)n_rec + 1) * 8 * 2));
-    GCI_TRY(gci_ensure(ctx, ctx->blk_u64, (size_t)(n_rec / TILE + 2) * 8));
-    uint32_t* cost = (uint32_t*)ctx->pg_cost.p;
-    uint32_t* blob = cost + n_rec + 1;
-    unsigned long long* S = (unsigned long long*)ctx->pg_scan.p;
-    unsigned long long* B = S + n_rec + 1;
-    int r;
+    GCI_TRY(pg_sums_ensure(ctx, n_rec));
+    const PgSums sums = pg_sums_of(ctx, n_rec);
+    unsigned long long* tot = (unsigned long long*)ctx->pg_scan.p;
     {
         ProfScope _ps(ctx, GCI_PROF_PAGES_SIZE);
-        hipLaunchKernelGGL(k_pg_measure, dim3((n_rec + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, ctx->stream, d_stream, n_bytes, d_rec_off, n_rec,
-                           has_seq, cost, blob);
+        hipLaunchKernelGGL(k_pg_measure, dim3(sums.nb), dim3(BLOCK), 0, ctx->stream, d_stream, n_bytes, d_rec_off, n_rec, has_seq,
+                           (uint32_t*)sums.S_loc, (unsigned long long*)sums.B_loc, (unsigned long long*)sums.blk, sums.nb);
         LAUNCHCHK("k_pg_measure");
-        r = device_exclusive_scan<uint32_t, unsigned long long>(ctx, cost, S, (unsigned long long*)ctx->blk_u64.p, n_rec, true);
-        if (r) return r;
-        r = device_exclusive_scan<uint32_t, unsigned long long>(ctx, blob, B, (unsigned long long*)ctx->blk_u64.p, n_rec, true);
-        if (r) return r;
+        hipLaunchKernelGGL(k_pg_blk_scan, dim3(1), dim3(BLOCK), 0, ctx->stream, (unsigned long long*)sums.blk, sums.nb, sums.S_loc, sums.B_loc,
+                           n_rec, tot);
+        LAUNCHCHK("k_pg_blk_scan");
     }
-    unsigned long long tail[2], b_total;
-    HIPCHK(hipMemcpyAsync(tail, S + n_rec - 1, 16, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(hipMemcpyAsync(&b_total, B + n_rec, 8, hipMemcpyDeviceToHost, ctx->stream));
+    unsigned long long tail[3];
+    HIPCHK(hipMemcpyAsync(tail, tot, 24, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
+    const unsigned long long b_total = tail[2];
     const uint64_t n_pages = tail[0] / Q + 1;
     if (n_pages > 0xFFFFFFF0ull) return GCI_E_INVALID;
-    GCI_TRY(gci_ensure(ctx, ctx->pg_first, (size_t)(n_pages + 1) * 4));
-    hipLaunchKernelGGL(k_pg_first, dim3((uint32_t)((n_pages + 1 + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, ctx->stream, S, n_rec,
-                       (uint32_t)n_pages, Q, (uint32_t*)ctx->pg_first.p);
+    GCI_TRY(gci_ensure(ctx, ctx->pg_first, (size_t)(n_pages + 1) * (8 + 4)));          // page_off (u64), then page_first (u32)
+    uint64_t* page_off = (uint64_t*)ctx->pg_first.p;
+    hipLaunchKernelGGL(k_pg_first, dim3((uint32_t)((n_pages + 1 + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, ctx->stream, sums, n_rec,
+                       (uint32_t)n_pages, Q, d_rec_off, n_bytes, (uint32_t*)(page_off + n_pages + 1), page_off);
     LAUNCHCHK("k_pg_first");
     ctx->pg_n_pages = (uint32_t)n_pages;
     ctx->pg_blob_off = n_pages * page_bytes;
@@ -388,18 +646,31 @@ extern "C" int gci_bam_pages_write(gci_ctx* ctx, const uint8_t* d_stream, uint64
     if (!ctx || !d_out || (n_rec && (!d_stream || !d_rec_off))) return GCI_E_INVALID;
     if (n_rec != ctx->pg_n_rec) return GCI_E_INVALID;                       // not the input gci_bam_pages_size measured
     if (n_rec == 0) { HIPCHK(hipMemsetAsync(d_out, 0, cap < 16 ? cap : 16, ctx->stream)); return GCI_OK; }
-    unsigned long long* S = (unsigned long long*)ctx->pg_scan.p;
-    unsigned long long* B = S + n_rec + 1;
     // (size of the blob: read back by the size call; the caller allocated what that call said)
     PgArgs A;
     A.bam = d_stream; A.n_bytes = n_bytes; A.rec_off = d_rec_off; A.n_rec = n_rec; A.has_seq = has_seq;
-    A.S = S; A.B = B; A.page_first = (const uint32_t*)ctx->pg_first.p; A.page_bytes = ctx->pg_page_bytes;
+    A.sums = pg_sums_of(ctx, n_rec); A.page_off = (const uint64_t*)ctx->pg_first.p; A.page_first = (const uint32_t*)(A.page_off + ctx->pg_n_pages + 1);
+    A.n_pages = ctx->pg_n_pages; A.page_bytes = ctx->pg_page_bytes;
     A.blob_off = ctx->pg_blob_off; A.out = d_out;
     const uint64_t need = ctx->pg_blob_off + ctx->pg_blob_bytes + 16;        // = h_out[1] of the size call
     if (cap < need) return GCI_E_CAPACITY;
+    // as many workgroups as the device holds at a time: each walks its share of the pages, one page ahead with its loads
+    const uint32_t lds = pg_win_cap(ctx->pg_page_bytes) + PG_WIN_SLACK;
+    if (!ctx->pg_cus) {
+        int cus = 0;
+        HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+        ctx->pg_cus = cus > 0 ? (uint32_t)cus : 256u;
+    }
+    if (ctx->pg_per_cu_page_bytes != ctx->pg_page_bytes) {                  // (the LDS a workgroup takes depends on the page size alone)
+        int per_cu = 0;
+        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_pg_write, PG_BLOCK, lds));
+        ctx->pg_per_cu = per_cu > 0 ? (uint32_t)per_cu : 1u;
+        ctx->pg_per_cu_page_bytes = ctx->pg_page_bytes;
+    }
+    const uint32_t resident = ctx->pg_cus * ctx->pg_per_cu;
     {
         ProfScope _ps(ctx, GCI_PROF_PAGES_WRITE);
-        hipLaunchKernelGGL(k_pg_write, dim3(ctx->pg_n_pages), dim3(PG_BLOCK), ctx->pg_page_bytes, ctx->stream, A);
+        hipLaunchKernelGGL(k_pg_write, dim3(PG_PERSIST && resident < ctx->pg_n_pages ? resident : ctx->pg_n_pages), dim3(PG_BLOCK), lds, ctx->stream, A);
         LAUNCHCHK("k_pg_write");
     }
     // the 16 zero bytes directly behind the blob (k_cigar_chunks fetches whole 16-byte pieces)
