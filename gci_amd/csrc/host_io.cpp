@@ -352,7 +352,8 @@ extern "C" int gci_bgzf_inflate(const uint8_t* h_raw, uint64_t n_raw, uint8_t* h
     std::atomic<int> err{GCI_OK};
     parallel_for(blocks.size(), threads, [&](uint64_t i) {
         const Block& b = blocks[i];
-        if (b.isize == 0) return;
+        uint8_t none = 0;                                        // (a member of no bytes is a stream too, and zlib wants a place to write)
+        uint8_t* const to = b.isize ? h_out + b.out : &none;
         const uint8_t* h = h_raw + b.pos;
         const uint32_t xlen = h[10] | (h[11] << 8);
         z_stream zs;
@@ -360,7 +361,7 @@ extern "C" int gci_bgzf_inflate(const uint8_t* h_raw, uint64_t n_raw, uint8_t* h
         if (inflateInit2(&zs, -15) != Z_OK) { err = GCI_E_NOMEM; return; }
         zs.next_in = const_cast<Bytef*>(h + 12 + xlen);
         zs.avail_in = (uInt)(b.size - 12 - xlen - 8);
-        zs.next_out = h_out + b.out;
+        zs.next_out = to;
         zs.avail_out = (uInt)b.isize;
         const int r = inflate(&zs, Z_FINISH);
         const bool ok = r == Z_STREAM_END && zs.total_out == b.isize;
@@ -369,7 +370,7 @@ extern "C" int gci_bgzf_inflate(const uint8_t* h_raw, uint64_t n_raw, uint8_t* h
         if (check_crc) {
             uint32_t crc;
             memcpy(&crc, h + b.size - 8, 4);
-            if ((uint32_t)crc32(0L, h_out + b.out, (uInt)b.isize) != crc) err = GCI_E_MALFORMED;
+            if ((uint32_t)crc32(0L, to, (uInt)b.isize) != crc) err = GCI_E_MALFORMED;
         }
     });
     return err.load();
@@ -891,7 +892,8 @@ struct Barrier {
 
 bool inflate_member(const uint8_t* raw, const Block& b, uint8_t* out, int check_crc)
 {
-    if (b.isize == 0) return true;
+    uint8_t none = 0;                                            // (a member of no bytes is a stream too, and zlib wants a place to write)
+    if (b.isize == 0) out = &none;
     const uint8_t* h = raw + b.pos;
     const uint32_t xlen = h[10] | (h[11] << 8);
     z_stream zs;

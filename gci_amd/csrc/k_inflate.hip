@@ -96,9 +96,13 @@ static_assert(sizeof(uint16_t) << LIT_BITS >= 352, "the code lengths must fit un
 
 __device__ __forceinline__ uint32_t bit_reverse(uint32_t v, int n) { return __brev(v) >> (32 - n); }
 
-// lens[0 .. n) -> limits, offsets and the symbols sorted by code; false: over-subscribed code
+// lens[0 .. n) -> limits, offsets and the symbols sorted by code; false: a set zlib (and with it htslib) refuses -- an
+// over-subscribed one always; an incomplete one (code space `left` over) unless `incomplete` allows it: CODE_COMPLETE never (the
+// code-length code), CODE_ONE when the set has no code at all or exactly one code of length 1 (the lit/len and distance codes of a
+// dynamic block), CODE_ANY always (the fixed distance code: 30 codes of 5 bits)
+enum { CODE_COMPLETE = 0, CODE_ONE = 1, CODE_ANY = 2 };
 template <typename SortedPtr>
-__device__ bool build_code(const uint8_t* lens, int n, Canon& cn, SortedPtr sorted)
+__device__ bool build_code(const uint8_t* lens, int n, Canon& cn, SortedPtr sorted, int incomplete)
 {
     for (int l = 0; l < 16; l++) cn.next[l] = 0;
     for (int i = 0; i < n; i++) cn.next[lens[i]]++;
@@ -116,6 +120,7 @@ __device__ bool build_code(const uint8_t* lens, int n, Canon& cn, SortedPtr sort
         if (need > left) ok = false; else left -= need;
     }
     if (!ok) return false;
+    if (left && incomplete != CODE_ANY && !(incomplete == CODE_ONE && (idx == 0u || (idx == 1u && left == 1u << 14)))) return false;
     for (int s = 0; s < n; s++) {
         const int l = lens[s];
         if (l) sorted[cn.next[l]++] = (uint16_t)s;
@@ -294,7 +299,7 @@ void k_bgzf_inflate(const uint8_t* __restrict__ raw, const uint64_t* __restrict_
         if (type == 1) {                                                     // fixed code (RFC 1951 3.2.6)
             for (int i = 0; i < 288; i++) ll[i] = i < 144 ? 8 : i < 256 ? 9 : i < 280 ? 7 : 8;
             for (int i = 0; i < 30; i++) ll[288 + i] = 5;
-            if (!build_code(ll, 288, T.lit_cn, lit_sorted) || !build_code(ll + 288, 30, T.dist_cn, T.dist_sorted)) { bad = true; break; }
+            if (!build_code(ll, 288, T.lit_cn, lit_sorted, CODE_ANY) || !build_code(ll + 288, 30, T.dist_cn, T.dist_sorted, CODE_ANY)) { bad = true; break; }
         } else {                                                             // dynamic code (3.2.7)
             need32(B);
             const int hlit = (int)take(B, 5) + 257, hdist = (int)take(B, 5) + 1, hclen = (int)take(B, 4) + 4;
@@ -302,7 +307,7 @@ void k_bgzf_inflate(const uint8_t* __restrict__ raw, const uint64_t* __restrict_
             for (int i = 0; i < 19; i++) T.lens[i] = 0;
             for (int i = 0; i < hclen; i++) { need32(B); T.lens[c_clen_order[i]] = (uint8_t)take(B, 3); }
             // the code-length code: 19 symbols of at most 7 bits, decoded bit by bit (dist_cn / dist_sorted are free until below)
-            if (!build_code(T.lens, 19, T.dist_cn, T.dist_sorted)) { bad = true; break; }
+            if (!build_code(T.lens, 19, T.dist_cn, T.dist_sorted, CODE_COMPLETE)) { bad = true; break; }
             int n = 0, prev = 0;
             while (n < hlit + hdist) {
                 need32(B);
@@ -318,7 +323,7 @@ void k_bgzf_inflate(const uint8_t* __restrict__ raw, const uint64_t* __restrict_
             }
             if (bad) break;
             if (ll[256] == 0) { bad = true; break; }                          // no end-of-block code
-            if (!build_code(ll, hlit, T.lit_cn, lit_sorted) || !build_code(ll + hlit, hdist, T.dist_cn, T.dist_sorted)) { bad = true; break; }
+            if (!build_code(ll, hlit, T.lit_cn, lit_sorted, CODE_ONE) || !build_code(ll + hlit, hdist, T.dist_cn, T.dist_sorted, CODE_ONE)) { bad = true; break; }
         }
         build_table<LIT_BITS>(T.lit_cn, lit_sorted, T.lit_tab);
         build_table<INF_DIST_BITS>(T.dist_cn, T.dist_sorted, T.dist_tab);

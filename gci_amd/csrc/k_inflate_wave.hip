@@ -61,7 +61,7 @@ constexpr int LIT_BITS = IW_LIT_BITS, DIST_BITS = IW_DIST_BITS;
 // limit[BITS] on -- a direct table over that range.  A HiFi BAM's blocks need ~300 / ~130 entries; in a block that needs more
 // than the tables hold (Codes::search_*, uniform) the lanes that stand on such a code search the limits.
 constexpr uint32_t LIT_TAIL = 512, DIST_TAIL = 256;
-constexpr uint32_t HDR_U = CHUNK_U < 128u ? CHUNK_U : 128u;    // units staged for a block's header (8192 bits; the longest header has 4498)
+constexpr uint32_t HDR_U = CHUNK_U < 128u ? CHUNK_U : 128u;    // units staged for a block's header (8192 bits; the longest legal header has 2286)
 constexpr uint32_t MAXS = PIECE < 512u ? 256u : PIECE / 2u;      // symbols a lane may list per chunk (its piece and what it runs on into)
 constexpr uint32_t NONE = 0xFFFFFFFFu;
 constexpr uint32_t SYM_STRIDE = 65536;                          // entries of symbol stream per member (one per output byte at most)
@@ -190,7 +190,8 @@ __device__ __forceinline__ Sym step(const Lds& S, const Codes& C, const Reader& 
     return r;
 }
 
-// lens[0 .. n) -> the canonical code, by one lane (the 19 symbols of the code-length code)
+// lens[0 .. n) -> the canonical code, by one lane (the 19 symbols of the code-length code); false: over-subscribed or incomplete
+// (zlib refuses both: the member goes to the lane decoder, whose verdict is the call's)
 __device__ bool build_code(const uint8_t* lens, int n, Canon& cn, uint16_t* sorted)
 {
     for (int l = 0; l < 16; l++) cn.next[l] = 0;
@@ -208,7 +209,7 @@ __device__ bool build_code(const uint8_t* lens, int n, Canon& cn, uint16_t* sort
         const uint32_t need = cnt << (15 - l);
         if (need > left) ok = false; else left -= need;
     }
-    if (!ok) return false;
+    if (!ok || left) return false;
     for (int s = 0; s < n; s++) {
         const int l = lens[s];
         if (l) sorted[cn.next[l]++] = (uint16_t)s;
@@ -218,7 +219,9 @@ __device__ bool build_code(const uint8_t* lens, int n, Canon& cn, uint16_t* sort
 
 // ... and by the whole wave: the counts per length and every symbol's place among those of its length by ballots (lane s + 64 c
 // holds symbol s of chunk c), the fifteen-step prefix over the lengths by lane 0.  Same Canon, same `sorted`.
-__device__ bool build_code_wave(const uint8_t* lens, int n, Canon& cn, uint16_t* sorted, int lane, uint32_t* s_ok)
+// complete: the set of a dynamic block, which may leave code space over only if it has no code at all or one code of length 1
+// (k_inflate.hip build_code, CODE_ONE); the fixed distance code -- 30 codes of 5 bits -- is not asked.
+__device__ bool build_code_wave(const uint8_t* lens, int n, Canon& cn, uint16_t* sorted, int lane, uint32_t* s_ok, bool complete)
 {
     uint32_t my[5];
 #pragma unroll
@@ -246,6 +249,7 @@ __device__ bool build_code_wave(const uint8_t* lens, int n, Canon& cn, uint16_t*
             const uint32_t need = k << (15 - l);
             if (need > left) ok = false; else left -= need;
         }
+        if (complete && left && !(idx == 0u || (idx == 1u && left == 1u << 14))) ok = false;
         *s_ok = ok ? 1u : 0u;
     }
     __syncthreads();
@@ -452,8 +456,8 @@ __global__ __launch_bounds__(64, 4) void k_inflate_symbols(const uint8_t* __rest
             Codes C;
             {
                 __syncthreads();
-                const bool ok_l = build_code_wave(S.lens + 32, hlit, S.lit_cn, S.lit_sorted, lane, &S.hdr[4]);
-                const bool ok_d = build_code_wave(S.lens + 32 + hlit, hdist, S.dist_cn, S.dist_sorted, lane, &S.hdr[4]);
+                const bool ok_l = build_code_wave(S.lens + 32, hlit, S.lit_cn, S.lit_sorted, lane, &S.hdr[4], type == 2u);
+                const bool ok_d = build_code_wave(S.lens + 32 + hlit, hdist, S.dist_cn, S.dist_sorted, lane, &S.hdr[4], type == 2u);
                 if (!ok_l || !ok_d) { st = 12u; break; }
                 const bool fits_l = fill_tables(S.lit_tab, LIT_BITS, S.lit_tail, LIT_TAIL, S.lit_cn, S.lit_sorted, lane);
                 const bool fits_d = fill_tables(S.dist_tab, DIST_BITS, S.dist_tail, DIST_TAIL, S.dist_cn, S.dist_sorted, lane);

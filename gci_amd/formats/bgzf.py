@@ -106,10 +106,8 @@ def decompress(raw: bytes, threads: int = 1, check_crc: bool = False) -> np.ndar
 
     def work(i: int) -> None:
         pos, size, isize = blocks[i]
-        if isize == 0:
-            return
         xlen = raw[pos + 10] | (raw[pos + 11] << 8)
-        data = zlib.decompress(mv[pos + 12 + xlen: pos + size - 8], -15, isize)
+        data = zlib.decompress(mv[pos + 12 + xlen: pos + size - 8], -15, max(isize, 1))       # (a member of no bytes is a stream too)
         if len(data) != isize:
             raise BGZFError("ISIZE mismatch in member at byte %d" % pos)
         if check_crc:
