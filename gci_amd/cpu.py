@@ -75,6 +75,8 @@ EXPORTS = [
     ("gci_depth_deflate_write", c_int, [c_void_p] * 4 + [c_uint32] + [c_void_p] * 5 + [c_uint64]),
     ("gci_depth_text_index", c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p]),
     ("gci_depth_text_parse", c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_uint32, c_void_p, c_uint64]),
+    ("gci_sdepth_index", c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p]),
+    ("gci_sdepth_parse", c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_void_p, c_uint32, c_void_p, c_uint64]),
 ]
 
 
@@ -315,4 +317,28 @@ class CpuEngine:
         segs = np.ascontiguousarray(segs, dtype=np.int64).reshape(-1, 3)
         self._chk(self.lib.gci_depth_text_parse(self.ctx, _p(text), text.shape[0], _p(line0), _p(segs), segs.shape[0], _p(track),
                                                 track.shape[0]), "gci_depth_text_parse")
+        return track
+
+    # ---- samtools depth text to a track (k_sdepth.hip's twin)
+    def sdepth_index(self, text: np.ndarray, prev_name: bytes = b"", cap: int = 1 << 10) -> Tuple[np.ndarray, np.ndarray, int]:
+        """-> (uint32 line starts per 4096-byte tile, sorted uint64 keys (offset << 12 | rank in tile) of the lines whose name differs
+        from the line in front -- the first line: from prev_name --, smallest offset of a line outside the strict grammar or 2**64 - 1)."""
+        text = np.ascontiguousarray(text, dtype=np.uint8)
+        tiles = np.zeros(max((text.shape[0] + 4095) // 4096, 1), dtype=np.uint32)
+        prev = np.frombuffer(bytes(prev_name) or b"\0", dtype=np.uint8)
+        while True:
+            keys = np.zeros(max(cap, 1), dtype=np.uint64)
+            nk, bad = np.zeros(1, dtype=np.uint32), np.zeros(1, dtype=np.uint64)
+            self._chk(self.lib.gci_sdepth_index(self.ctx, _p(text), text.shape[0], _p(prev), len(prev_name), _p(tiles), _p(keys), cap, _p(nk),
+                                                _p(bad)), "gci_sdepth_index")
+            if int(nk[0]) <= cap:
+                return tiles[:(text.shape[0] + 4095) // 4096], np.sort(keys[:int(nk[0])]), int(bad[0])
+            cap = int(nk[0])
+
+    def sdepth_parse(self, text: np.ndarray, tile_line0: np.ndarray, segs: np.ndarray, track: np.ndarray, line_base: int = 0) -> np.ndarray:
+        text = np.ascontiguousarray(text, dtype=np.uint8)
+        line0 = np.ascontiguousarray(tile_line0, dtype=np.uint64)
+        segs = np.ascontiguousarray(segs, dtype=np.int64).reshape(-1, 3)
+        self._chk(self.lib.gci_sdepth_parse(self.ctx, _p(text), text.shape[0], _p(line0), int(line_base), _p(segs), segs.shape[0], _p(track),
+                                            track.shape[0]), "gci_sdepth_parse")
         return track

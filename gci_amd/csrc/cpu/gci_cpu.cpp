@@ -851,3 +851,112 @@ int gci_depth_text_parse(gci_ctx* ctx, const uint8_t* text, uint64_t n, const ui
 }
 
 }  // extern "C"
+
+/* ---- samtools depth text -> track (k_sdepth.hip): the same tiles, line ownership, grammar, keys and status word ------------------ */
+namespace {
+constexpr uint64_t SD_LINE_MAX = 255;              // bytes of a line with its '\n'
+inline bool name_end(uint8_t c) { return c == '\t' || c == '\n'; }
+bool sd_strict_line(const uint8_t* text, uint64_t i, uint64_t n)
+{
+    const uint64_t lim = std::min(n - i, SD_LINE_MAX);
+    const uint8_t* b = text + i;
+    uint64_t k = 0;
+    while (k < lim && b[k] >= 0x21 && b[k] <= 0x7E) k++;
+    if (k == 0 || k >= lim || b[k] != '\t') return false;
+    k++;
+    uint64_t d = 0;
+    while (k < lim && d < 11 && b[k] >= '0' && b[k] <= '9') { k++; d++; }
+    if (d == 0 || d > 10 || k >= lim || b[k] != '\t') return false;
+    k++;
+    if (k >= lim) return false;
+    const bool zero = b[k] == '0';
+    uint64_t v = 0;
+    d = 0;
+    while (k < lim && d < 11 && b[k] >= '0' && b[k] <= '9') { v = v * 10 + (uint64_t)(b[k] - '0'); k++; d++; }
+    if (d == 0 || d > 10 || (zero && d > 1) || v > 0x7FFFFFFFull) return false;
+    return i + k == n || (k < lim && b[k] == '\n');
+}
+// the name of the line at i equals a[0 .. a_len) cut at its first '\t' / '\n' (a_len: the bytes of a that may be read)
+bool sd_same_name(const uint8_t* a, uint64_t a_len, bool a_is_name, const uint8_t* text, uint64_t i, uint64_t n)
+{
+    const uint64_t lim = std::min(n - i, SD_LINE_MAX);
+    for (uint64_t k = 0; k < lim; k++) {
+        const bool ea = a_is_name ? k >= a_len : name_end(a[k]), ec = name_end(text[i + k]);
+        if (ea || ec) return ea && ec;
+        if (a[k] != text[i + k]) return false;
+    }
+    return false;
+}
+}  // namespace
+
+extern "C" {
+
+int gci_sdepth_index(gci_ctx* ctx, const uint8_t* text, uint64_t n, const uint8_t* prev_name, uint32_t prev_len, uint32_t* tile_lines,
+                     uint64_t* keys, uint32_t cap, uint32_t* n_keys, uint64_t* bad)
+{
+    if (!ctx || !n_keys || !bad || (n && (!text || !tile_lines)) || (cap && !keys) || (prev_len && !prev_name) || prev_len > SD_LINE_MAX)
+        return GCI_E_INVALID;
+    std::atomic<uint32_t> slots{0};
+    std::atomic<uint64_t> first_bad{~0ull};
+    parallel_blocks(ctx->threads, (n + PARSE_TILE - 1) / PARSE_TILE, 64, [&](uint64_t lo, uint64_t hi) {
+        for (uint64_t t = lo; t < hi; t++) {
+            uint32_t rank = 0;
+            for (uint64_t i = t * PARSE_TILE; i < std::min(n, (t + 1) * PARSE_TILE); i++) {
+                if (!line_start(text, i)) continue;
+                if (!sd_strict_line(text, i, n)) {
+                    uint64_t cur = first_bad.load();
+                    while (i < cur && !first_bad.compare_exchange_weak(cur, i)) {}
+                }
+                bool same;
+                if (i == 0) {
+                    same = sd_same_name(prev_name, prev_len, true, text, 0, n);
+                } else {                                    // the line in front begins at most SD_LINE_MAX bytes back, or equals nothing
+                    uint64_t q = i - 1;
+                    while (q > 0 && i - q < SD_LINE_MAX + 1 && text[q - 1] != '\n') q--;
+                    same = i - q <= SD_LINE_MAX && (q == 0 || text[q - 1] == '\n') && sd_same_name(text + q, 0, false, text, i, n);
+                }
+                if (!same) {
+                    const uint32_t s = slots.fetch_add(1);
+                    if (s < cap) keys[s] = (i << 12) | rank;
+                }
+                rank++;
+            }
+            tile_lines[t] = rank;
+        }
+    });
+    *n_keys = slots.load();
+    *bad = first_bad.load();
+    return GCI_OK;
+}
+
+int gci_sdepth_parse(gci_ctx* ctx, const uint8_t* text, uint64_t n, const uint64_t* tile_line0, uint64_t line_base, const int64_t* segs,
+                     uint32_t n_segs, int32_t* track, uint64_t track_n)
+{
+    if (!ctx || (n && (!text || !tile_line0)) || (n_segs && !segs) || (track_n && !track)) return GCI_E_INVALID;
+    if (!n || !n_segs || !track_n) return GCI_OK;
+    parallel_blocks(ctx->threads, (n + PARSE_TILE - 1) / PARSE_TILE, 64, [&](uint64_t lo, uint64_t hi) {
+        for (uint64_t t = lo; t < hi; t++) {
+            uint64_t g = line_base + tile_line0[t];
+            for (uint64_t i = t * PARSE_TILE; i < std::min(n, (t + 1) * PARSE_TILE); i++) {
+                if (!line_start(text, i)) continue;
+                const uint64_t line = g++;
+                uint32_t a = 0, b = n_segs;                 // the last segment whose first line is <= line
+                while (a < b) { const uint32_t m = (a + b) / 2; if ((uint64_t)segs[3 * m] <= line) a = m + 1; else b = m; }
+                if (a == 0) continue;
+                const int64_t* s = segs + 3 * (a - 1);
+                if (s[2] < 0 || (int64_t)line >= s[0] + s[1]) continue;
+                const int64_t e = s[2] + ((int64_t)line - s[0]);
+                if ((uint64_t)e >= track_n) continue;
+                uint64_t end = i;                           // the depth column: the digits in front of the line's end
+                while (end < n && text[end] != '\n') end++;
+                uint32_t v = 0, mul = 1;
+                for (uint64_t d = 1; d <= 10 && d <= end && text[end - d] >= '0' && text[end - d] <= '9'; d++, mul *= 10)
+                    v += (uint32_t)(text[end - d] - '0') * mul;
+                track[e] = (int32_t)v;
+            }
+        }
+    });
+    return GCI_OK;
+}
+
+}  // extern "C"

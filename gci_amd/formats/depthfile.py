@@ -151,3 +151,89 @@ def parse_depth_lines(lines) -> Dict[str, object]:
             depths[target].append(int(item))
     depths[target] = np.array(depths[target])
     return depths
+
+
+# ---- `samtools depth` text -> .depth.gz (utility/convert_samtools_depth.py): host halves of the device path (k_sdepth.hip) -----------
+
+SDEPTH_LINE_MAX = 255                      # bytes of a line with its '\n': the bound of the device's grammar (k_sdepth.hip)
+
+
+def convert_samtools_host(in_path: str, out_path: str) -> None:
+    """utility/convert_samtools_depth.py:11-20 statement for statement: the slow path for text outside the device's strict grammar
+    (CRLF, blank-padded or signed depths, blanks in names, bytes beyond ASCII) and the way a damaged file raises what the
+    reference raises.  The output is opened first, as there."""
+    f_out = gzip.open(out_path, "wb")
+    try:
+        with open(in_path, "r") as f:
+            pre_chr_id = ""
+            for line in f:
+                chr_id, _, depth = line.strip().split("\t")
+                if chr_id != pre_chr_id:
+                    f_out.write((f">{chr_id}\n").encode("utf-8"))
+                    pre_chr_id = chr_id
+                f_out.write((f"{depth}\n").encode("utf-8"))
+    finally:
+        f_out.close()
+
+
+def _last_newline(raw, a: int, b: int) -> int:
+    """Offset of the last '\\n' in raw[a:b], or -1; read from the back in small pieces (raw: the file's mapping)."""
+    hi = b
+    while hi > a:
+        lo = max(a, hi - (1 << 16))
+        idx = np.flatnonzero(np.asarray(raw[lo:hi]) == 10)
+        if idx.size:
+            return lo + int(idx[-1])
+        hi = lo
+    return -1
+
+
+def _next_newline(raw, a: int, b: int) -> int:
+    lo = a
+    while lo < b:
+        hi = min(b, lo + (1 << 16))
+        idx = np.flatnonzero(np.asarray(raw[lo:hi]) == 10)
+        if idx.size:
+            return lo + int(idx[0])
+        lo = hi
+    return -1
+
+
+def sdepth_chunks(raw, chunk_bytes: int):
+    """Cut the text into [a, b) pieces of at most chunk_bytes that end behind a '\\n' (or at the end of the text); a line longer than
+    a piece gets a piece of its own.  -> [(a, b, name of the last line in front of a)]: with that name a piece needs nothing
+    from the piece in front of it (gci_sdepth_index: prev_name)."""
+    n = int(raw.shape[0])
+    out, a, prev = [], 0, b""
+    while a < n:
+        b = min(n, a + max(1, int(chunk_bytes)))
+        if b < n:
+            j = _last_newline(raw, a, b)
+            if j < 0:
+                j = _next_newline(raw, b, n)
+            b = j + 1 if j >= 0 else n
+        out.append((a, b, prev))
+        # the last line of this piece begins behind the last '\n' in front of its closing byte
+        j = _last_newline(raw, a, b - 1)
+        prev = sdepth_name(raw, j + 1 if j >= 0 else a)
+        a = b
+    return out
+
+
+def sdepth_name(raw, at: int) -> bytes:
+    """The name column of the line that begins at `at`, cut at the device's bound (a longer one is outside the grammar anyway)."""
+    piece = np.asarray(raw[at:at + SDEPTH_LINE_MAX]).tobytes()
+    for k, c in enumerate(piece):
+        if c in (9, 10):
+            return piece[:k]
+    return piece
+
+
+def sdepth_segments(raw, keys: np.ndarray, tile_line0: np.ndarray, byte_base: int = 0, line_base: int = 0):
+    """The keys of gci_sdepth_index over raw[byte_base:] -> [(name, first line index in the file)] in file order: one segment per
+    line whose name differs from the line in front, so a name that returns gets a segment of its own (as the reference writes a
+    second header for it -- unlike header_segments, where the last one wins)."""
+    keys = keys.astype(np.uint64)
+    off = (keys >> np.uint64(12)).astype(np.int64)
+    line = tile_line0[off >> 12].astype(np.int64) + (keys & np.uint64(0xFFF)).astype(np.int64) + line_base
+    return [(sdepth_name(raw, byte_base + int(o)), int(g)) for o, g in zip(off.tolist(), line.tolist())]

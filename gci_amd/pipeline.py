@@ -1765,3 +1765,83 @@ def _checked_upload(engine: Engine, depths: Dict[str, np.ndarray], ref_lengths) 
         if arr.size and (int(arr.min()) < depthfile.INT32_MIN or int(arr.max()) > depthfile.INT32_MAX):
             sys.exit(f'ERROR!!! The depth file holds a depth of "{target}" outside the 32-bit range (-2^31 .. 2^31 - 1), which is not supported')
     return _upload_depths(engine, depths)
+
+
+# ==============================================================================================
+# convert_samtools_depth.py: the text of `samtools depth -a` to a .depth.gz (k_sdepth.hip)
+# ==============================================================================================
+
+def convert_samtools_depth(engine: Optional[Engine], path: str, prefix: str) -> str:
+    """utility/convert_samtools_depth.py for `path` -> `{prefix}.depth.gz`, a multi-member gzip whose payload is the reference's.
+    The file is mapped, its text goes to HBM through the staging ring, the device checks the grammar, counts the lines and marks
+    the lines where the name changes (gci_sdepth_index), the host turns those into segments -- one per run of a name, in file
+    order -- and lays out the track, the device writes the depths (gci_sdepth_parse) and deflates them (Engine.depth_deflate).
+    A file larger than GCI_SDEPTH_RESIDENT_MAX bytes (default 64 GiB) goes through in pieces of GCI_SDEPTH_CHUNK_BYTES cut at line
+    ends, twice: once to index, once to parse.  Text outside the strict grammar, and an empty file, take the reference's own
+    statements on the host (formats.depthfile.convert_samtools_host).  -> the path taken: "device", "device-chunked" or "host"."""
+    from . import hostio
+    from .formats import depthfile
+    out = f"{prefix}.depth.gz"
+    open(out, "wb").close()                                    # (the reference opens its output first: it exists when the input does not)
+    n = os.stat(path).st_size if os.path.exists(path) else -1
+    if n < 0:
+        open(path, "r").close()                                # raises the reference's FileNotFoundError
+    taken = "host"
+    segs = None
+    if n > 0:
+        engine = engine if engine is not None else default_engine()
+        raw = np.memmap(path, dtype=np.uint8, mode="r")
+        resident = n <= int(os.environ.get("GCI_SDEPTH_RESIDENT_MAX", str(64 << 30)))
+        pieces = [(0, n, b"")] if resident else depthfile.sdepth_chunks(raw, int(os.environ.get("GCI_SDEPTH_CHUNK_BYTES", str(8 << 30))))
+
+        def upload(a, b):
+            with phases.wall("sdepth_text_upload"):
+                return engine.upload_staged(raw[a:b]) if b - a >= (256 << 20) else engine.to_device(np.asarray(raw[a:b]))
+
+        with phases.wall("sdepth_index"):
+            found, lines_of, keys_of, kept, line_base, valid = [], [], [], None, 0, True
+            for a, b, prev in pieces:
+                d_text = upload(a, b)
+                d_line0, line0, keys, bad = engine.sdepth_index(d_text, prev)
+                if bad != (1 << 64) - 1:
+                    valid = False
+                    break
+                found += depthfile.sdepth_segments(raw, keys, line0, a, line_base)
+                lines_of.append(int(line0[-1]))
+                keys_of.append(int(keys.shape[0]))
+                line_base += int(line0[-1])
+                kept = (d_text, d_line0) if resident else None
+                del d_text, d_line0
+        if valid:
+            first = np.array([g for _, g in found] + [line_base], dtype=np.int64)
+            lengths = np.diff(first)
+            if lengths.size and int(lengths.max()) > depthfile.INT32_MAX:
+                sys.exit("ERROR!!! A contig of the samtools depth file is longer than 2^31 - 1 bases, which is not supported")
+            engine.set_layout(lengths.tolist())
+            segs = np.stack([first[:-1], lengths, np.asarray(engine.offsets, dtype=np.int64)], axis=1) if lengths.size else np.zeros((0, 3), np.int64)
+            with phases.wall("sdepth_parse"):
+                track = engine.T.zeros(max(engine.total, 1), engine.T.int32, engine.device)     # (the padding behind every segment too)
+                line_base = 0
+                for k, (a, b, prev) in enumerate(pieces):
+                    if kept is not None:
+                        d_text, d_line0 = kept
+                    else:
+                        d_text = upload(a, b)
+                        d_line0 = engine.sdepth_index(d_text, prev, cap=max(keys_of[k], 1))[0]
+                    engine.sdepth_parse(d_text, d_line0, segs, track, line_base)
+                    line_base += lines_of[k]
+                    del d_text, d_line0
+                kept = None
+            taken = "device" if resident else "device-chunked"
+            with phases.wall("sdepth_deflate"):
+                blobs = engine.depth_deflate(track)                # views of the engine's pinned staging buffer
+            with phases.wall("depth_gz_write"), open(out, "wb") as f:
+                for (name, _), blob in zip(found, blobs):
+                    f.write(hostio.gzip_members(b">" + name + b"\n", threads=1))
+                    f.write(blob)
+        del raw
+    if taken == "host":
+        with phases.wall("sdepth_host_convert"):
+            depthfile.convert_samtools_host(path, out)
+    phases.note("convert_samtools_depth_path", taken)
+    return taken

@@ -62,7 +62,10 @@ def _spans(tracks: pipeline.DepthTracks, target: str, start: int, end: int, lo: 
 
 def figure_spec(depths_list: Sequence[pipeline.DepthTracks], target: str, averaged_dicts, mean_depths: Sequence[float],
                 y_frac: float, start: int, depth_min: float, dist_percent: float, y_min: float, y_max: float, image_type: str,
-                directory: str, prefix: str, end: int, regions_flag: bool, threshold) -> FigureSpec:
+                directory: str, prefix: str, end: int, regions_flag: bool, threshold, images_dir: Optional[str] = None) -> FigureSpec:
+    """images_dir: where the figure goes; None = `{directory}/images`, GCI.py's place (utility/plot_depth.py writes into the
+    output directory itself)."""
+    images_dir = f"{directory}/images" if images_dir is None else images_dir
     layers = []
     for i, tracks in enumerate(depths_list):
         y_from, y_to = (y_frac, 1) if i == 0 else (0, y_frac)
@@ -71,10 +74,10 @@ def figure_spec(depths_list: Sequence[pipeline.DepthTracks], target: str, averag
                             _spans(tracks, target, start, end, threshold, mean_depths[i] * depth_min, dist_percent),
                             _spans(tracks, target, start, end, -1, threshold, dist_percent), y_from, y_to))
     if not regions_flag:
-        title, path = f"Filtered depth across the whole genome:{target}", f"{directory}/images/{prefix}.{target}.{image_type}"
+        title, path = f"Filtered depth across the whole genome:{target}", f"{images_dir}/{prefix}.{target}.{image_type}"
     else:
         title = f"Filtered depth across the region:{target}:{start}-{end}"
-        path = f"{directory}/images/{prefix}.{target}:{start}-{end}.{image_type}"
+        path = f"{images_dir}/{prefix}.{target}:{start}-{end}.{image_type}"
     return FigureSpec(layers, y_min, y_max, title, path, depth_min)
 
 
@@ -170,4 +173,39 @@ def plot_depth(depths_list: Sequence[pipeline.DepthTracks] = (), depth_min=0.1, 
         if root:
             for spec in specs:
                 render(spec)
+        print("Plotting depth for regions done!!!\n\n")
+
+
+def plot_depth_utility(depths_list: Sequence[pipeline.DepthTracks] = (), depth_min=0.1, depth_max=4.0, window_size=50000,
+                       image_type="png", directory=".", prefix="GCI", force=False, targets_length: Optional[Dict[str, int]] = None,
+                       dist_percent=0.005, regions_bed: Optional[Dict[str, list]] = None, threshold=0, depth_mean=None):
+    """plot_depth of the stand-alone utility (utility/plot_depth.py:345-406), where it differs from GCI.py's: the figures go into
+    `directory` itself, the mean depths are the caller's (depth_mean; None: the tracks' own), and a regions file replaces the
+    whole-genome figures instead of adding to them -- each region checked, computed and drawn before the next one is looked at."""
+    targets_length = targets_length or {}
+    regions_bed = regions_bed or {}
+    if image_type not in ("pdf", "png"):
+        sys.exit("ERROR!!! The format of output images only supports pdf and png")
+    mean_depths = depth_mean if depth_mean is not None else [tracks.mean() for tracks in depths_list]
+    max_depths = [m * depth_max for m in mean_depths]
+    if len(regions_bed) == 0:
+        for target in depths_list[0].targets:
+            pipeline.refuse_overwrite(f"{directory}/{prefix}.{target}.{image_type}", force)
+        print("Plotting whole genome depth ...")
+        averaged, y_frac, y_min, y_max = pipeline.pre_plot_base(depths_list, max_depths, window_size, 0)
+        for target in depths_list[0].targets:
+            render(figure_spec(depths_list, target, averaged, mean_depths, y_frac, 0, depth_min, dist_percent, y_min, y_max, image_type,
+                               directory, prefix, targets_length[target], False, threshold, images_dir=directory))
+        print("Plotting whole genome depth done!!!\n\n")
+    else:
+        print("Plotting depth for regions ...")
+        for target, segments in regions_bed.items():
+            for start, end in segments:
+                pipeline.refuse_overwrite(f"{directory}/{prefix}.{target}:{start}-{end}.{image_type}", force)
+                if target not in depths_list[0]:
+                    raise KeyError(target)                                   # (the utility's `depthss[target]`)
+                averaged, y_frac, y_min, y_max = pipeline.pre_plot_base(depths_list, max_depths, window_size, start,
+                                                                        region=(target, start, end))
+                render(figure_spec(depths_list, target, averaged, mean_depths, y_frac, start, depth_min, dist_percent, y_min, y_max,
+                                   image_type, directory, prefix, end, True, threshold, images_dir=directory))
         print("Plotting depth for regions done!!!\n\n")

@@ -621,3 +621,34 @@ def write_reference_fasta(path: str, contigs: Sequence[Tuple[str, int]], gaps: O
                 f.write(body.tobytes())
             if L % width:
                 f.write(seq[nfull * width:].tobytes() + b"\n")
+
+
+def samtools_depth_text(items: Sequence[Tuple[str, np.ndarray]], block: int = 1 << 22) -> np.ndarray:
+    """The text `samtools depth -a` writes for per-contig depth arrays -- name, 1-based position, depth, tab-separated, one line per
+    base -- as a uint8 array.  Vectorised: lines of one contig with the same number of position and depth digits have one length,
+    so a run of them is a 2-D array filled one byte position at a time (fast when the depths are piecewise constant)."""
+    p10 = 10 ** np.arange(11, dtype=np.int64)
+    parts: List[np.ndarray] = []
+    for name, depth in items:
+        nm = np.frombuffer(name.encode(), dtype=np.uint8)
+        for a0 in range(0, int(depth.shape[0]), block):
+            d = np.asarray(depth[a0:a0 + block], dtype=np.uint32)               # (depths and positions below 2^32)
+            pos = np.arange(a0 + 1, a0 + 1 + d.shape[0], dtype=np.uint32)
+            nd_pos = np.searchsorted(p10, pos, side="right").astype(np.int64)
+            nd_dep = np.maximum(np.searchsorted(p10, d, side="right"), 1).astype(np.int64)
+            cuts = np.concatenate([[0], np.flatnonzero(np.diff(nd_pos * 16 + nd_dep)) + 1, [d.shape[0]]])
+            for a, b in zip(cuts[:-1].tolist(), cuts[1:].tolist()):
+                np_, ndd = int(nd_pos[a]), int(nd_dep[a])
+                cols = np.empty((nm.shape[0] + np_ + ndd + 3, b - a), dtype=np.uint8)      # (one row per byte of the line: contiguous fills)
+                cols[:nm.shape[0]] = nm[:, None]
+                c = nm.shape[0]
+                cols[c] = 9
+                for k in range(np_):
+                    cols[c + np_ - k] = (pos[a:b] // np.uint32(p10[k])) % np.uint32(10) + np.uint32(48)
+                c += np_ + 1
+                cols[c] = 9
+                for k in range(ndd):
+                    cols[c + ndd - k] = (d[a:b] // np.uint32(p10[k])) % np.uint32(10) + np.uint32(48)
+                cols[c + ndd + 1] = 10
+                parts.append(np.ascontiguousarray(cols.T).reshape(-1))
+    return np.concatenate(parts) if parts else np.zeros(0, dtype=np.uint8)

@@ -436,6 +436,26 @@ int gci_depth_text_index(gci_ctx* ctx, const uint8_t* d_text, uint64_t n_bytes, 
 int gci_depth_text_parse(gci_ctx* ctx, const uint8_t* d_text, uint64_t n_bytes, const uint64_t* d_tile_line0, const int64_t* d_segs,
                          uint32_t n_segs, int32_t* d_track, uint64_t track_n);
 
+/* ---- samtools depth text -> track: the line loop of utility/convert_samtools_depth.py:12-19 (k_sdepth.hip) ----------------------
+ * d_text: the text of `samtools depth -a`, (name '\t' position '\t' depth '\n')*, 16-byte aligned.  Tiles and line ownership as
+ * above.  The strict grammar: name = 1 or more bytes 0x21 .. 0x7E; position = [0-9]{1,10}; depth = 0 or [1-9][0-9]{0,9} with a
+ * value <= INT32_MAX; the line closed by '\n' or the end of the text and, its '\n' included, at most 255 bytes long.
+ *   gci_sdepth_index  d_tile_lines[k] = line starts in tile k; keys = (byte offset << 12) | rank of the line within its tile for
+ *                     every line whose name (the bytes in front of its first '\t' or '\n') differs from the name of the line in
+ *                     front of it, or whose line in front is longer than the bound; the first line of the text is compared with
+ *                     d_prev_name[0 .. prev_len) (prev_len = 0 at the start of a file, <= 255; a later chunk of a file gives
+ *                     the name of the last line of the chunk in front).  *d_n_keys may exceed cap (nothing is written beyond
+ *                     it: call again with more room); *d_bad = smallest byte offset of a line outside the grammar, UINT64_MAX
+ *                     if none.
+ *   gci_sdepth_parse  d_tile_line0 = exclusive scan of d_tile_lines (gci_dev_u32_scan_u64); line_base = lines of the file in front
+ *                     of this text; d_segs = n_segs triples of int64 (first line index in the file, lines, track element of the
+ *                     first or -1 = skip), sorted by first line; line g of segment s goes to d_track[base + g - first] (element
+ *                     indices >= track_n are not written).  Only for text that gci_sdepth_index found valid. */
+int gci_sdepth_index(gci_ctx* ctx, const uint8_t* d_text, uint64_t n_bytes, const uint8_t* d_prev_name, uint32_t prev_len,
+                     uint32_t* d_tile_lines, uint64_t* d_keys, uint32_t cap, uint32_t* d_n_keys, uint64_t* d_bad);
+int gci_sdepth_parse(gci_ctx* ctx, const uint8_t* d_text, uint64_t n_bytes, const uint64_t* d_tile_line0, uint64_t line_base,
+                     const int64_t* d_segs, uint32_t n_segs, int32_t* d_track, uint64_t track_n);
+
 /* ---- host-side container helpers (no GPU work) ---------------------------------
  * The reference reaches BGZF / BAM through pysam/htslib (GCI.py:150-151) and writes gzip through Python's gzip
  * module (GCI.py:111).  All pointers are HOST pointers.
