@@ -135,6 +135,22 @@ class Pages:
     n_rec: int
 
 
+class _Upload:
+    """A file on its way to the device in pieces (Engine.start_upload): the device buffer, where the pieces end, per piece the copy
+    stream's event and whether it has been recorded yet, and the helper thread that enqueues the copies (`future`: its outcome)."""
+
+    def __init__(self, d_raw: Buffer, cuts: List[int], events: list, queued: list, stream, run):
+        self.d_raw, self.cuts, self.events, self.queued, self.stream = d_raw, cuts, events, queued, stream
+        self.pool = ThreadPoolExecutor(1)
+        self.future = self.pool.submit(run)
+
+    def close(self) -> None:
+        """The helper thread is through and gone.  Idempotent; raises nothing (what the upload raised is future.result()'s to tell)."""
+        pool, self.pool = self.pool, None
+        if pool is not None:
+            pool.shutdown(wait=True)
+
+
 class Engine:
     """A gci_ctx bound to a stream of its provider (hbm.py) on `device`."""
 
@@ -321,13 +337,15 @@ class Engine:
             self.check_status("gci_bam_filter_pages")
         return out[:n], name_off[:n]
 
-    def check_status(self, what: str) -> None:
-        w = int(self._status.item()) & _M64
+    def _raise_status(self, w: int, what: str, base: int = 0) -> None:
+        """A status word of the library as a GciError (none for a clean one); `base`: what the word's record index counts from."""
         rec = ctypes.c_uint32(0)
-        st = self.lib.gci_decode_status(w, ctypes.byref(rec))
+        st = self.lib.gci_decode_status(int(w) & _M64, ctypes.byref(rec))
         if st != 0:
-            raise GciError(st, "%s: %s (record %d)" % (what, self.lib.gci_strerror(st).decode(), rec.value),
-                           rec=int(rec.value))
+            raise GciError(st, "%s: %s (record %d)" % (what, self.lib.gci_strerror(st).decode(), rec.value + base), rec=int(rec.value) + base)
+
+    def check_status(self, what: str) -> None:
+        self._raise_status(self._status.item(), what)
 
     # ---- R5 ----------------------------------------------------------------------------------
     def set_join_mode(self, mode: str = "auto") -> None:
@@ -491,20 +509,23 @@ class Engine:
             d_raw[:n_raw].copy_(self._host_src(raw))
         return d_raw
 
+    def _member_table(self, pos: np.ndarray, isize: np.ndarray) -> Tuple[int, int, Buffer, Buffer]:
+        """-> (members, inflated bytes, on the device: where every member begins in the file and in the inflated stream)."""
+        n = int(isize.shape[0])
+        off = np.zeros(n + 1, dtype=np.uint64)
+        np.cumsum(isize, out=off[1:])
+        return n, int(off[n]), self.to_device(np.ascontiguousarray(pos[:n + 1], dtype=np.uint64)), self.to_device(off)
+
     def bgzf_inflate(self, raw: Optional[np.ndarray], pos: np.ndarray, isize: np.ndarray, check_crc: bool = True,
                      prefix: Optional[Buffer] = None, d_raw: Optional[Buffer] = None) -> Buffer:
         """raw: the bytes of a BGZF file (or of a run of its members) -- or d_raw, the same already on the device
         (upload_padded); pos (uint64, n + 1) / isize (uint64, n): its member table (hostio.bgzf_blocks), pos relative to
         raw.  -> the inflated bytes on the device, behind the bytes of `prefix` (the partial record a previous run of
         members ended in).  Raises GciError(GCI_E_MALFORMED, rec = member) on a bad member / CRC."""
-        n = int(isize.shape[0])
-        off = np.zeros(n + 1, dtype=np.uint64)
-        np.cumsum(isize, out=off[1:])
-        total = int(off[n])
         n_pre = int(prefix.shape[0]) if prefix is not None else 0
         if d_raw is None:
             d_raw = self.upload_padded(raw)
-        d_pos, d_off = self.to_device(np.ascontiguousarray(pos[:n + 1], dtype=np.uint64)), self.to_device(off)
+        n, total, d_pos, d_off = self._member_table(pos, isize)
         # (sizes in steps of 256 MiB: the runs of a file differ by a few MB, and a request a little larger than the block the run before
         #  gave back is a new device allocation -- 44 ms beside a copy in flight -- where the same step finds that block again)
         want = max(n_pre + total, 1)
@@ -523,11 +544,7 @@ class Engine:
         before ended in -- which it knows only when that run has been walked, while this run is already being inflated) and the
         status word into a buffer of its own, which the caller checks (check_status_word) once it has made its stream wait for this
         one.  -> (buffer of headroom + total bytes, status word, total)."""
-        n = int(isize.shape[0])
-        off = np.zeros(n + 1, dtype=np.uint64)
-        np.cumsum(isize, out=off[1:])
-        total = int(off[n])
-        d_pos, d_off = self.to_device(np.ascontiguousarray(pos[:n + 1], dtype=np.uint64)), self.to_device(off)
+        n, total, d_pos, d_off = self._member_table(pos, isize)
         want = max(int(headroom) + total, 1)
         out = self.T.empty(((want + (1 << 28) - 1) >> 28) << 28 if want > (1 << 28) else want, self.T.uint8, self.device)
         status = self.T.empty(1, self.T.int64, self.device)
@@ -537,11 +554,7 @@ class Engine:
 
     def check_status_word(self, status: Buffer, what: str) -> None:
         """check_status() over a status word of the caller's (read on the calling thread's current stream)."""
-        w = int(status.item()) & _M64
-        rec = ctypes.c_uint32(0)
-        st = self.lib.gci_decode_status(w, ctypes.byref(rec))
-        if st != 0:
-            raise GciError(st, "%s: %s (record %d)" % (what, self.lib.gci_strerror(st).decode(), rec.value), rec=int(rec.value))
+        self._raise_status(status.item(), what)
 
     def inflate_stats(self) -> dict:
         """How the members of the last bgzf_inflate fared with the wave decoder (gci_bgzf_inflate_last_stats; synchronises)."""
@@ -558,7 +571,6 @@ class Engine:
         """Begin uploading the bytes of a BGZF file in `parts` pieces on a copy stream of its own (a helper thread: the
         copies come from pageable memory and block their caller) -> a handle for bgzf_inflate_uploaded, which starts
         inflating the members of a piece as soon as that piece has arrived."""
-        from concurrent.futures import ThreadPoolExecutor
         n_raw = int(raw.shape[0])
         cuts = sorted({min(n_raw, (n_raw * (k + 1) // parts + 15) & ~15) for k in range(parts)} | {n_raw})
         d_raw = self.T.empty(n_raw + 16, self.T.uint8, self.device)
@@ -580,49 +592,40 @@ class Engine:
                     lo = hi
             return True
 
-        pool = ThreadPoolExecutor(1)
-        return dict(d_raw=d_raw, cuts=cuts, events=events, queued=queued, future=pool.submit(run), pool=pool, stream=copy_stream)
+        return _Upload(d_raw, cuts, events, queued, copy_stream, run)
 
     def bgzf_inflate_uploaded(self, up, pos: np.ndarray, isize: np.ndarray, check_crc: bool = True) -> Buffer:
         """bgzf_inflate over a file whose upload start_upload began: one launch per uploaded piece, over the members that lie
         wholly inside what has arrived (and the 16 bytes the decoder may read behind a member)."""
-        n = int(isize.shape[0])
-        off = np.zeros(n + 1, dtype=np.uint64)
-        np.cumsum(isize, out=off[1:])
-        total = int(off[n])
-        d_pos, d_off = self.to_device(np.ascontiguousarray(pos[:n + 1], dtype=np.uint64)), self.to_device(off)
+        n, total, d_pos, d_off = self._member_table(pos, isize)
         out = self.T.empty(max(total, 1), self.T.uint8, self.device)
         ends = np.asarray(pos[1:n + 1], dtype=np.uint64)
-        n_raw = int(up["d_raw"].shape[0]) - 16
-        status = self.T.zeros(len(up["cuts"]), self.T.int64, self.device)
+        n_raw = int(up.d_raw.shape[0]) - 16
+        status = self.T.zeros(len(up.cuts), self.T.int64, self.device)
         m_lo, bases = 0, []
         try:
-            for k, (cut, ev) in enumerate(zip(up["cuts"], up["events"])):
+            for k, (cut, ev) in enumerate(zip(up.cuts, up.events)):
                 m_hi = n if cut >= n_raw else int(np.searchsorted(ends, np.uint64(max(0, cut - 16)), side="right"))
                 m_hi = max(m_hi, m_lo)
-                while not up["queued"][k].wait(0.05):
-                    if up["future"].done():
-                        up["future"].result()                    # the upload failed: its exception, not a hang
+                while not up.queued[k].wait(0.05):
+                    if up.future.done():
+                        up.future.result()                    # the upload failed: its exception, not a hang
                         break
                 self.stream.wait_event(ev)
                 bases.append(m_lo)
                 if m_hi > m_lo:
-                    self._chk(self.lib.gci_bgzf_inflate_device(self.ctx, self._p(up["d_raw"]), ctypes.c_void_p(d_pos.data_ptr() + 8 * m_lo),
+                    self._chk(self.lib.gci_bgzf_inflate_device(self.ctx, self._p(up.d_raw), ctypes.c_void_p(d_pos.data_ptr() + 8 * m_lo),
                                                                ctypes.c_void_p(d_off.data_ptr() + 8 * m_lo), m_hi - m_lo, self._p(out), total,
                                                                int(check_crc), ctypes.c_void_p(status.data_ptr() + 8 * k)), "gci_bgzf_inflate_device")
                 else:
                     status[k] = -1
                 m_lo = m_hi
-            up["future"].result()
+            up.future.result()
         finally:
-            up["pool"].shutdown()
+            up.close()
         for k, w in enumerate(status.cpu().numpy().view(np.uint64).tolist()):
-            rec = ctypes.c_uint32(0)
-            st = self.lib.gci_decode_status(int(w) & _M64, ctypes.byref(rec))
-            if st != 0:
-                raise GciError(st, "gci_bgzf_inflate_device: %s (record %d)" % (self.lib.gci_strerror(st).decode(), rec.value + bases[k]),
-                               rec=int(rec.value) + bases[k])
-        self.stream.wait_stream(up["stream"])
+            self._raise_status(w, "gci_bgzf_inflate_device", bases[k])
+        self.stream.wait_stream(up.stream)
         return out[:total]
 
     def bam_record_offsets(self, d_stream: Buffer, first_record: int, n_ref: int) -> Tuple[Buffer, int, bool]:

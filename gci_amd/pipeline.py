@@ -16,17 +16,19 @@ interval algebra (gci_amd/score.py) and writes files.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import os
+import queue
 import threading
 import warnings
 import sys
-from concurrent.futures import ThreadPoolExecutor
+from concurrent.futures import Future, ThreadPoolExecutor
 from typing import Dict, List, Optional, Sequence, Set, Tuple
 
 import numpy as np
 
-from . import hbm, phases, score
+from . import hbm, hostio, phases, score
 from .device import Buffer, Engine, JoinInput, REC_DTYPE, name_hash_np
 from . import _lib
 from ._lib import GciError, REC_HQ, REC_PASS
@@ -229,7 +231,6 @@ def paf_filter(paf_files: Sequence[str], targets: Sequence[str], map_qual: int, 
                ) -> Tuple[List[Dict[str, Tuple[str, int, int, int]]], Set[str]]:
     """GCI.py:211-254 as dicts, from the native filter (hostio.paf_filter / gci_paf_filter): what the reference's
     paf_lines and high_qual hold.  The product path (filter()) uploads the native records directly."""
-    from . import hostio
     per_file, high_qual = [], set()
     for recs, names, off in hostio.paf_filter(paf_files, targets, map_qual, mq_cutoff, iden_percent):
         r = recs.reshape(-1).view(REC_DTYPE)
@@ -338,15 +339,51 @@ def _concat_parts(engine: Engine, parts: List[JoinInput]) -> JoinInput:
     return JoinInput(T.cat([p.recs for p in parts]), names, T.cat(offs), 0)
 
 
-def _runs_of_members(engine: Engine, isz: np.ndarray, chunk_bytes: int) -> List[Tuple[int, int]]:
+@contextlib.contextmanager
+def _rebased(base: int):
+    """A GciError raised inside counts its record (or member) from the beginning of a piece of the file: outside, from `base`."""
+    try:
+        yield
+    except GciError as e:
+        if e.rec >= 0:
+            e.rec += base
+        raise
+
+
+class _Parts:
+    """A file that goes through the device piece by piece (runs of members, chunks of the host's stream, a rank's contigs): K1 over
+    every piece on `engine`, records counted from the beginning of the file, and what is kept of each (_keep_part) for the join --
+    which reads it on the stream of `join`, where that is another engine."""
+
+    def __init__(self, engine: Engine, ref_sel: Buffer, filt, join: Optional[Engine] = None):
+        self.engine, self.ref_sel, self.filt, self.join = engine, ref_sel, filt, join
+        self.parts: List[JoinInput] = []
+        self.n_done = 0
+
+    def add(self, d_buf: Buffer, d_off: Buffer) -> None:
+        with _rebased(self.n_done):
+            ji = _filter_stream(self.engine, d_buf, d_off, True, self.ref_sel, self.filt, rec_idx_base=self.n_done)
+        kept = _keep_part(self.engine, ji)
+        if self.join is not None:
+            for t in (kept.recs, kept.name_base, kept.name_off):    # (made in this engine's stream order, joined in the other's)
+                t.record_stream(self.join.stream)
+        self.parts.append(kept)
+        self.n_done += int(d_off.shape[0])
+
+    def result(self) -> JoinInput:
+        return _concat_parts(self.join or self.engine, self.parts)
+
+
+def _runs_of_members(engine: Engine, isz: np.ndarray, chunk_bytes: int, whole_rounds: bool = True) -> List[Tuple[int, int]]:
     """Runs of members of at most chunk_bytes inflated -- and a whole number of the device's decode rounds each: every member takes
     about as long as every other, so 65 536 members (4 GiB) on a device that decodes 28 672 at a time cost three rounds for the
     work of 2.3 (bench.py's ingest of 64.5 GB: 4.1 s; with whole rounds per run: see DESIGN.md section 5).  Greedy, cut by cut
-    on the running sum (a loop over the 3.4 M members of a whole-genome file is a quarter of a second of interpreter)."""
+    on the running sum (a loop over the 3.4 M members of a whole-genome file is a quarter of a second of interpreter).
+    whole_rounds=False: by the bytes alone, the device not asked (the groups the host threads inflate: _ingest_full)."""
     n = int(isz.shape[0])
     cs = np.concatenate([np.zeros(1, dtype=np.int64), np.cumsum(isz.astype(np.int64))])
     total = int(cs[-1])
-    rnd = engine.inflate_round()
+    rnd = engine.inflate_round() if whole_rounds else 0
     per_run = 0
     if rnd > 0:
         per_run = max(1, int(chunk_bytes // max(1, total // max(1, n))) // rnd) * rnd
@@ -420,7 +457,6 @@ class _RunUploads:
     that run k + 1 crosses PCIe while the device inflates, walks and filters run k."""
 
     def __init__(self, engine: Engine, raw, members: _Members):
-        from concurrent.futures import ThreadPoolExecutor
         self.engine, self.raw, self.m = engine, raw, members
         self.bufs = [None, None]
         self.copy = engine.copy_stream()
@@ -514,43 +550,62 @@ def _bam_join_input_gpu(engine: Engine, path: str, raw, members: _Members, ref_s
     the names inside it); a larger one goes through run by run of members (at most chunk_bytes inflated each): inflate,
     record walk, K1, and only the 32-byte records and the packed names are kept -- the partial record a run ends in is
     put in front of the next one.  None: the parallel record walk lost the chain (the caller takes the host path)."""
-    map_qual, mq_cutoff, clip_percent, iden_percent = filt
     hdr = bamfmt.read_header(path)
     ref_sel = ref_sel_for(hdr)
-    n_ref = len(hdr.references)
     if not members.lazy() and int(members.isz.sum()) <= GPU_INFLATE_MAX:
-        pos, isz = members.pos, members.isz
-        total = int(isz.sum())
         if uploads is not None:
             uploads.close()
-            uploads = None
-        with phases.gpu("bgzf_inflate + crc"):
-            if upload is not None:
-                d_bam = engine.bgzf_inflate_uploaded(upload, pos, isz, check_crc=BGZF_CRC)
-                upload = None
-            else:
-                d_bam = engine.bgzf_inflate(raw, pos, isz, check_crc=BGZF_CRC)
-        with phases.gpu("record walk"):
-            d_off, used, ok = engine.bam_record_offsets(d_bam, hdr.first_record, n_ref)
-        if not ok:
-            return None
-        if used != total:
-            raise bamfmt.BAMError("truncated BAM: %d trailing bytes do not form a record" % (total - used))
-        return _filter_stream(engine, d_bam, d_off, True, ref_sel, filt)
+        return _gpu_whole(engine, hdr, raw, members, ref_sel, filt, upload)
     if upload is not None:                                  # larger than it looked: uploaded run by run instead
-        upload["future"].result()
-        upload["pool"].shutdown()
-        upload = None
-    # the bytes of run k + 1 travel while run k is inflated and filtered (the first run may be on its way already:
-    # prefetch_member_tables); and (round 6) run k + 1 is INFLATED while run k is walked, paged and filtered: the inflate stays on this
-    # engine's stream, everything behind it runs on a second context with a stream of its own (Engine.walk_engine), two output buffers in
-    # turns.  The partial record run k ends in is known only when run k has been walked -- by then run k + 1 is being inflated --, so
-    # every run is inflated INGEST_HEADROOM bytes into its buffer and the carried bytes are put in front of it afterwards.
+        upload.future.result()
+    return _gpu_runs(engine, hdr, raw, members, ref_sel, filt, uploads)
+
+
+def _gpu_whole(engine: Engine, hdr, raw, members: _Members, ref_sel: Buffer, filt, upload) -> Optional[JoinInput]:
+    """The file inflated into one buffer (from the upload that is under way, if one is), walked and filtered there."""
+    pos, isz = members.pos, members.isz
+    total = int(isz.sum())
+    with phases.gpu("bgzf_inflate + crc"):
+        if upload is not None:
+            d_bam = engine.bgzf_inflate_uploaded(upload, pos, isz, check_crc=BGZF_CRC)
+        else:
+            d_bam = engine.bgzf_inflate(raw, pos, isz, check_crc=BGZF_CRC)
+    with phases.gpu("record walk"):
+        d_off, used, ok = engine.bam_record_offsets(d_bam, hdr.first_record, len(hdr.references))
+    if not ok:
+        return None
+    if used != total:
+        raise bamfmt.BAMError("truncated BAM: %d trailing bytes do not form a record" % (total - used))
+    return _filter_stream(engine, d_bam, d_off, True, ref_sel, filt)
+
+
+def _with_carry(engine: Engine, buf: Buffer, carry: Optional[Buffer]) -> Buffer:
+    """A run's bytes, inflated INGEST_HEADROOM into `buf`, with the partial record the run before ended in in front of them: in
+    the headroom -- or, a record of more than the headroom, put together in a buffer of its own."""
+    T = engine.T
+    n_carry = int(carry.shape[0]) if carry is not None else 0
+    if n_carry > INGEST_HEADROOM:
+        whole = T.empty(n_carry + int(buf.shape[0]) - INGEST_HEADROOM, T.uint8, engine.device)
+        whole[:n_carry].copy_(carry)
+        whole[n_carry:].copy_(buf[INGEST_HEADROOM:])
+        return whole
+    if n_carry:
+        buf[INGEST_HEADROOM - n_carry:INGEST_HEADROOM].copy_(carry)
+    return buf[INGEST_HEADROOM - n_carry:]
+
+
+def _gpu_runs(engine: Engine, hdr, raw, members: _Members, ref_sel: Buffer, filt, uploads: Optional[_RunUploads]) -> Optional[JoinInput]:
+    """The file run by run.  The bytes of run k + 1 travel while run k is inflated and filtered (the first run may be on its way
+    already: prefetch_member_tables); and (round 6) run k + 1 is INFLATED while run k is walked, paged and filtered: the inflate stays on
+    this engine's stream, everything behind it runs on a second context with a stream of its own (Engine.walk_engine), two output buffers
+    in turns.  The partial record run k ends in is known only when run k has been walked -- by then run k + 1 is being inflated --, so
+    every run is inflated INGEST_HEADROOM bytes into its buffer and the carried bytes are put in front of it afterwards (_with_carry)."""
     ahead = uploads if uploads is not None else _RunUploads(engine, raw, members)
     T = engine.T
     walk = engine.walk_engine()
-    parts: List[JoinInput] = []
-    carry, start, n_done = None, hdr.first_record, 0
+    parts = _Parts(walk, ref_sel, filt, join=engine)
+    n_ref = len(hdr.references)
+    carry, start = None, hdr.first_record
 
     def launch(k: int):
         """Run k's inflate on the engine's stream, as soon as its bytes are on the device; None behind the last run."""
@@ -564,7 +619,7 @@ def _bam_join_input_gpu(engine: Engine, path: str, raw, members: _Members, ref_s
         pos, isz = members.pos, members.isz
         p0 = int(pos[lo])
         with phases.gpu("bgzf_inflate + crc"):
-            buf, status, total = engine.bgzf_inflate_ahead(d_raw, pos[lo:hi + 1] - np.uint64(p0), isz[lo:hi], INGEST_HEADROOM, check_crc=BGZF_CRC)
+            buf, status, _ = engine.bgzf_inflate_ahead(d_raw, pos[lo:hi + 1] - np.uint64(p0), isz[lo:hi], INGEST_HEADROOM, check_crc=BGZF_CRC)
         ahead.release(k)
         ev = T.Event()
         ev.record(engine.stream)
@@ -580,24 +635,9 @@ def _bam_join_input_gpu(engine: Engine, path: str, raw, members: _Members, ref_s
             nxt = launch(k + 1)                              # enqueued BEFORE run k is walked: the two overlap on the device
             with T.stream(walk.stream):
                 walk.stream.wait_event(cur["ev"])
-                try:
+                with _rebased(cur["lo"]):
                     walk.check_status_word(cur["status"], "gci_bgzf_inflate_device")
-                except GciError as e:
-                    if e.rec >= 0:
-                        e.rec += cur["lo"]
-                    raise
-                buf = cur["buf"]
-                n_carry = int(carry.shape[0]) if carry is not None else 0
-                if n_carry > INGEST_HEADROOM:                 # (a record of more than the headroom: put together in a buffer of its own)
-                    whole = T.empty(n_carry + int(buf.shape[0]) - INGEST_HEADROOM, T.uint8, engine.device)
-                    whole[:n_carry].copy_(carry)
-                    whole[n_carry:].copy_(buf[INGEST_HEADROOM:])
-                    d_buf = whole
-                else:
-                    if n_carry:
-                        buf[INGEST_HEADROOM - n_carry:INGEST_HEADROOM].copy_(carry)
-                    d_buf = buf[INGEST_HEADROOM - n_carry:]
-                del buf
+                d_buf = _with_carry(engine, cur["buf"], carry)
                 cur = None
                 if int(d_buf.shape[0]) <= start:              # still inside the header
                     carry, start = None, start - int(d_buf.shape[0])
@@ -608,18 +648,7 @@ def _bam_join_input_gpu(engine: Engine, path: str, raw, members: _Members, ref_s
                         return None
                     carry, start = (d_buf[used:].clone() if used < int(d_buf.shape[0]) else None), 0
                     if int(d_off.shape[0]):
-                        try:
-                            ji = _filter_stream(walk, d_buf, d_off, True, ref_sel, filt, rec_idx_base=n_done)
-                        except GciError as e:
-                            if e.rec >= 0:
-                                e.rec += n_done
-                            raise
-                        kept = _keep_part(walk, ji)
-                        for t in (kept.recs, kept.name_base, kept.name_off):    # (made in the walk stream's order, joined in the engine's)
-                            t.record_stream(engine.stream)
-                        parts.append(kept)
-                        n_done += int(d_off.shape[0])
-                        del ji
+                        parts.add(d_buf, d_off)
                     del d_off
                 del d_buf
             phases.trace("run_done", k, phases.now())
@@ -630,7 +659,7 @@ def _bam_join_input_gpu(engine: Engine, path: str, raw, members: _Members, ref_s
         engine.stream.wait_stream(walk.stream)               # (what the join reads was written over there)
     if carry is not None:
         raise bamfmt.BAMError("truncated BAM: %d trailing bytes do not form a record" % int(carry.shape[0]))
-    return _concat_parts(engine, parts)
+    return parts.result()
 
 
 # A large file's runs: the bytes kept free in front of every run's inflated bytes for the record the run before it ended in (a longer
@@ -647,8 +676,6 @@ def _drop_later(*objs) -> None:
     should be launching kernels."""
     global _DROP_QUEUE
     if _DROP_QUEUE is None:
-        import queue
-        import threading
         _DROP_QUEUE = queue.SimpleQueue()
 
         def run(q):
@@ -672,9 +699,7 @@ def prefetch_member_tables(paths: Sequence[str]) -> None:
     0.7 s of table and a third of a second of upload per file at genome size -- happens beside the assembly's N scan and beside
     the inflate of the file in front.  bam_join_input() picks the results up; an unreadable or damaged file raises there (a
     damaged member behind the table's first piece: where the run that holds it is asked for)."""
-    from concurrent.futures import Future
-    from . import hostio
-    if os.environ.get("GCI_BAM_INGEST", "gpu") != "gpu" or not paths or _sharded():
+    if _ingest_mode() != "gpu" or not paths or _sharded():
         return                                            # (a contig-sharded run reads only its contigs' members, through the index)
     todo = []
     for path in paths:
@@ -692,30 +717,60 @@ def prefetch_member_tables(paths: Sequence[str]) -> None:
     # (the first file's table is wanted as soon as the assembly has been scanned; the later ones have the seconds the file before
     # them takes on the device, and their threads would compete with the ones that stage that file's bytes: a quarter as many)
     many = hostio.default_threads()
-    first_run = os.environ.get("GCI_FIRST_RUN_AHEAD", "1") != "0"
-
-    def table(path, raw, threads, limit=None, known=None):
-        """The member table up to byte `limit` (None: all of the file); known = the table of a beginning of the file: only what lies
-        behind it is walked."""
-        with phases.wall("bgzf_member_table (ahead, on a helper thread)"):
-            begin = int(known[0][-1]) if known is not None else 0
-            if begin >= int(raw.shape[0]):
-                return known
-            pos, isz = hostio.bgzf_blocks(np.asarray(raw[begin:]), threads=threads, limit=None if limit is None else limit - begin)
-            if known is None:
-                return pos, isz
-            return np.concatenate([known[0][:-1], pos + np.uint64(begin)]), np.concatenate([known[1], isz])
-
     # The tables of the files BEHIND the first are walked beside the first one's (a thread each), not one after the other: with the
     # uploads at 40 - 57 GB/s a 77 GB file is through the device in under two seconds, and the table of the file behind it -- 1.2 s of page
     # faults over 3.4 M member headers, started only when the first file's own 1.2 s were over -- was not there yet (round 6, one run
     # of the command line at genome size: 1.3 s of waiting for it, 5.7 s instead of 4.4).
     later_pool = ThreadPoolExecutor(max(1, min(4, len(todo) - 1))) if len(todo) > 1 else None
-    later = {k: later_pool.submit(table, path, raw, max(2, many // 4)) for k, (path, raw, _) in enumerate(todo) if k > 0} if later_pool else {}
+    later = {k: later_pool.submit(_table_ahead, path, raw, max(2, many // 4)) for k, (path, raw, _) in enumerate(todo) if k > 0} if later_pool else {}
+    first_run = os.environ.get("GCI_FIRST_RUN_AHEAD", "1") != "0"
+    th = threading.Thread(target=_chain_ahead, args=(todo, later, later_pool, many, first_run), daemon=True)
+    _CHAINS.append(th)
+    th.start()
 
-    def chain():
-        from concurrent.futures import Future
-        before = None                                     # the uploader of the file in front
+
+def _table_ahead(path, raw, threads, limit=None, known=None):
+    """The member table up to byte `limit` (None: all of the file); known = the table of a beginning of the file: only what lies
+    behind it is walked."""
+    with phases.wall("bgzf_member_table (ahead, on a helper thread)"):
+        begin = int(known[0][-1]) if known is not None else 0
+        if begin >= int(raw.shape[0]):
+            return known
+        pos, isz = hostio.bgzf_blocks(np.asarray(raw[begin:]), threads=threads, limit=None if limit is None else limit - begin)
+        if known is None:
+            return pos, isz
+        return np.concatenate([known[0][:-1], pos + np.uint64(begin)]), np.concatenate([known[1], isz])
+
+
+def _first_file_in_pieces(path, raw, fut, threads) -> _RunUploads:
+    """A first file with more bytes than a whole-file ingestion may inflate to -- run by run for certain: the table of its beginning,
+    the first run on its way (`fut` is told), only then the rest of the table, piece by piece (a failure: raised by the run that needs it)."""
+    engine = default_engine()
+    n_raw = int(raw.shape[0])
+    # (5/8 of a run's inflated size in file bytes holds a whole first run at the usual 2.4 - 4 : 1; four times a
+    # run's size holds eight more: a second of inflate, which covers the walk through the rest)
+    limits = [x for x in (BAM_CHUNK_BYTES * 5 // 8, BAM_CHUNK_BYTES * 4) if x < n_raw]
+    rests = [Future() for _ in limits]
+    first = _table_ahead(path, raw, threads, limit=limits[0]) if limits else _table_ahead(path, raw, threads)
+    members = _Members(engine, BAM_CHUNK_BYTES, first[0], first[1], rests[0] if rests else None)
+    uploads = _RunUploads(engine, raw, members)
+    fut.set_result((members, uploads))
+    nxt = first
+    for j, rest in enumerate(rests):
+        try:
+            nxt = _table_ahead(path, raw, threads, limit=limits[j + 1] if j + 1 < len(limits) else None, known=nxt)
+            rest.set_result((nxt[0], nxt[1], rests[j + 1] if j + 1 < len(rests) else None))
+        except BaseException as e:        # noqa: BLE001
+            for r in rests[j:]:
+                r.set_exception(e)
+            break
+    return uploads
+
+
+def _chain_ahead(todo, later, later_pool, many, first_run) -> None:
+    """The helper thread of prefetch_member_tables: file after file, every outcome handed to the file's future."""
+    before = None                                         # the uploader of the file in front
+    try:
         for k, (path, raw, fut) in enumerate(todo):
             if _QUIESCE.is_set():                         # (the run is over: nobody will ask for this file's table)
                 if not fut.done():
@@ -725,28 +780,9 @@ def prefetch_member_tables(paths: Sequence[str]) -> None:
                 threads = max(2, many // 2) if k == 0 else max(2, many // 4)
                 n_raw = int(raw.shape[0])
                 if k == 0 and first_run and n_raw > GPU_INFLATE_MAX + (GPU_INFLATE_MAX >> 6):
-                    # (more bytes than a whole-file ingestion may inflate to: run by run for certain.)  The table of the beginning of
-                    # the file, the first run on its way, and only then the walk through the rest of the file's members
-                    engine = default_engine()
-                    # (5/8 of a run's inflated size in file bytes holds a whole first run at the usual 2.4 - 4 : 1; four times a
-                    # run's size holds eight more: a second of inflate, which covers the walk through the rest)
-                    limits = [x for x in (BAM_CHUNK_BYTES * 5 // 8, BAM_CHUNK_BYTES * 4) if x < n_raw]
-                    rests = [Future() for _ in limits]
-                    first = table(path, raw, threads, limit=limits[0]) if limits else table(path, raw, threads)
-                    members = _Members(engine, BAM_CHUNK_BYTES, first[0], first[1], rests[0] if rests else None)
-                    before = _RunUploads(engine, raw, members)
-                    fut.set_result((members, before))
-                    nxt = first
-                    for j, rest in enumerate(rests):
-                        try:
-                            nxt = table(path, raw, threads, limit=limits[j + 1] if j + 1 < len(limits) else None, known=nxt)
-                            rest.set_result((nxt[0], nxt[1], rests[j + 1] if j + 1 < len(rests) else None))
-                        except BaseException as e:        # noqa: BLE001  (raised where the run behind the known ones is asked for)
-                            for r in rests[j:]:
-                                r.set_exception(e)
-                            break
+                    before = _first_file_in_pieces(path, raw, fut, threads)
                     continue
-                pos, isz = later.pop(k).result() if k in later else table(path, raw, threads)
+                pos, isz = later.pop(k).result() if k in later else _table_ahead(path, raw, threads)
                 if first_run and n_raw > GPU_INFLATE_MAX // 8 and int(isz.sum()) > GPU_INFLATE_MAX:
                     engine = default_engine()
                     members = _Members(engine, BAM_CHUNK_BYTES, pos, isz)
@@ -761,17 +797,9 @@ def prefetch_member_tables(paths: Sequence[str]) -> None:
             except BaseException as e:                    # noqa: BLE001  (handed to the thread that asks for the table)
                 if not fut.done():
                     fut.set_exception(e)
-
-    def chain_and_pool():
-        try:
-            chain()
-        finally:
-            if later_pool is not None:
-                later_pool.shutdown(wait=True)
-
-    th = threading.Thread(target=chain_and_pool, daemon=True)
-    _CHAINS.append(th)
-    th.start()
+    finally:
+        if later_pool is not None:
+            later_pool.shutdown(wait=True)
 
 
 _CHAINS: List[threading.Thread] = []    # the helper threads of prefetch_member_tables (quiesce_ahead joins them)
@@ -791,8 +819,7 @@ def start_ingest_ahead(bam_files: Sequence[str], chrs_list, filt: Tuple[int, int
     The helper is the ONLY user of the default engine's context until filter() has taken its result (filter() asks for it
     before it touches the context; the N scan meanwhile runs on a context and stream of its own: get_Ns_ref).  Whatever the
     ingestion raises is raised by filter() where bam_join_input() would have raised it."""
-    from concurrent.futures import Future
-    if (os.environ.get("GCI_INGEST_AHEAD", "1") == "0" or os.environ.get("GCI_BAM_INGEST", "gpu") != "gpu" or _sharded()
+    if (os.environ.get("GCI_INGEST_AHEAD", "1") == "0" or _ingest_mode() != "gpu" or _sharded()
             or not bam_files or bam_files[0] in _INGEST_AHEAD):
         return
     path = bam_files[0]
@@ -856,23 +883,32 @@ def _drop_ahead(ahead) -> None:
     ahead[1].add_done_callback(done)
 
 
+def _ingest_mode() -> str:                                      # (bam_join_input's `ingest`, where the caller does not say)
+    return os.environ.get("GCI_BAM_INGEST", "gpu")
+
+
+def _ref_sel(engine: Engine, hdr, targets: Sequence[str], own: Optional[Sequence[str]] = None) -> Buffer:
+    """refID of the file -> index in `targets` (-1: not selected -- or, with `own`, not one of this rank's contigs), on the device."""
+    for t in targets:
+        if t not in hdr.references:
+            raise ValueError(f"invalid contig `{t}`")          # what pysam's fetch() raises
+    tindex = {t: i for i, t in enumerate(targets)}
+    keep = tindex if own is None else set(own)
+    return engine.to_device(np.asarray([tindex[r] if r in keep else -1 for r in hdr.references], dtype=np.int32))
+
+
 def bam_join_input(engine: Engine, path: str, targets: Sequence[str], filt: Tuple[int, int, float, float],
                    threads: int = 1, chunk_bytes: Optional[int] = None, ingest: Optional[str] = None) -> JoinInput:
     """K1 over one BAM file -> the file's join input (compact records + where their names are).
 
     ingest = "gpu" (default; GCI_BAM_INGEST overrides): the file's bytes are uploaded as they are and inflated on the
-    device, the record offsets come from the parallel walk (_bam_join_input_gpu); a stream that walk cannot follow
-    takes the next path.
+    device, the record offsets come from the parallel walk (_ingest_gpu); a stream that walk cannot follow takes the next
+    path.
     ingest = "heads": the native host pipeline (gci_bam_heads) inflates the file group by group and keeps every record
     without its SEQ / QUAL bytes; only that heads stream (about 400 B of a 27 KB HiFi record) is uploaded and filtered
-    through its record pages; names stay addressable inside those.
-    ingest = "full" (or an explicit chunk_bytes): the whole stream, inflated on the host, goes to the device.  Small
-    files: one upload.  Large files: groups of BGZF members are inflated into a host buffer (the next group on a
-    background thread while the GPU works on the current one), the partial record at the end of a group is carried
-    over, K1 runs per chunk and only the 32-byte records and the packed names (gci_pack_names) are kept on the device."""
-    from concurrent.futures import ThreadPoolExecutor
-    from . import hostio
-    ingest = ingest or ("full" if chunk_bytes else os.environ.get("GCI_BAM_INGEST", "gpu"))
+    through its record pages; names stay addressable inside those (_ingest_heads).
+    ingest = "full" (or an explicit chunk_bytes): the whole stream, inflated on the host, goes to the device (_ingest_full)."""
+    ingest = ingest or ("full" if chunk_bytes else _ingest_mode())
     if ingest not in ("heads", "full", "gpu"):
         raise ValueError("ingest must be 'heads', 'full' or 'gpu'")
     chunk_bytes = int(chunk_bytes or BAM_CHUNK_BYTES)
@@ -882,76 +918,75 @@ def bam_join_input(engine: Engine, path: str, targets: Sequence[str], filt: Tupl
         _drop_ahead(ahead)
         ahead = None
     raw = ahead[0] if ahead is not None else (np.memmap(path, dtype=np.uint8, mode="r") if os.path.getsize(path) else np.zeros(0, np.uint8))
-    map_qual, mq_cutoff, clip_percent, iden_percent = filt
-
-    def ref_sel_for(hdr):
-        for t in targets:
-            if t not in hdr.references:
-                raise ValueError(f"invalid contig `{t}`")          # what pysam's fetch() raises
-        tindex = {t: i for i, t in enumerate(targets)}
-        return engine.to_device(np.asarray([tindex.get(r, -1) for r in hdr.references], dtype=np.int32))
-
+    ref_sel_for = lambda hdr: _ref_sel(engine, hdr, targets)      # noqa: E731
+    ji = None
     if ingest == "gpu":
-        # N1 on the device: the file's bytes are uploaded as they are, the BGZF members are inflated there
-        # (gci_bgzf_inflate_device, CRC verified), the record offsets come from a parallel walk
-        # (gci_bam_record_offsets_device) and K1 runs over the inflated stream.  A stream the parallel walk cannot follow
-        # takes the heads path below.
-        # (the member table is made on the host while the file's bytes are on their way to the device; a file that may not
-        # fit -- BGZF deflates BAM 2.4 - 4 : 1 -- is uploaded run by run instead)
-        upload = None
+        ji = _ingest_gpu(engine, path, raw, ahead, chunk_bytes, ref_sel_for, filt)
+        if ji is not None:
+            _drop_later(raw)                                  # (the unmapping, off this thread)
+            return ji
+    if ingest != "full":
+        ji = _ingest_heads(engine, raw, nthreads, ref_sel_for, filt)
+    return ji if ji is not None else _ingest_full(engine, path, raw, nthreads, chunk_bytes, ref_sel_for, filt)
+
+
+def _ingest_gpu(engine: Engine, path: str, raw, ahead, chunk_bytes: int, ref_sel_for, filt) -> Optional[JoinInput]:
+    """N1 on the device: the file's bytes are uploaded as they are, the BGZF members are inflated there (gci_bgzf_inflate_device, CRC
+    verified), the record offsets come from a parallel walk (gci_bam_record_offsets_device) and K1 runs over the inflated stream.  The
+    member table is made on the host while the file's bytes are on their way to the device; a file that may not fit -- BGZF deflates BAM
+    2.4 - 4 : 1 -- is uploaded run by run instead.  `ahead`: from prefetch_member_tables.  None: the members are empty, or the walk lost the chain."""
+    upload = uploads = None
+    try:
         if 0 < raw.shape[0] <= GPU_INFLATE_MAX // 8:
             upload = engine.start_upload(raw, parts=2 if raw.shape[0] >= (256 << 20) else 1)
-        members = uploads = None
-        try:
-            with phases.wall("bgzf_member_table"):
-                if ahead is not None:
-                    members, uploads = ahead[1].result()
-                else:
-                    members = hostio.bgzf_blocks(np.asarray(raw))
-        except BaseException:
-            if upload is not None:
-                upload["pool"].shutdown()
-            raise
+        with phases.wall("bgzf_member_table"):
+            if ahead is not None:
+                members, uploads = ahead[1].result()
+            else:
+                members = hostio.bgzf_blocks(np.asarray(raw))
         if isinstance(members, _Members) and (members.engine is not engine or members.chunk_bytes != chunk_bytes):
             if uploads is not None:
                 uploads.close()                               # (made for another engine or other runs: not this call's)
             members, uploads = members.whole(), None
         if not isinstance(members, _Members):
             members = _Members(engine, chunk_bytes, members[0], members[1])
-        if members.lazy() or int(members.isz.sum()) > 0:
-            with phases.wall("bam_ingest (upload | inflate + crc | record walk | pages | filter, overlapped)"):
-                try:
-                    ji = _bam_join_input_gpu(engine, path, raw, members, ref_sel_for, filt, upload, uploads)
-                finally:
-                    if uploads is not None:
-                        uploads.close()                       # (idempotent: a failure in front of the run loop leaves it open)
-                if phases.on():
-                    engine.T.synchronize()
+        if not members.lazy() and int(members.isz.sum()) == 0:
+            return None
+        with phases.wall("bam_ingest (upload | inflate + crc | record walk | pages | filter, overlapped)"):
+            ji = _bam_join_input_gpu(engine, path, raw, members, ref_sel_for, filt, upload, uploads)
             if phases.on():
-                pos, isz = members.whole()
-                phases.add("bgzf_bytes", int(raw.shape[0]))
-                phases.add("bgzf_members", int(isz.shape[0]))
-                phases.add("inflated_bytes", int(isz.sum()))
-            if ji is not None:
-                _drop_later(raw)                              # (the unmapping, off this thread)
-                del raw
-                return ji
-        elif upload is not None:
-            upload["pool"].shutdown()
-        ingest = "heads"
-    if ingest == "heads":
-        try:
-            heads = hostio.bam_heads(np.asarray(raw), threads=nthreads, check_crc=BGZF_CRC)
-        except GciError as e:
-            if e.status != _lib.GCI_E_NOMEM:
-                raise
-            heads = None              # the address-space reservation was refused (strict overcommit): whole-stream ingestion
-        if heads is not None:
-            with heads:
-                hdr = bamfmt.parse_header(heads.stream)
-                d_bam, d_off = engine.to_device(heads.stream), engine.to_device(heads.offsets)
-            return _filter_stream(engine, d_bam, d_off, False, ref_sel_for(hdr), filt)
+                engine.T.synchronize()
+        if phases.on():
+            isz = members.whole()[1]
+            phases.add("bgzf_bytes", int(raw.shape[0]))
+            phases.add("bgzf_members", int(isz.shape[0]))
+            phases.add("inflated_bytes", int(isz.sum()))
+        return ji
+    finally:                                                  # every way out, a failure in front of the first run included
+        if upload is not None:
+            upload.close()
+        if uploads is not None:
+            uploads.close()                                   # (idempotent)
 
+
+def _ingest_heads(engine: Engine, raw, nthreads: int, ref_sel_for, filt) -> Optional[JoinInput]:
+    """The heads stream of the host pipeline, uploaded and filtered.  None: gci_bam_heads was refused its address space (strict overcommit)."""
+    try:
+        heads = hostio.bam_heads(np.asarray(raw), threads=nthreads, check_crc=BGZF_CRC)
+    except GciError as e:
+        if e.status != _lib.GCI_E_NOMEM:
+            raise
+        return None
+    with heads:
+        hdr = bamfmt.parse_header(heads.stream)
+        d_bam, d_off = engine.to_device(heads.stream), engine.to_device(heads.offsets)
+    return _filter_stream(engine, d_bam, d_off, False, ref_sel_for(hdr), filt)
+
+
+def _ingest_full(engine: Engine, path: str, raw, nthreads: int, chunk_bytes: int, ref_sel_for, filt) -> JoinInput:
+    """The stream inflated on the host.  Up to chunk_bytes: one upload.  Larger: groups of BGZF members are inflated into a host buffer
+    (the next group on a background thread while the GPU works on the current one), the partial record at the end of a group is
+    carried over, K1 runs per chunk and only the 32-byte records and the packed names (gci_pack_names) are kept on the device."""
     pos, isz = hostio.bgzf_blocks(np.asarray(raw))
     if int(isz.sum()) <= chunk_bytes:
         stream = hostio.bgzf_inflate(np.asarray(raw), threads=nthreads, check_crc=BGZF_CRC)
@@ -959,23 +994,14 @@ def bam_join_input(engine: Engine, path: str, targets: Sequence[str], filt: Tupl
         offs, _ = hostio.bam_record_offsets(stream)
         d_bam, d_off = engine.to_device(stream), engine.to_device(offs)
         return _filter_stream(engine, d_bam, d_off, True, ref_sel_for(hdr), filt)
-
-    # ---- streamed ------------------------------------------------------------------------------------------
-    groups, a, acc = [], 0, 0
-    for i, sz in enumerate(isz.tolist()):
-        if acc and acc + sz > chunk_bytes:
-            groups.append((a, i))
-            a, acc = i, 0
-        acc += sz
-    groups.append((a, len(isz)))
+    groups = _runs_of_members(engine, isz, chunk_bytes, whole_rounds=False)
 
     def inflate(g):
         lo, hi = g
         return hostio.bgzf_inflate(np.asarray(raw[int(pos[lo]):int(pos[hi])]), threads=nthreads, check_crc=BGZF_CRC)
 
-    parts: List[JoinInput] = []
     carry = np.zeros(0, dtype=np.uint8)
-    n_done, hdr, ref_sel = 0, None, None
+    hdr = parts = None
     with ThreadPoolExecutor(1) as ex:
         nxt = ex.submit(inflate, groups[0])
         for k in range(len(groups)):
@@ -990,26 +1016,19 @@ def bam_join_input(engine: Engine, path: str, targets: Sequence[str], filt: Tupl
                 except Exception:                              # header longer than one chunk: keep accumulating
                     carry = buf
                     continue
-                start, ref_sel = hdr.first_record, ref_sel_for(hdr)
+                start, parts = hdr.first_record, _Parts(engine, ref_sel_for(hdr), filt)
             offs, used = hostio.bam_chunk_offsets(buf, start)
             carry = buf[used:].copy()
             if offs.shape[0] == 0:
                 continue
             d_buf, d_off = engine.to_device(buf[:used]), engine.to_device(offs)
-            try:
-                ji = _filter_stream(engine, d_buf, d_off, True, ref_sel, filt, rec_idx_base=n_done)
-            except GciError as e:
-                if e.rec >= 0:
-                    e.rec += n_done
-                raise
-            parts.append(_keep_part(engine, ji))
-            n_done += int(offs.shape[0])
-            del d_buf, d_off, ji
+            parts.add(d_buf, d_off)
+            del d_buf, d_off
     if carry.shape[0]:
         raise bamfmt.BAMError("truncated BAM: %d trailing bytes do not form a record" % carry.shape[0])
     if hdr is None:
         raise bamfmt.BAMError("no BAM header in %s" % path)
-    return _concat_parts(engine, parts)
+    return parts.result()
 
 
 def filter(paf_files=[], bam_files=[], prefix="GCI", map_qual=30, mq_cutoff=50, iden_percent=0.9,  # noqa: A001
@@ -1032,7 +1051,6 @@ def filter(paf_files=[], bam_files=[], prefix="GCI", map_qual=30, mq_cutoff=50, 
     first = bamfmt.read_header(bam_files[0])
     targets_length = _targets_of(first, chrs_list)
     targets = list(targets_length.keys())
-    tindex = {t: i for i, t in enumerate(targets)}
     filt = (map_qual, mq_cutoff, clip_percent, iden_percent)
     # The depth track is asked for NOW, while the first file is still being ingested on its helper thread (this thread would only
     # wait for it): a driver allocation costs by the GB on this chip -- the kernel driver clears VRAM it does not know to be clean,
@@ -1059,7 +1077,6 @@ def filter(paf_files=[], bam_files=[], prefix="GCI", map_qual=30, mq_cutoff=50, 
     if len(paf_files) != 0:
         try:
             if PAF_FILTER == "host":                          # the native host filter (host_io.cpp), kept as a switch
-                from . import hostio
                 native = hostio.paf_filter(paf_files, targets, map_qual, mq_cutoff, iden_percent, threads=hostio.pick_threads(threads))
                 inputs += [JoinInput(engine.to_device(r), engine.to_device(nm), engine.to_device(off), 0) for r, nm, off in native]
             else:                                             # K2: tokeniser, grouping and scoring on the GPU
@@ -1091,18 +1108,26 @@ def filter(paf_files=[], bam_files=[], prefix="GCI", map_qual=30, mq_cutoff=50, 
     with phases.wall("depth_build"), phases.gpu("depth build"):
         fused = engine.depth_build_fused(ivl, count, flank_len, track, want_text=False, want_sums=True,
                                          issue=issue_hint, counted=True, want_runs=bool(write))
-    depths = DepthTracks(engine, targets_length, track)
+    depths = _depths_of_build(engine, targets_length, targets, track, fused, issue_hint, log_reads_type, directory, prefix, write, from_build=True)
+    return depths, targets_length
+
+
+def _depths_of_build(engine: Engine, tl: Dict[str, int], all_targets: List[str], track: Buffer, fused: dict, issue_hint, log_reads_type,
+                     directory, prefix, write, from_build: bool) -> DepthTracks:
+    """The tail of filter(): the track a fused build has just written, with the build's by-products, and its file.  from_build: the
+    build kept its run lists for the writer (the single-process filter(), which also puts the write in the phase log)."""
+    depths = DepthTracks(engine, tl, track)
+    depths.all_targets = all_targets
     depths._fresh_sums = fused["sums"]
     if issue_hint is not None:
         depths._fresh_runs = (tuple(float(x) for x in issue_hint[:2]) + (int(issue_hint[2]),), fused["runs"])
-
     print(f"Filtering {log_reads_type} alignment files done!!!")
     if write:
         print(f'Writing depths into "{directory}/{prefix}.depth.gz" ...')
-        with phases.wall("write_depth_gz (deflate on the device, D2H, file)"):
-            _write_depth_members(directory, prefix, depths, from_build=True)         # (the build just above kept its run lists)
+        with phases.wall("write_depth_gz (deflate on the device, D2H, file)") if from_build else contextlib.nullcontext():
+            _write_depth_members(directory, prefix, depths, from_build=from_build)
         print("Writing depths done!!!\n\n")
-    return depths, targets_length
+    return depths
 
 
 # ==============================================================================================
@@ -1118,17 +1143,10 @@ def bam_records_of_contigs(engine: Engine, path: str, targets: Sequence[str], ow
     chunks) gives the virtual offsets of the contig's first record and of the end of its last one; that run of members
     is inflated and walked on the device (GCI_BAM_INGEST=gpu, the default) or on host threads.  Without an index the
     whole file is ingested and K1 drops the records of the other contigs."""
-    from . import hostio
-    map_qual, mq_cutoff, clip_percent, iden_percent = filt
     hdr = bamfmt.read_header(path)
-    for t in targets:
-        if t not in hdr.references:
-            raise ValueError(f"invalid contig `{t}`")              # what pysam's fetch() raises
-    tindex = {t: i for i, t in enumerate(targets)}
+    ref_sel = _ref_sel(engine, hdr, targets, own)
     own_set = set(own)
-    ref_sel = engine.to_device(np.asarray([tindex[r] if r in own_set else -1 for r in hdr.references], dtype=np.int32))
     index = bamfmt.read_bai(path + ".bai")
-    dev = engine.device
     nthreads = hostio.pick_threads(threads)
     if index is None or len(index) != len(hdr.references):
         raw = np.fromfile(path, dtype=np.uint8)
@@ -1137,9 +1155,8 @@ def bam_records_of_contigs(engine: Engine, path: str, targets: Sequence[str], ow
         return _filter_stream(engine, d_bam, d_off, False, ref_sel, filt)
     raw = np.memmap(path, dtype=np.uint8, mode="r")
     n_raw = int(raw.shape[0])
-    on_device = os.environ.get("GCI_BAM_INGEST", "gpu") == "gpu"
-    parts: List[JoinInput] = []
-    n_done = 0
+    on_device = _ingest_mode() == "gpu"
+    parts = _Parts(engine, ref_sel, filt)
     for r, name in enumerate(hdr.references):
         if name not in own_set or index[r] is None:
             continue
@@ -1171,12 +1188,8 @@ def bam_records_of_contigs(engine: Engine, path: str, targets: Sequence[str], ow
         if on_device and int(isz[a:last + 1].sum()) <= GPU_INFLATE_MAX:
             # the run's members inflated and walked on the device (N1, as in bam_join_input)
             p0 = int(pos[a])
-            try:
+            with _rebased(a):
                 d_run = engine.bgzf_inflate(raw[p0:int(pos[last + 1])], pos[a:last + 2] - np.uint64(p0), isz[a:last + 1], check_crc=BGZF_CRC)
-            except GciError as e:
-                if e.rec >= 0:
-                    e.rec += a
-                raise
             d_off, used, ok = engine.bam_record_offsets(d_run[:stop], beg & 0xFFFF, len(hdr.references))
             if ok and used == stop:
                 d_buf = d_run[:stop]
@@ -1188,16 +1201,12 @@ def bam_records_of_contigs(engine: Engine, path: str, targets: Sequence[str], ow
         if d_off.shape[0] == 0:
             continue
         try:
-            ji = _filter_stream(engine, d_buf, d_off, True, ref_sel, filt, rec_idx_base=n_done)
+            parts.add(d_buf, d_off)
         except GciError as e:
-            if e.rec >= 0:
-                e.rec += n_done
-            e.contig = tindex[name]                 # (the ranks agree on the error of the earliest contig: _agree_on_error)
+            e.contig = targets.index(name)          # (the ranks agree on the error of the earliest contig: _agree_on_error)
             raise
-        parts.append(_keep_part(engine, ji))
-        n_done += int(d_off.shape[0])
-        del d_buf, d_off, ji
-    return _concat_parts(engine, parts)
+        del d_buf, d_off
+    return parts.result()
 
 
 def _replicate(engine: Engine, ji: JoinInput) -> JoinInput:
@@ -1257,8 +1266,7 @@ def _filter_sharded(paf_files, bam_files, prefix, map_qual, mq_cutoff, iden_perc
     the names it owns (round 2's way)."""
     from . import shard
     first = bamfmt.read_header(bam_files[0])
-    pairs = [(r, l) for r, l in zip(first.references, first.lengths) if (len(chrs_list) == 0 or r in chrs_list)]
-    targets_length = {r: l for r, l in pairs}
+    targets_length = _targets_of(first, chrs_list)
     targets = list(targets_length.keys())
     mine = SHARD.assign([targets_length[t] for t in targets])
     if SHARD.world > len(targets):                  # (every rank sees this: rank 0 says it)
@@ -1331,16 +1339,7 @@ def _filter_sharded(paf_files, bam_files, prefix, map_qual, mq_cutoff, iden_perc
             engine._chk(engine.lib.gci_join_mode(engine.ctx, engine.join_mode), "gci_join_mode")
     track = engine.new_track()
     fused = engine.depth_build_fused(ivl, None, flank_len, track, want_text=False, want_sums=True, issue=issue_hint, counted=False)
-    depths = DepthTracks(engine, local_tl, track)
-    depths.all_targets = targets
-    depths._fresh_sums = fused["sums"]
-    if issue_hint is not None:
-        depths._fresh_runs = (tuple(float(x) for x in issue_hint[:2]) + (int(issue_hint[2]),), fused["runs"])
-    print(f"Filtering {log_reads_type} alignment files done!!!")
-    if write:
-        print(f'Writing depths into "{directory}/{prefix}.depth.gz" ...')
-        _write_depth_members(directory, prefix, depths)
-        print("Writing depths done!!!\n\n")
+    depths = _depths_of_build(engine, local_tl, targets, track, fused, issue_hint, log_reads_type, directory, prefix, write, from_build=False)
     return depths, targets_length
 
 
@@ -1396,7 +1395,6 @@ def _write_depth_members(directory, prefix, depths: DepthTracks, from_build: boo
     """'>contig' member (host), then the contig's lines as the members the device wrote.  Contig-sharded run: every rank
     deflates the contigs it owns, rank 0 gathers the members and writes them in header order.  from_build: only filter() says
     so, for the track its own build has just written (Engine.depth_deflate)."""
-    from . import hostio
     blobs = depths.engine.depth_deflate(depths.track, from_build=from_build)               # views of the engine's pinned staging buffer
     items = list(zip(depths.targets, depths.lengths, blobs))
     if _sharded():
@@ -1716,7 +1714,6 @@ def read_depth_tracks(engine: Engine, path: str, ref_lengths: Optional[Dict[str,
     (gci_depth_text_parse).  Text outside the strict grammar, and a file the native inflate refuses, take the reference's own
     statements on the host (rare: hand-made files).  ref_lengths: when a contig of the file is not among them nothing is
     uploaded and the tracks are None (the caller refuses the file)."""
-    from . import hostio
     from .formats import depthfile
     raw = np.fromfile(path, dtype=np.uint8)
     try:
@@ -1779,7 +1776,6 @@ def convert_samtools_depth(engine: Optional[Engine], path: str, prefix: str) -> 
     A file larger than GCI_SDEPTH_RESIDENT_MAX bytes (default 64 GiB) goes through in pieces of GCI_SDEPTH_CHUNK_BYTES cut at line
     ends, twice: once to index, once to parse.  Text outside the strict grammar, and an empty file, take the reference's own
     statements on the host (formats.depthfile.convert_samtools_host).  -> the path taken: "device", "device-chunked" or "host"."""
-    from . import hostio
     from .formats import depthfile
     out = f"{prefix}.depth.gz"
     open(out, "wb").close()                                    # (the reference opens its output first: it exists when the input does not)

@@ -347,6 +347,42 @@ def test_streamed_bam_ingestion_equals_one_shot(engine, oracle, tmp_path, monkey
             assert np.array_equal(depths[t], want2[t]), (knob, kw, t)
 
 
+def test_first_error_keeps_its_file_index_across_run_cuts(engine, tmp_path, monkeypatch):
+    """A record the reference dies on (mapped, primary, MAPQ 60, on the target, no NM tag) at index j of the file: every
+    ingestion mode raises GciError(GCI_E_NO_NM) with rec == j -- the index in the FILE, also where the file goes through the
+    device in runs and K1 counts from the beginning of each.  j is known by construction: the record is put there."""
+    from gci_amd import _lib, hostio
+    from gci_amd.formats import bam
+    rs = synth.simulate_reads((("a", 400_000),), 8, "hifi", seed=5).sorted()
+    stream, offs = synth.to_bam_stream(rs)
+    j = len(rs) - len(rs) // 20                                      # in the last tenth of the file
+    bad = bam.encode_record(0, 1000, "no_nm", 60, 0, [(0, 100)], 100, bam.encode_aux([("AS", "i", 0)]))
+    at, behind = int(offs[j]), int(offs[j + 1])
+    stream = np.concatenate([stream[:at], np.frombuffer(bad, dtype=np.uint8), stream[behind:]])
+    p = str(tmp_path / "nonm.bam")
+    bam.write_bam_stream(p, stream, level=1, threads=4)
+    # not vacuous: the run-by-run case cuts at least three runs, and record j lies behind the first of them
+    pos, isz = hostio.bgzf_blocks(np.fromfile(p, dtype=np.uint8))
+    runs = pipeline._Members(engine, 400_000, pos, isz)
+    assert len(runs.run_bytes()) >= 3
+    lo, hi = runs.group(0)
+    assert int(isz[lo:hi].sum()) <= at and len(rs) * 9 // 10 <= j < len(rs)
+    monkeypatch.delenv("GCI_BAM_INGEST", raising=False)
+    engine.set_layout([400_000])
+    modes = [("whole", {}, {}), ("run by run", {"GPU_INFLATE_MAX": 0, "BAM_CHUNK_BYTES": 400_000}, {}),
+             ("full", {}, {"ingest": "full", "chunk_bytes": 300_000}), ("heads", {}, {"ingest": "heads"})]
+    got = {}
+    for mode, knobs, kw in modes:
+        with monkeypatch.context() as m:
+            for k, v in knobs.items():
+                m.setattr(pipeline, k, v)
+            with pytest.raises(GciError) as e:
+                pipeline.bam_join_input(engine, p, ["a"], (30, 50, 0.1, 0.9), threads=4, **kw)
+        got[mode] = (e.value.status, e.value.rec)
+    print("j", j, got)
+    assert got == {mode: (_lib.GCI_E_NO_NM, j) for mode, _, _ in modes}
+
+
 @pytest.mark.parametrize("layout,events", [("chm13", "atomic"), ("diploid", "radix")])
 def test_genome_scale_layout_chm13(engine, oracle, layout, events, monkeypatch):
     """BASELINE configs[2] geometry: CHM13 (25 contigs, 3.117 Gb => 761 k tiles, > 2^31 elements in one track).

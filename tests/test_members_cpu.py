@@ -50,6 +50,18 @@ def test_runs_of_members_equal_the_loop():
         assert pipeline._runs_of_members(eng, isz, chunk) == _loop_runs(eng, isz, chunk)
 
 
+def test_runs_without_whole_rounds_equal_the_loop_whatever_the_decode_round():
+    """What the host-streamed ingestion cuts its member groups with: no decode round applied, the engine's not asked for."""
+    rng = np.random.default_rng(11)
+    for _ in range(200):
+        n = int(rng.integers(1, 4000))
+        _, isz = _table(rng, n)
+        chunk = int(rng.integers(70_000, 6_000_000))
+        want = _loop_runs(_Rounds(0), isz, chunk)
+        for r in (0, 7, 64):
+            assert pipeline._runs_of_members(_Rounds(r), isz, chunk, whole_rounds=False) == want
+
+
 @pytest.mark.parametrize("pieces", [1, 2, 3])
 def test_members_in_pieces_cover_the_file(pieces):
     rng = np.random.default_rng(pieces)

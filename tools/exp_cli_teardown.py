@@ -23,9 +23,8 @@ for it in range(3):
     ji = pipeline._bam_join_input_gpu(eng, p, raw, pipeline._Members(eng, pipeline.BAM_CHUNK_BYTES, pos, isz), lambda hdr: eng.to_device(np.zeros(1, np.int32)), filt, upload)
     mark("_bam_join_input_gpu")
     torch.cuda.synchronize(); mark("sync")
-    up_keys = list(upload.keys())
-    d_raw = upload.pop("d_raw"); del d_raw; mark("del d_raw")
-    pool = upload.pop("pool"); pool.shutdown(); del pool; mark("pool.shutdown")
+    upload.d_raw = None; mark("del d_raw")
+    upload.close(); mark("pool.shutdown")
     del upload; mark("del upload")
     del raw; mark("del raw (munmap)")
     del ji; mark("del ji")
