@@ -132,6 +132,9 @@ EXPORTS = [
     ("gci_depth_text_parse", c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_uint32, c_void_p, c_uint64]),
     ("gci_sdepth_index", c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p]),
     ("gci_sdepth_parse", c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_void_p, c_uint32, c_void_p, c_uint64]),
+    ("gci_depth_gz_scan", c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_void_p]),
+    ("gci_depth_gz_runs", c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_void_p]),
+    ("gci_depth_gz_expand", c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint64]),
     ("gci_paf_filter", c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, ctypes.c_double, c_int, c_void_p, c_void_p]),
     ("gci_paf_count", c_uint64, [c_void_p, c_int]),
     ("gci_paf_name_bytes", c_uint64, [c_void_p, c_int]),

@@ -77,6 +77,9 @@ EXPORTS = [
     ("gci_depth_text_parse", c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_uint32, c_void_p, c_uint64]),
     ("gci_sdepth_index", c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p]),
     ("gci_sdepth_parse", c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_void_p, c_uint32, c_void_p, c_uint64]),
+    ("gci_depth_gz_scan", c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_void_p]),
+    ("gci_depth_gz_runs", c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_void_p]),
+    ("gci_depth_gz_expand", c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint64]),
 ]
 
 
@@ -318,6 +321,36 @@ class CpuEngine:
         self._chk(self.lib.gci_depth_text_parse(self.ctx, _p(text), text.shape[0], _p(line0), _p(segs), segs.shape[0], _p(track),
                                                 track.shape[0]), "gci_depth_text_parse")
         return track
+
+    # ---- this project's own .depth.gz to a track without inflating it (k_depth_gz.hip's twin)
+    def depth_gz_scan(self, raw: np.ndarray, cand_pos: np.ndarray) -> np.ndarray:
+        """-> DGZ_INFO_DTYPE per candidate member start: status, end offset, lines, runs, CRC-32 / ISIZE verdicts."""
+        from .formats.depthfile import DGZ_INFO_DTYPE
+        raw = np.ascontiguousarray(raw, dtype=np.uint8)
+        cand = np.ascontiguousarray(cand_pos, dtype=np.uint64)
+        info = np.zeros(cand.shape[0], dtype=DGZ_INFO_DTYPE)
+        self._chk(self.lib.gci_depth_gz_scan(self.ctx, _p(raw), raw.shape[0], _p(cand), cand.shape[0], _p(info)), "gci_depth_gz_scan")
+        return info
+
+    def depth_gz_runs(self, raw: np.ndarray, members: np.ndarray) -> np.ndarray:
+        """members: DGZ_MEMBER_DTYPE (pos, run0, runs as the scan reported them) -> DGZ_RUN_DTYPE, every member's runs at its run0."""
+        from .formats.depthfile import DGZ_MEMBER_DTYPE, DGZ_RUN_DTYPE
+        raw = np.ascontiguousarray(raw, dtype=np.uint8)
+        members = np.ascontiguousarray(members, dtype=DGZ_MEMBER_DTYPE)
+        runs = np.zeros(max(int(members["runs"].astype(np.uint64).sum()), 1), dtype=DGZ_RUN_DTYPE)
+        self._chk(self.lib.gci_depth_gz_runs(self.ctx, _p(raw), raw.shape[0], _p(members), members.shape[0], _p(runs)), "gci_depth_gz_runs")
+        return runs
+
+    def depth_gz_expand(self, runs: np.ndarray, members: np.ndarray, track: np.ndarray) -> np.ndarray:
+        from .formats.depthfile import DGZ_MEMBER_DTYPE
+        members = np.ascontiguousarray(members, dtype=DGZ_MEMBER_DTYPE)
+        self._chk(self.lib.gci_depth_gz_expand(self.ctx, _p(runs), _p(members), members.shape[0], _p(track), track.shape[0]),
+                  "gci_depth_gz_expand")
+        return track
+
+    def depth_gz_track(self, raw: np.ndarray, members: np.ndarray, track: np.ndarray) -> np.ndarray:
+        """The members' lines into `track` at each member's elem0 (device.Engine.depth_gz_track's twin)."""
+        return self.depth_gz_expand(self.depth_gz_runs(raw, members), members, track)
 
     # ---- samtools depth text to a track (k_sdepth.hip's twin)
     def sdepth_index(self, text: np.ndarray, prev_name: bytes = b"", cap: int = 1 << 10) -> Tuple[np.ndarray, np.ndarray, int]:

@@ -778,6 +778,175 @@ int gci_depth_deflate_write(gci_ctx* ctx, const int32_t* depth, const uint64_t* 
 
 }  // extern "C"
 
+/* ---- this library's own .depth.gz -> track without inflating it (k_depth_gz.hip) --------------------------------------------------------
+ * The grammar of include/gci_hip.h, read a bit at a time against RFC 1951's tables; the CRC of a member is taken over the text of its
+ * runs, byte by byte: no GF(2) algebra to agree with.  Like the device, a token is only looked at with 20 bits in hand. */
+namespace {
+const uint16_t DGZ_LEN_BASE[29] = {3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258};
+const uint8_t DGZ_LEN_EXTRA[29] = {0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0};
+const uint16_t DGZ_DIST_BASE[8] = {1, 2, 3, 4, 5, 7, 9, 13};
+const uint8_t DGZ_DIST_EXTRA[8] = {0, 0, 0, 0, 1, 1, 2, 2};
+
+struct DgzBits {
+    const uint8_t* raw;
+    uint64_t n_bits, at;
+    bool has(uint64_t k) const { return n_bits - at >= k; }
+    uint32_t bit() { const uint32_t v = (raw[at >> 3] >> (at & 7u)) & 1u; at++; return v; }
+    uint32_t value(uint32_t k) { uint32_t v = 0; for (uint32_t i = 0; i < k; i++) v |= bit() << i; return v; }     // LSB first
+    uint32_t code(uint32_t k) { uint32_t v = 0; for (uint32_t i = 0; i < k; i++) v = (v << 1) | bit(); return v; }  // Huffman: MSB first
+};
+
+struct DgzMember { uint64_t end = 0; uint32_t lines = 0, crc_file = 0, isize_file = 0; };
+
+// on_run(depth, lines) for every run as it closes (false: stop) -> false: not this writer's
+template <typename F>
+bool dgz_decode(const uint8_t* raw, uint64_t n, uint64_t pos, F on_run, DgzMember& out)
+{
+    static const uint8_t head[10] = {0x1F, 0x8B, 8, 0, 0, 0, 0, 0, 0, 0xFF};
+    if (pos >= n || n - pos < 10 || memcmp(raw + pos, head, 10) != 0) return false;
+    DgzBits b{raw, n * 8, (pos + 10) * 8};
+    uint32_t blocks = 0, lines = 0;
+    bool prev_fixed = false;
+    for (;;) {
+        if (!b.has(3)) return false;
+        const uint32_t bfinal = b.bit(), btype = b.value(2);
+        if (btype == 0) {
+            if (!prev_fixed || bfinal) return false;
+            b.at = (b.at + 7) & ~(uint64_t)7;
+            if (!b.has(32)) return false;
+            const uint32_t len = b.value(16), nlen = b.value(16);
+            if (len != 0 || nlen != 0xFFFFu) return false;
+            prev_fixed = false;
+            continue;
+        }
+        if (btype != 1 || ++blocks > GCI_DGZ_MAX_BLOCKS) return false;
+        std::string line;                        // the characters literals have spelled of a line not yet closed
+        bool spelling = false;
+        uint32_t w = 0, run_val = 0, run_lines = 0, partial = 0;   // partial: bytes matches have copied of a line not yet whole
+        for (;;) {
+            if (!b.has(20)) return false;
+            // the fixed code, RFC 1951 3.2.6: 7 bits 0000000 .. 0010111 = 256 .. 279, 8 bits 00110000 .. 10111111 = 0 .. 143,
+            // 8 bits 11000000 .. 11000111 = 280 .. 287, 9 bits = 144 .. 255
+            uint32_t c = b.code(7), sym;
+            if (c <= 0x17u) sym = 256 + c;
+            else {
+                c = (c << 1) | b.bit();
+                if (c >= 0x30u && c <= 0xBFu) sym = c - 0x30u;
+                else if (c >= 0xC0u && c <= 0xC7u) sym = 280 + (c - 0xC0u);
+                else return false;               // a literal of 144 or more
+            }
+            if (sym == 256) break;
+            if (sym < 256) {
+                if (partial) return false;
+                if (!spelling) {
+                    if (w && !on_run(run_val, run_lines)) return false;
+                    w = 0; spelling = true; line.clear();
+                }
+                if (sym == '\n') {
+                    if (line.empty() || line.size() > 10 || (line.size() > 1 && line[0] == '0')) return false;
+                    const unsigned long long v = strtoull(line.c_str(), nullptr, 10);
+                    if (v > 0x7FFFFFFFull || lines == GCI_DGZ_MAX_LINES) return false;
+                    w = (uint32_t)line.size() + 1; run_val = (uint32_t)v; run_lines = 1; lines++;
+                    spelling = false;
+                } else if (sym >= '0' && sym <= '9') {
+                    if (line.size() == 10 || (line.size() == 1 && line[0] == '0')) return false;
+                    line.push_back((char)sym);
+                } else return false;
+                continue;
+            }
+            if (sym > 285) return false;
+            const uint32_t len = DGZ_LEN_BASE[sym - 257] + b.value(DGZ_LEN_EXTRA[sym - 257]);
+            const uint32_t dc = b.code(5);
+            if (dc >= 8) return false;
+            const uint32_t dist = DGZ_DIST_BASE[dc] + b.value(DGZ_DIST_EXTRA[dc]);
+            if (spelling || w == 0 || dist != w) return false;
+            partial += len;
+            const uint32_t whole = partial / w;
+            partial %= w;
+            if (whole > GCI_DGZ_MAX_LINES - lines) return false;
+            run_lines += whole; lines += whole;
+        }
+        if (spelling || partial) return false;
+        if (w && !on_run(run_val, run_lines)) return false;
+        prev_fixed = true;
+        if (bfinal) break;
+    }
+    const uint64_t q = (b.at + 7) >> 3;
+    if (q > n || n - q < 8) return false;
+    auto le32 = [&](uint64_t o) { return (uint32_t)raw[o] | (uint32_t)raw[o + 1] << 8 | (uint32_t)raw[o + 2] << 16 | (uint32_t)raw[o + 3] << 24; };
+    out.crc_file = le32(q);
+    out.isize_file = le32(q + 4);
+    out.end = q + 8;
+    out.lines = lines;
+    return true;
+}
+}  // namespace
+
+extern "C" {
+
+int gci_depth_gz_scan(gci_ctx* ctx, const uint8_t* raw, uint64_t n_raw, const uint64_t* cand_pos, uint32_t n_cand, gci_dgz_info* info)
+{
+    if (!ctx || (n_cand && (!raw || !cand_pos || !info))) return GCI_E_INVALID;
+    const uint32_t* T = crc_table();
+    parallel_blocks(ctx->threads, n_cand, 1, [&](uint64_t i, uint64_t) {
+        uint32_t reg = 0xFFFFFFFFu, text_len = 0, runs = 0;
+        DgzMember mem;
+        const bool ok = dgz_decode(raw, n_raw, cand_pos[i], [&](uint32_t v, uint32_t n) {
+            char line[16];
+            const int w = snprintf(line, sizeof line, "%u\n", v);
+            for (uint32_t r = 0; r < n; r++)
+                for (int k = 0; k < w; k++) reg = T[(reg ^ (uint8_t)line[k]) & 0xFFu] ^ (reg >> 8);
+            text_len += n * (uint32_t)w;
+            runs++;
+            return true;
+        }, mem);
+        gci_dgz_info o;
+        memset(&o, 0, sizeof o);
+        o.status = ok ? GCI_DGZ_OK : GCI_DGZ_FOREIGN;
+        if (ok) {
+            o.end = mem.end; o.lines = mem.lines; o.runs = runs;
+            o.crc_ok = (reg ^ 0xFFFFFFFFu) == mem.crc_file;
+            o.isize_ok = text_len == mem.isize_file;
+        }
+        info[i] = o;
+    });
+    return GCI_OK;
+}
+
+int gci_depth_gz_runs(gci_ctx* ctx, const uint8_t* raw, uint64_t n_raw, const gci_dgz_member* members, uint32_t n_members, gci_dgz_run* runs)
+{
+    if (!ctx || (n_members && (!raw || !members || !runs))) return GCI_E_INVALID;
+    parallel_blocks(ctx->threads, n_members, 1, [&](uint64_t m, uint64_t) {
+        uint32_t r = 0;
+        DgzMember mem;
+        (void)dgz_decode(raw, n_raw, members[m].pos, [&](uint32_t v, uint32_t n) {
+            if (r >= members[m].runs) return false;
+            runs[members[m].run0 + r].depth = (int32_t)v;
+            runs[members[m].run0 + r].count = n;
+            r++;
+            return true;
+        }, mem);
+    });
+    return GCI_OK;
+}
+
+int gci_depth_gz_expand(gci_ctx* ctx, const gci_dgz_run* runs, const gci_dgz_member* members, uint32_t n_members, int32_t* track,
+                        uint64_t track_n)
+{
+    if (!ctx || (n_members && (!runs || !members || !track))) return GCI_E_INVALID;
+    parallel_blocks(ctx->threads, n_members, 1, [&](uint64_t m, uint64_t) {
+        uint64_t k = 0;                          // lines of the member written so far
+        for (uint32_t r = 0; r < members[m].runs && k < members[m].lines; r++) {
+            const gci_dgz_run& run = runs[members[m].run0 + r];
+            for (uint32_t j = 0; j < run.count && k < members[m].lines; j++, k++)
+                if (members[m].elem0 + k < track_n) track[members[m].elem0 + k] = run.depth;
+        }
+    });
+    return GCI_OK;
+}
+
+}  // extern "C"
+
 /* ---- depth text -> track (k_depth_parse.hip): the same tiles, line ownership, keys and status word, on host threads ------------ */
 namespace {
 constexpr uint64_t PARSE_TILE = 4096;

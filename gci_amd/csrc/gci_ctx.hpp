@@ -73,8 +73,11 @@ struct gci_ctx {
     DevBuf part_a, part_b, part_hist, part_blk;   // partitioned join: entry ping-pong, histograms + segment table, scan totals
     DevBuf route_tab;                       // gci_route_*: per (part, chunk) counts and their scan
     DevBuf deflate_nruns, deflate_runs;     // gci_depth_deflate_*: per tile its constant-depth runs (k_depth_runs)
-    DevBuf deflate_tab;                     // ... the CRC tables of the size pass (k_deflate.hip: host_crc_tab)
+    DevBuf deflate_tab;                     // ... the CRC tables of the size pass and of gci_depth_gz_scan (gci_crc_gf2.hpp: host_crc_tab)
     bool deflate_tab_ready = false;
+    DevBuf dgz_tiles;                       // gci_depth_gz_runs -> _expand: per 4096 lines of a member the run they begin in
+    uint32_t dgz_members = 0;               // ... of the members the last runs call decoded,
+    const void* dgz_key = nullptr;          // ... in this member table
     bool deflate_from_build = false;        // ... the last size call took the lists of the build (build_runs) instead
     uint32_t deflate_members = 0;           // ... of the members the last size call measured,
     const void* deflate_key_depth = nullptr;    // ... over this track

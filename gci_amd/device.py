@@ -924,6 +924,44 @@ class Engine:
                                                 int(segs.shape[0]), self._p(track), int(track.shape[0])), "gci_depth_text_parse")
         return track
 
+    # ---- this project's own .depth.gz to a track without inflating it (k_depth_gz.hip) ------------------------------------
+    def depth_gz_scan(self, d_raw: Buffer, cand_pos: np.ndarray) -> np.ndarray:
+        """gci_depth_gz_scan over the bytes of a .depth.gz in HBM: one lane per candidate member start -> DGZ_INFO_DTYPE on the host
+        (status, end offset, lines, runs, CRC-32 / ISIZE verdicts)."""
+        from .formats.depthfile import DGZ_INFO_DTYPE
+        cand = np.ascontiguousarray(cand_pos, dtype=np.uint64)
+        n = int(cand.shape[0])
+        if n == 0:
+            return np.zeros(0, dtype=DGZ_INFO_DTYPE)
+        d_cand = self.to_device(cand.view(np.int64))
+        d_info = self.T.empty(n * DGZ_INFO_DTYPE.itemsize, self.T.uint8, self.device)
+        self._chk(self.lib.gci_depth_gz_scan(self.ctx, self._p(d_raw), int(d_raw.shape[0]), self._p(d_cand), n, self._p(d_info)),
+                  "gci_depth_gz_scan")
+        return d_info.cpu().numpy().view(DGZ_INFO_DTYPE)
+
+    def depth_gz_runs(self, d_raw: Buffer, members: np.ndarray) -> Tuple[Buffer, Buffer]:
+        """gci_depth_gz_runs: members = DGZ_MEMBER_DTYPE on the host -> (device runs, 8 bytes each, every member's at its run0;
+        the member table on the device, for depth_gz_expand)."""
+        from .formats.depthfile import DGZ_MEMBER_DTYPE, DGZ_RUN_DTYPE
+        members = np.ascontiguousarray(members, dtype=DGZ_MEMBER_DTYPE)
+        d_members = self.to_device(members.view(np.uint8)) if members.shape[0] else None
+        n_runs = int(members["runs"].astype(np.uint64).sum())
+        d_runs = self.T.empty(max(n_runs, 1) * DGZ_RUN_DTYPE.itemsize, self.T.uint8, self.device)
+        self._chk(self.lib.gci_depth_gz_runs(self.ctx, self._p(d_raw), int(d_raw.shape[0]), self._p(d_members), int(members.shape[0]),
+                                             self._p(d_runs)), "gci_depth_gz_runs")
+        return d_runs, d_members
+
+    def depth_gz_expand(self, d_runs: Buffer, d_members: Buffer, n_members: int, track: Buffer) -> Buffer:
+        """gci_depth_gz_expand, right behind depth_gz_runs over the same member table."""
+        self._chk(self.lib.gci_depth_gz_expand(self.ctx, self._p(d_runs), self._p(d_members), int(n_members), self._p(track),
+                                               int(track.shape[0])), "gci_depth_gz_expand")
+        return track
+
+    def depth_gz_track(self, d_raw: Buffer, members: np.ndarray, track: Buffer) -> Buffer:
+        """The members' lines into `track` at each member's elem0: runs, then their expansion."""
+        d_runs, d_members = self.depth_gz_runs(d_raw, members)
+        return self.depth_gz_expand(d_runs, d_members, int(members.shape[0]), track)
+
     def sdepth_index(self, d_text: Buffer, prev_name: bytes = b"", cap: int = 1 << 12) -> Tuple[Buffer, np.ndarray, np.ndarray, int]:
         """gci_sdepth_index + the exclusive scan of its tile counts over `samtools depth` text in HBM -> (device uint64 [n_tiles + 1]
         first line index of every tile, the same on the host, sorted uint64 keys (byte offset << 12 | rank in its tile) of the

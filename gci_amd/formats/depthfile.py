@@ -153,6 +153,103 @@ def parse_depth_lines(lines) -> Dict[str, object]:
     return depths
 
 
+# ---- this project's own .depth.gz read without inflating it: host halves of the compressed-domain read (k_depth_gz.hip) --------------
+
+MEMBER_HEAD = bytes([0x1F, 0x8B, 8, 0, 0, 0, 0, 0, 0, 0xFF])       # the ten bytes a member of k_deflate.hip begins with
+DGZ_OK, DGZ_FOREIGN = 0, 1
+# include/gci_hip.h: gci_dgz_info, gci_dgz_member, gci_dgz_run
+DGZ_INFO_DTYPE = np.dtype([("end", "<u8"), ("status", "<u4"), ("lines", "<u4"), ("runs", "<u4"), ("crc_ok", "<u4"), ("isize_ok", "<u4"),
+                           ("reserved", "<u4")])
+DGZ_MEMBER_DTYPE = np.dtype([("pos", "<u8"), ("run0", "<u8"), ("elem0", "<u8"), ("runs", "<u4"), ("lines", "<u4")])
+DGZ_RUN_DTYPE = np.dtype([("depth", "<i4"), ("count", "<u4")])
+HEADER_MEMBER_MAX = 4096                   # bytes of a '>name\n' member, raw and inflated: anything larger is not one
+
+
+def member_candidates(buf) -> np.ndarray:
+    """Every position of the ten-byte member header in `buf` (bytes / bytearray) -> uint64 array, ascending.  Most are member
+    starts; one inside another member's bits is possible and harmless (member_chain never looks at it)."""
+    out, at = [], buf.find(MEMBER_HEAD)
+    while at >= 0:
+        out.append(at)
+        at = buf.find(MEMBER_HEAD, at + 1)
+    return np.asarray(out, dtype=np.uint64)
+
+
+def header_member(view, pos: int):
+    """The gzip member at view[pos:] when it is exactly one header line '>name\\n' whose name is what the reference's
+    `line.decode().strip().split('>')[-1]` yields -> (name, end offset), else None."""
+    d = zlib.decompressobj(31)
+    piece = view[pos:pos + HEADER_MEMBER_MAX]
+    try:
+        text = d.decompress(piece, HEADER_MEMBER_MAX)
+    except zlib.error:
+        return None
+    if not d.eof or len(text) < 3 or text[:1] != b">" or text[-1:] != b"\n" or text.count(b"\n") != 1:
+        return None
+    try:
+        name = text[1:-1].decode("utf-8")
+    except UnicodeDecodeError:
+        return None
+    if name == "" or ">" in name or name != name.strip() or header_name(text) != name:
+        return None
+    return name, pos + len(piece) - len(d.unused_data)
+
+
+def member_chain(buf, cand: np.ndarray, info: np.ndarray):
+    """The file as a chain of members from byte 0.  A position that the device accepted (gci_depth_gz_scan: status OK, CRC-32 and
+    ISIZE matching) is a data member of the contig named last and the chain continues at its end offset; any other position must be
+    a '>name\\n' member, inflated here.  -> (names, lengths, members: DGZ_MEMBER_DTYPE without elem0) or None: the file is not
+    wholly of this kind -- data lines in a host member, NUL padding, a damaged member, a name seen twice, data in front of the first
+    header, a contig without lines -- and the text path, which defines every result and every exception, takes all of it."""
+    view = memoryview(buf)
+    n = len(view)
+    at = {int(p): k for k, p in enumerate(cand.tolist())}
+    names, lengths, rows = [], [], []
+    seen = set()
+    pos = 0
+    while pos < n:
+        k = at.get(pos)
+        if k is not None and int(info["status"][k]) == DGZ_OK:
+            if not (info["crc_ok"][k] and info["isize_ok"][k]) or not names:
+                return None
+            end = int(info["end"][k])
+            if end <= pos or end > n:
+                return None
+            rows.append((pos, int(info["runs"][k]), int(info["lines"][k]), len(names) - 1))
+            lengths[-1] += int(info["lines"][k])
+            pos = end
+            continue
+        got = header_member(view, pos)
+        if got is None or got[0] in seen:
+            return None
+        seen.add(got[0])
+        names.append(got[0])
+        lengths.append(0)
+        pos = got[1]
+    if not names or any(L == 0 for L in lengths):
+        return None
+    members = np.zeros(len(rows), dtype=DGZ_MEMBER_DTYPE)
+    contig = np.zeros(len(rows), dtype=np.int64)
+    if rows:
+        r = np.asarray(rows, dtype=np.int64)
+        members["pos"], members["runs"], members["lines"], contig = r[:, 0], r[:, 1], r[:, 2], r[:, 3]
+        members["run0"] = np.cumsum(r[:, 1]) - r[:, 1]
+    return names, lengths, (members, contig)
+
+
+def place_members(members_contig, offsets) -> np.ndarray:
+    """member_chain's members with elem0 = the track element of each member's first line, for the layout's contig offsets."""
+    members, contig = members_contig
+    members = members.copy()
+    if members.shape[0]:
+        lines = members["lines"].astype(np.int64)
+        before = np.cumsum(lines) - lines                                  # lines of the file in front of the member
+        first = np.full(len(offsets), -1, dtype=np.int64)                  # ... in front of the contig's first member
+        first[contig[::-1]] = before[::-1]
+        members["elem0"] = np.asarray(offsets, dtype=np.int64)[contig] + before - first[contig]
+    return members
+
+
 # ---- `samtools depth` text -> .depth.gz (utility/convert_samtools_depth.py): host halves of the device path (k_sdepth.hip) -----------
 
 SDEPTH_LINE_MAX = 255                      # bytes of a line with its '\n': the bound of the device's grammar (k_sdepth.hip)

@@ -1706,16 +1706,76 @@ def _upload_depths(engine: Engine, depths: Dict[str, np.ndarray]) -> Tuple[Depth
     return DepthTracks(engine, targets_length, engine.to_device(host)), targets_length
 
 
+def depth_read_mode() -> str:
+    """GCI_DEPTH_READ: "members" (the default: this project's own files are read in the compressed domain, every other file as
+    text) or "text" (today's path for every file)."""
+    mode = os.environ.get("GCI_DEPTH_READ", "") or "members"
+    if mode not in ("members", "text"):
+        raise ValueError("GCI_DEPTH_READ=%s: members or text" % mode)
+    return mode
+
+
+def depth_members_plan(engine, path: str, buf, to_engine):
+    """The first half of the compressed-domain read of a `.depth.gz`: every ten-byte member header of `buf`
+    is a candidate, the engine decodes them all side by side (gci_depth_gz_scan over to_engine(buf), the same bytes in the engine's
+    memory -- asked for only once the file begins with a '>name' member and has candidates) and the host follows the chain from
+    byte 0 (depthfile.member_chain).  -> ((names, lengths, members), the bytes in the engine's memory) when the whole file is this
+    project's writer's, else None: the text path takes all of it.  Which one it is goes to the phase log as "depth_read:<path>"."""
+    from .formats import depthfile
+    plan = None
+    if depth_read_mode() == "members" and depthfile.header_member(memoryview(buf), 0) is not None:
+        cand = depthfile.member_candidates(buf)
+        if cand.shape[0]:
+            d_raw = to_engine(buf)
+            chain = depthfile.member_chain(buf, cand, engine.depth_gz_scan(d_raw, cand))
+            plan = None if chain is None else (chain, d_raw)
+    phases.note("depth_read:" + path, "members" if plan is not None else "text")
+    return plan
+
+
+def _read_depth_members(engine: Engine, path: str, buf: bytearray, ref_lengths):
+    """read_depth_tracks for a file of this project's own writer: its bytes to HBM as they are, the members decoded into runs and
+    the runs expanded into the track (k_depth_gz.hip).  No text on the host or the device.  -> None: not such a file."""
+    from .formats import depthfile
+
+    def upload(b):
+        raw = np.frombuffer(b, dtype=np.uint8)
+        return engine.upload_staged(raw) if raw.shape[0] >= (256 << 20) else engine.to_device(raw)
+
+    plan = depth_members_plan(engine, path, buf, upload)
+    if plan is None:
+        return None
+    (names, lengths, members), d_raw = plan
+    targets_length = dict(zip(names, lengths))
+    if ref_lengths is not None and any(t not in ref_lengths for t in targets_length):
+        return None, targets_length
+    if any(L > depthfile.INT32_MAX for L in lengths):
+        sys.exit("ERROR!!! A contig of the depth file is longer than 2^31 - 1 bases, which is not supported")
+    engine.set_layout(lengths)
+    track = engine.T.zeros(max(engine.total, 1), engine.T.int32, engine.device)     # (the padding behind every contig too)
+    engine.depth_gz_track(d_raw, depthfile.place_members(members, engine.offsets), track)
+    return DepthTracks(engine, targets_length, track), targets_length
+
+
 def read_depth_tracks(engine: Engine, path: str, ref_lengths: Optional[Dict[str, int]] = None
                       ) -> Tuple[Optional[DepthTracks], Dict[str, int]]:
-    """parse_depth of the reference's GCI_score.py for a `.depth.gz` file -> (DepthTracks, {contig: length}).  The file is inflated
+    """parse_depth of the reference's GCI_score.py for a `.depth.gz` file -> (DepthTracks, {contig: length}).  A file this project
+    wrote itself is read in the compressed domain (_read_depth_members; GCI_DEPTH_READ=text switches that off).  Any other file is inflated
     on host threads (hostio.GzipText), its text goes to HBM through the staging ring, the device checks the grammar and ranks the
     lines (gci_depth_text_index), the host resolves the header lines into contigs and the device writes the track
     (gci_depth_text_parse).  Text outside the strict grammar, and a file the native inflate refuses, take the reference's own
     statements on the host (rare: hand-made files).  ref_lengths: when a contig of the file is not among them nothing is
     uploaded and the tracks are None (the caller refuses the file)."""
     from .formats import depthfile
-    raw = np.fromfile(path, dtype=np.uint8)
+    with open(path, "rb") as f:
+        buf = bytearray(os.path.getsize(path))
+        f.readinto(buf)
+    with phases.wall("depth_gz_members"):
+        got = _read_depth_members(engine, path, buf, ref_lengths)
+    if got is not None:
+        return got
+    raw = np.frombuffer(buf, dtype=np.uint8)
+    del buf
     try:
         with phases.wall("depth_gz_inflate"):
             gz = hostio.GzipText(raw, hostio.pick_threads(1))

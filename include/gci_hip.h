@@ -456,6 +456,57 @@ int gci_sdepth_index(gci_ctx* ctx, const uint8_t* d_text, uint64_t n_bytes, cons
 int gci_sdepth_parse(gci_ctx* ctx, const uint8_t* d_text, uint64_t n_bytes, const uint64_t* d_tile_line0, uint64_t line_base,
                      const int64_t* d_segs, uint32_t n_segs, int32_t* d_track, uint64_t track_n);
 
+/* ---- this library's own .depth.gz -> track, without inflating it (k_depth_gz.hip) ---------------------------------------------
+ * The counterpart of gci_depth_deflate_*: the members those calls write are decoded straight back into (depth, count) runs, their
+ * CRC-32 and ISIZE checked by the same GF(2) algebra, and the runs expanded into the int32 track.  No text exists anywhere.
+ * The grammar a member must obey (anything else, however legal as gzip, is GCI_DGZ_FOREIGN and the caller's to inflate):
+ *   header   the ten bytes 1f 8b 08 00 00 00 00 00 00 ff
+ *   blocks   fixed-Huffman blocks (at most 65), a stored block only behind a fixed one, empty and never final; the final block fixed
+ *   a block  literals spell one line [0-9]{1,10} '\n' (no leading zero, value <= INT32_MAX) of width w; matches follow with distance
+ *            exactly w; their lengths add up to whole lines before the next literal or the end of the block; at most 262 144 lines
+ *            per member
+ *   trailer  CRC-32 and ISIZE behind the final block, byte aligned
+ * d_raw: the bytes of the file (any alignment, no padding needed: nothing at or beyond d_raw + n_raw is read).
+ *   gci_depth_gz_scan    one lane per candidate member start d_cand_pos[i] (every position of the ten-byte header in the file will
+ *                        do: a false candidate inside another member's bits is refused or, rarely, accepted -- the caller follows
+ *                        the chain of end offsets from byte 0 and never looks at it).  d_info[i]: status; for GCI_DGZ_OK the end
+ *                        offset (behind ISIZE), lines, runs (one per literal line) and whether the trailer's CRC-32 / ISIZE equal
+ *                        those of the text the runs stand for; all zero behind GCI_DGZ_FOREIGN.
+ *   gci_depth_gz_runs    d_members[m]: pos, runs and lines as the scan reported them, run0 = exclusive scan of runs; writes member
+ *                        m's runs to d_runs[run0 ...] and keeps, per 4096 lines of a member, where they begin in its runs.
+ *   gci_depth_gz_expand  the same d_members (elem0 = track element of the member's first line), right behind gci_depth_gz_runs on
+ *                        the same context: line k of member m to d_track[elem0 + k] (16-byte stores where elem0 is a multiple of
+ *                        4); elements at or beyond track_n are not written. */
+enum { GCI_DGZ_OK = 0, GCI_DGZ_FOREIGN = 1 };
+#define GCI_DGZ_MAX_LINES 262144u
+#define GCI_DGZ_MAX_BLOCKS 65u
+typedef struct gci_dgz_info {
+    uint64_t end;
+    uint32_t status;
+    uint32_t lines;
+    uint32_t runs;
+    uint32_t crc_ok;
+    uint32_t isize_ok;
+    uint32_t reserved;
+} gci_dgz_info;
+typedef struct gci_dgz_member {
+    uint64_t pos;
+    uint64_t run0;
+    uint64_t elem0;
+    uint32_t runs;
+    uint32_t lines;
+} gci_dgz_member;
+typedef struct gci_dgz_run {
+    int32_t depth;
+    uint32_t count;
+} gci_dgz_run;
+int gci_depth_gz_scan(gci_ctx* ctx, const uint8_t* d_raw, uint64_t n_raw, const uint64_t* d_cand_pos, uint32_t n_cand,
+                      gci_dgz_info* d_info);
+int gci_depth_gz_runs(gci_ctx* ctx, const uint8_t* d_raw, uint64_t n_raw, const gci_dgz_member* d_members, uint32_t n_members,
+                      gci_dgz_run* d_runs);
+int gci_depth_gz_expand(gci_ctx* ctx, const gci_dgz_run* d_runs, const gci_dgz_member* d_members, uint32_t n_members,
+                        int32_t* d_track, uint64_t track_n);
+
 /* ---- host-side container helpers (no GPU work) ---------------------------------
  * The reference reaches BGZF / BAM through pysam/htslib (GCI.py:150-151) and writes gzip through Python's gzip
  * module (GCI.py:111).  All pointers are HOST pointers.

@@ -5,7 +5,8 @@ Run on one MI355X by tools/measure_score.sh, which adds the rocprofv3 runs.
     python tools/measure_score.py make DIR [SCALE]   CHM13 geometry (every contig x SCALE): ref.fa, three ~40x .depth.gz files of
                                                     this project's writer (hifi, nano, two), one reference-style file (Python's
                                                     gzip, level 9, FNAME, one member per contig) of the hifi track
-    python tools/measure_score.py run DIR OUT        wall time of `GCI_score.py --hifi --nano --two-type -f` under GCI_PHASES and of
+    python tools/measure_score.py run DIR OUT        wall time and peak host RSS of `GCI_score.py --hifi --nano --two-type -f` under
+                                                    GCI_PHASES, with GCI_DEPTH_READ=members and =text in turn, and of
                                                     `GCI_score.py --hifi <reference-style file> -f` -> OUT/score_runs.json
     python tools/measure_score.py summarize DIR OUT  kernel times (rocprofv3 --kernel-trace --stats) and FETCH_SIZE / WRITE_SIZE
                                                     (rocprofv3 --pmc, a run of its own) of the two parse kernels against the bytes
@@ -85,13 +86,16 @@ def make(d: str, scale: float = 1.0) -> None:
     print(json.dumps(info))
 
 
-def _timed(cmd, env=None):
+def _timed(cmd, env=None, log=None):
+    """-> (wall seconds, peak resident set of the child in MB)"""
     t = time.perf_counter()
-    r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True)
-    if r.returncode != 0:
-        sys.stderr.write(r.stdout[-2000:] + r.stderr[-4000:])
-        raise SystemExit("failed: %s" % " ".join(cmd))
-    return round(time.perf_counter() - t, 3)
+    with open(log or os.devnull, "w") as f:
+        p = subprocess.Popen(cmd, cwd=ROOT, env=env, stdout=f, stderr=subprocess.STDOUT)
+        _, status, usage = os.wait4(p.pid, 0)
+        p.returncode = os.waitstatus_to_exitcode(status)
+    if p.returncode != 0:
+        raise SystemExit("failed (%d): %s" % (p.returncode, " ".join(cmd)))
+    return round(time.perf_counter() - t, 3), round(usage.ru_maxrss / 1024.0, 1)
 
 
 def run(d: str, out: str) -> None:
@@ -99,13 +103,22 @@ def run(d: str, out: str) -> None:
     entry = [sys.executable, os.path.join(ROOT, "GCI_score.py"), "-r", os.path.join(d, "ref.fa")]
     three = ["--hifi", os.path.join(d, "hifi.depth.gz"), "--nano", os.path.join(d, "nano.depth.gz"), "--two-type", os.path.join(d, "two.depth.gz")]
     res = {"inputs": json.load(open(os.path.join(d, "inputs.json")))}
-    for k in range(2):
-        ph = os.path.join(out, "score_phases_three_files_run%d.json" % k)
-        res["three_files_wall_s_run%d" % k] = _timed(entry + three + ["-d", os.path.join(d, "out"), "-o", "M", "-f"],
-                                                     env=dict(os.environ, GCI_PHASES=ph))
+    for k in range(2):                                       # the two paths of the read in turn, twice
+        for mode in ("members", "text"):
+            ph = os.path.join(out, "score_phases_three_files_%s_run%d.json" % (mode, k))
+            wall, rss = _timed(entry + three + ["-d", os.path.join(d, "out_" + mode), "-o", "M", "-f"],
+                               env=dict(os.environ, GCI_PHASES=ph, GCI_DEPTH_READ=mode), log=os.path.join(out, "score_%s_run%d.log" % (mode, k)))
+            res["three_files_%s_wall_s_run%d" % (mode, k)], res["three_files_%s_peak_rss_mb_run%d" % (mode, k)] = wall, rss
+            wall_s = json.load(open(ph))["wall_s"]
+            res["three_files_%s_phases_s_run%d" % (mode, k)] = {n: round(v, 4) for n, v in wall_s.items() if n.startswith("depth_")}
+    same = all(open(os.path.join(d, "out_members", fn), "rb").read() == open(os.path.join(d, "out_text", fn), "rb").read()
+               for fn in sorted(os.listdir(os.path.join(d, "out_text"))))
+    res["outputs_of_the_two_paths_identical"] = bool(same and sorted(os.listdir(os.path.join(d, "out_members"))) ==
+                                                     sorted(os.listdir(os.path.join(d, "out_text"))))
     ph = os.path.join(out, "score_phases_reference_style.json")
-    res["reference_style_hifi_wall_s"] = _timed(entry + ["--hifi", os.path.join(d, "refstyle.depth.gz"), "-d", os.path.join(d, "out_ref"),
-                                                         "-o", "R", "-f"], env=dict(os.environ, GCI_PHASES=ph))
+    res["reference_style_hifi_wall_s"], res["reference_style_hifi_peak_rss_mb"] = _timed(
+        entry + ["--hifi", os.path.join(d, "refstyle.depth.gz"), "-d", os.path.join(d, "out_ref"), "-o", "R", "-f"],
+        env=dict(os.environ, GCI_PHASES=ph))
     with open(os.path.join(out, "score_runs.json"), "w") as f:
         json.dump(res, f, indent=1)
     print(json.dumps(res))
@@ -137,6 +150,17 @@ def summarize(d: str, out: str) -> None:
                                                                 need[k] / s / 1e12, need[k] / s / HBM_PEAK))
     if tot_s:
         lines.append("both passes: %.3f of the 8 TB/s peak (bytes they must move over their kernel time)" % (tot_b / tot_s / HBM_PEAK))
+    # the compressed-domain read (k_depth_gz.hip): raw bytes in, 8 B per run, 4 B per base out
+    for path in stats:
+        for r in csv.DictReader(open(path)):
+            if "k_dgz_" in r["Name"]:
+                name = r["Name"][r["Name"].index("k_dgz_"):].split("(")[0]
+                lines.append("%s: %d calls, %.3f ms in all, %.3f ms per call" % (name, int(r["Calls"]), float(r["TotalDurationNs"]) * 1e-6,
+                                                                              float(r["TotalDurationNs"]) * 1e-6 / max(int(r["Calls"]), 1)))
+    own = [v for k, v in info["files"].items() if not k.startswith("refstyle")]
+    if own:
+        lines.append("k_dgz_*: bytes they must move per file: %.3f GB raw in (scan and runs each), 8 B per run (not counted here), "
+                     "%.2f GB of track out" % (sum(own) / len(own) / 1e9, 4 * bases / 1e9))
     pmc = {}
     for path in glob.glob(os.path.join(out, "pmc", "**", "*counter_collection.csv"), recursive=True):
         for r in csv.DictReader(open(path)):
