@@ -123,6 +123,7 @@ EXPORTS = [
     ("gci_issue_scan", c_int, [c_void_p, c_void_p, c_double, c_double, c_int, c_void_p, c_uint32, c_void_p]),
     ("gci_issue_scan_windows", c_int, [c_void_p, c_void_p, POINTER(Window), c_uint32, c_double, c_double, c_void_p,
                                        c_uint32, c_void_p]),
+    ("gci_depth_classes", c_int, [c_void_p, c_void_p, POINTER(Window), c_uint32, c_int32, c_void_p, c_uint32, c_void_p, c_void_p]),
     ("gci_depth_text_size", c_int, [c_void_p, c_void_p, c_void_p]),
     ("gci_depth_text_write", c_int, [c_void_p, c_void_p, c_void_p, c_uint64]),
     ("gci_depth_sum", c_int, [c_void_p, c_void_p, c_void_p]),

@@ -65,6 +65,7 @@ EXPORTS = [
     ("gci_max2", c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     ("gci_issue_scan", c_int, [c_void_p, c_void_p, c_double, c_double, c_int, c_void_p, c_uint32, c_void_p]),
     ("gci_issue_scan_windows", c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_double, c_double, c_void_p, c_uint32, c_void_p]),
+    ("gci_depth_classes", c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_int32, c_void_p, c_uint32, c_void_p, c_void_p]),
     ("gci_depth_text_size", c_int, [c_void_p, c_void_p, c_void_p]),
     ("gci_depth_text_write", c_int, [c_void_p, c_void_p, c_void_p, c_uint64]),
     ("gci_depth_sum", c_int, [c_void_p, c_void_p, c_void_p]),
@@ -228,19 +229,27 @@ class CpuEngine:
         return out
 
     # ---- R10
-    def issue_keys(self, track: np.ndarray, lo: float, hi: float, flank: int, windows: Optional[Sequence[Tuple[int, int]]] = None) -> np.ndarray:
+    @staticmethod
+    def _scan_keys(call, n_arrays: int = 1) -> List[np.ndarray]:
+        """call(keys, cap, counters) until every key fitted (n_arrays key arrays of `cap` keys back to back, one counter each), the
+        buffer grown to what the counters ask for -> the sorted keys of every array."""
         cap = 1 << 12
         while True:
-            keys = np.zeros(cap, dtype=np.uint64)
-            n = np.zeros(1, dtype=np.uint32)
+            keys = np.zeros(n_arrays * cap, dtype=np.uint64)
+            n = np.zeros(n_arrays, dtype=np.uint32)
+            call(keys, cap, n)
+            if int(n.max()) <= cap:
+                return [np.sort(keys[x * cap:x * cap + int(n[x])]) for x in range(n_arrays)]
+            cap = int(n.max())
+
+    def issue_keys(self, track: np.ndarray, lo: float, hi: float, flank: int, windows: Optional[Sequence[Tuple[int, int]]] = None) -> np.ndarray:
+        def call(keys, cap, n):
             if windows is None:
                 self._chk(self.lib.gci_issue_scan(self.ctx, _p(track), lo, hi, flank, _p(keys), cap, _p(n)), "gci_issue_scan")
             else:
                 w = (_Window * len(windows))(*[_Window(int(a), int(b)) for a, b in windows])
                 self._chk(self.lib.gci_issue_scan_windows(self.ctx, _p(track), w, len(windows), lo, hi, _p(keys), cap, _p(n)), "gci_issue_scan_windows")
-            if int(n[0]) <= cap:
-                return np.sort(keys[:int(n[0])])
-            cap = int(n[0])
+        return self._scan_keys(call)[0]
 
     def issue_runs(self, track: np.ndarray, lo: float, hi: float, flank: int, n_windows: Optional[int] = None,
                    windows: Optional[Sequence[Tuple[int, int]]] = None) -> List[List[Tuple[int, int]]]:
@@ -253,6 +262,26 @@ class CpuEngine:
             assert (a >> 33) == (b >> 33) and not (a & 1) and (b & 1)
             runs[a >> 33].append(((a >> 1) & 0xFFFFFFFF, (b >> 1) & 0xFFFFFFFF))
         return runs
+
+    def depth_classes(self, track: np.ndarray, windows: Sequence[Tuple[int, int]], low_below: int = 5
+                      ) -> Tuple[List[np.ndarray], List[np.ndarray], np.ndarray]:
+        """gci_depth_classes (device.Engine.depth_classes' twin): per window the runs of depth 0 and of 0 < depth < low_below as int64
+        [k, 2] of (start, exclusive end) relative to the window's beginning, and int64 [n, 2] of (sum, count) of the depths > 0."""
+        nw = len(windows)
+        w = (_Window * max(nw, 1))(*[_Window(int(a), int(b)) for a, b in windows])
+        stats = np.zeros((nw, 2), dtype=np.int64)
+
+        def call(keys, cap, n):
+            self._chk(self.lib.gci_depth_classes(self.ctx, _p(track), w, nw, int(low_below), _p(keys), cap, _p(n), _p(stats)), "gci_depth_classes")
+        out = []
+        for k in self._scan_keys(call, 2):
+            if (k.shape[0] & 1) or (k[0::2] & np.uint64(1)).any() or not (k[1::2] & np.uint64(1)).all():
+                raise CpuError(-1, "gci_depth_classes produced unpaired run boundaries")
+            win = (k >> np.uint64(33)).astype(np.int64)
+            rel = ((k >> np.uint64(1)) & np.uint64(0xFFFFFFFF)).astype(np.int64)
+            bounds = np.searchsorted(win, np.arange(nw + 1))
+            out.append([np.stack([rel[a:b:2], rel[a + 1:b:2]], axis=1) for a, b in zip(bounds[:-1], bounds[1:])])
+        return out[0], out[1], stats
 
     # ---- R7, R15
     def depth_text(self, track: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:

@@ -3,7 +3,7 @@
 //
 // Same signatures, same structs, same status words as libgci_hip.so for the seam set
 //   gci_bam_filter   gci_name_join   gci_depth_build   gci_gap_mask   gci_max2   gci_issue_scan(_windows)
-//   gci_depth_text_size / _write   gci_depth_sum   gci_range_sums
+//   gci_depth_text_size / _write   gci_depth_sum   gci_range_sums   gci_depth_classes
 // and the context / layout / memory calls around them.  "d_" pointers are host pointers here (gci_malloc is an aligned
 // malloc, gci_memcpy_* a memcpy, gci_sync a no-op): a host written against the header runs on either library.  What a GPU
 // makes worthwhile -- record pages, the partitioned join, the tile build with its fused by-products, the BGZF / DEFLATE
@@ -531,6 +531,53 @@ int gci_issue_scan(gci_ctx* ctx, const int32_t* depth, double lo, double hi, int
         win[(size_t)c] = L > 2 * (int64_t)flank ? gci_window{base + flank, base + L - flank} : gci_window{base, base};
     }
     return issue_scan(ctx, depth, win.data(), (uint32_t)win.size(), lo, hi, keys, cap, n_keys);
+}
+
+/* ---- depth_plotter_v2.py: zero runs, low runs and the non-zero statistics of every window (k_depth_classes' twin) ------------------- */
+int gci_depth_classes(gci_ctx* ctx, const int32_t* depth, const gci_window* h_windows, uint32_t n_windows, int32_t low_below, uint64_t* keys,
+                      uint32_t cap, uint32_t* n_keys, int64_t* stats)
+{
+    if (!ctx || !depth || !n_keys || (cap && !keys) || (n_windows && (!h_windows || !stats))) return GCI_E_INVALID;
+    const int st = need_layout(ctx);
+    if (st) return st;
+    if (n_windows >= (1u << 31)) return GCI_E_INVALID;
+    std::atomic<uint32_t> n[2];
+    n[0] = 0; n[1] = 0;
+    std::vector<std::atomic<int64_t>> acc((size_t)n_windows * 2);
+    for (auto& a : acc) a = 0;
+    // the windows clamped to the track, as the device's set_windows does; then in pieces of 4 M elements, as issue_scan
+    struct Piece { uint32_t w; int64_t begin, end, lo, hi; };
+    std::vector<Piece> pieces;
+    for (uint32_t w = 0; w < n_windows; w++) {
+        int64_t b = std::max<int64_t>(h_windows[w].begin, 0), e = std::min<int64_t>(h_windows[w].end, ctx->total);
+        if (e < b) e = b;
+        for (int64_t a = b; a < e; a += (int64_t)1 << 22) pieces.push_back({w, b, e, a, std::min(e, a + ((int64_t)1 << 22))});
+    }
+    auto cls = [&](int64_t i) { const int32_t d = depth[i]; return d == 0 ? 0 : (d > 0 && d < low_below) ? 1 : 2; };
+    parallel_blocks(ctx->threads, pieces.size(), 1, [&](uint64_t a, uint64_t) {
+        const Piece pc = pieces[a];
+        auto emit = [&](int x, bool is_end, int64_t at) {
+            const uint32_t k = n[x].fetch_add(1);
+            if (k < cap) keys[(size_t)x * cap + k] = ((uint64_t)pc.w << 33) | ((uint64_t)(at - pc.begin) << 1) | (is_end ? 1u : 0u);
+        };
+        int in = pc.lo > pc.begin ? cls(pc.lo - 1) : 2;
+        int64_t sum = 0, cnt = 0;
+        for (int64_t i = pc.lo; i < pc.hi; i++) {
+            const int now = cls(i);
+            if (now != in) {
+                if (in < 2) emit(in, true, i);
+                if (now < 2) emit(now, false, i);
+                in = now;
+            }
+            if (depth[i] > 0) { sum += depth[i]; cnt++; }
+        }
+        if (in < 2 && pc.hi == pc.end) emit(in, true, pc.end);
+        acc[(size_t)pc.w * 2] += sum;
+        acc[(size_t)pc.w * 2 + 1] += cnt;
+    });
+    n_keys[0] = n[0].load(); n_keys[1] = n[1].load();
+    for (size_t i = 0; i < acc.size(); i++) stats[i] = acc[i].load();
+    return GCI_OK;
 }
 
 /* ---- R7: f'{depth}\n' per base (GCI.py:115-117), contig after contig, without the '>' lines --------------------------------------- */

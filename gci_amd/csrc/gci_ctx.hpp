@@ -103,6 +103,7 @@ struct gci_ctx {
     hipStream_t inflate_stream2 = nullptr;  // k_inflate_wave.hip: every other batch of members on a stream of its own (made on first use)
     hipEvent_t inflate_ev_in = nullptr, inflate_ev_out = nullptr;   // k_inflate_wave.hip: a batch's symbol streams, per member its symbols and how it fared
     DevBuf tail_sums;                       // gci_two_type_tail: per-tile sums of the three tracks
+    DevBuf class_sums;                      // gci_depth_classes: per-tile (sum, count) of the depths > 0
     DevBuf tail_gaps;                       // gci_two_type_tail: the N runs as absolute sorted [begin, end) element ranges
     std::vector<int64_t> tail_gaps_host;    // ... what was uploaded last
     // issue-scan windows

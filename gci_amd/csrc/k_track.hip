@@ -1,7 +1,7 @@
 // k_track.hip -- kernels over an existing depth track: K6 gap mask, K7 two-type max, per-contig sums,
-// K8 issue scan, K10 decimal text.  These serve the seams that run on a track AFTER it was built
-// (masked, merged or uploaded tracks); a fresh build gets the same results fused into
-// k_tile_build (k_depth.hip) without re-reading the track.
+// K8 issue scan (and its two-class form for depth_plotter_v2.py, k_depth_classes), K10 decimal text.
+// These serve the seams that run on a track AFTER it was built (masked, merged or uploaded tracks);
+// a fresh build gets the same results fused into k_tile_build (k_depth.hip) without re-reading the track.
 #include "gci_ctx.hpp"
 #include <stdlib.h>
 #include <algorithm>
@@ -221,6 +221,115 @@ extern "C" int gci_issue_scan(gci_ctx* ctx, const int32_t* d_depth, double lo, d
         ctx->win_flank = flank;
     }
     return issue_scan_launch(ctx, d_depth, ctx->win_n, ctx->win_tiles, lo, hi, d_keys, cap, d_n_keys);
+}
+
+// ============================================================================================
+// depth_plotter_v2.py: the zero runs, the low runs and the non-zero statistics of a set of windows in ONE pass
+// ============================================================================================
+//
+// K8's tiling, windows and predecessor read, with the boundary test generalised from one predicate to a class id per base:
+// 0 = (d == 0), 1 = (0 < d < low), 2 = neither or outside the window.  A boundary of class x sits at p when (cls[p] == x) differs
+// from (cls[p-1] == x); each class has its own key array and counter, K8's key format and closing rule.  The same read gives the
+// sum and the number of the bases with d > 0: summed per thread, per wave, per workgroup, one (sum, count) table entry per tile
+// (k_reduce_class_stats folds the tiles of a window, as k_reduce_tiles does for gci_depth_sum's contigs).
+__device__ __forceinline__ int depth_class(int32_t d, int32_t low) { return d == 0 ? 0 : (d > 0 && d < low) ? 1 : 2; }
+
+__global__ __launch_bounds__(BLOCK) void k_depth_classes(const int32_t* __restrict__ depth, const gci_window* __restrict__ win,
+                                                         const int64_t* __restrict__ win_tile_first, int32_t n_win, int32_t low,
+                                                         unsigned long long* __restrict__ keys, uint32_t cap,
+                                                         uint32_t* __restrict__ n_keys, long long* __restrict__ tile_stats)
+{
+    __shared__ long long part[2][BLOCK / 64];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int32_t w = contig_of_tile(win_tile_first, n_win, blockIdx.x);
+    const gci_window W = win[w];
+    const int64_t p0 = (W.begin / TILE + ((int64_t)blockIdx.x - win_tile_first[w])) * TILE;
+    long long sum = 0, cnt = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const int64_t p = p0 + (int64_t)(j * BLOCK + t) * 4;
+        const int4 v = *reinterpret_cast<const int4*>(depth + p);
+        const int32_t d[4] = {v.x, v.y, v.z, v.w};
+        int cls[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const bool in = (p + k >= W.begin) && (p + k < W.end);
+            cls[k] = in ? depth_class(d[k], low) : 2;
+            if (in && d[k] > 0) { sum += d[k]; cnt++; }
+        }
+        int cp = __shfl_up(cls[3], 1, 64);
+        if (lane == 0) cp = (p - 1 >= W.begin && p - 1 < W.end) ? depth_class(depth[p - 1], low) : 2;
+        if ((cls[0] & cls[1] & cls[2] & cls[3] & cp) == 2) continue;                  // (2 = 0b10: no base of class 0 or 1 here)
+#pragma unroll
+        for (int x = 0; x < 2; x++) {
+            unsigned long long* kx = keys + (size_t)x * cap;
+            bool prev = cp == x;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int64_t q = p + k;
+                const bool g = cls[k] == x;
+                if (g != prev && q >= W.begin && (g || q < W.end)) {
+                    const uint32_t s = atomicAdd(n_keys + x, 1u);
+                    if (s < cap) kx[s] = issue_key((uint32_t)w, q - W.begin, !g);
+                }
+                if (g && q == W.end - 1) {
+                    const uint32_t s = atomicAdd(n_keys + x, 1u);
+                    if (s < cap) kx[s] = issue_key((uint32_t)w, W.end - W.begin, true);
+                }
+                prev = g;
+            }
+        }
+    }
+    sum = wave_sum<long long>(sum);
+    cnt = wave_sum<long long>(cnt);
+    if (lane == 0) { part[0][wave] = sum; part[1][wave] = cnt; }
+    __syncthreads();
+    if (t < 2) tile_stats[2 * (int64_t)blockIdx.x + t] = part[t][0] + part[t][1] + part[t][2] + part[t][3];      // (sum, count) per tile
+}
+
+// k_reduce_tiles for the (sum, count) pairs: REDUCE_SPLIT workgroups per window, each adds its share of the window's tiles to
+// stats[2 w] and stats[2 w + 1] with one 64-bit atomic per statistic (stats must be zeroed first)
+__global__ __launch_bounds__(BLOCK) void k_reduce_class_stats(const long long* __restrict__ tile_stats,
+                                                              const int64_t* __restrict__ win_tile_first,
+                                                              unsigned long long* __restrict__ stats)
+{
+    __shared__ long long part[2][BLOCK / 64];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int64_t a = win_tile_first[blockIdx.x], b = win_tile_first[blockIdx.x + 1];
+    long long s = 0, c = 0;
+    for (int64_t i = a + (int64_t)blockIdx.y * BLOCK + t; i < b; i += (int64_t)REDUCE_SPLIT * BLOCK) { s += tile_stats[2 * i]; c += tile_stats[2 * i + 1]; }
+    s = wave_sum<long long>(s);
+    c = wave_sum<long long>(c);
+    if (lane == 0) { part[0][wave] = s; part[1][wave] = c; }
+    __syncthreads();
+    if (t < 2) {
+        const long long v = part[t][0] + part[t][1] + part[t][2] + part[t][3];
+        if (v) atomicAdd(stats + 2 * (size_t)blockIdx.x + t, (unsigned long long)v);
+    }
+}
+
+extern "C" int gci_depth_classes(gci_ctx* ctx, const int32_t* d_depth, const gci_window* h_windows, uint32_t n_windows, int32_t low_below,
+                                 uint64_t* d_keys, uint32_t cap, uint32_t* d_n_keys, int64_t* d_stats)
+{
+    if (!ctx || !d_depth || !d_n_keys || (cap && !d_keys) || (n_windows && (!h_windows || !d_stats))) return GCI_E_INVALID;
+    if (!ctx->n_contigs) return GCI_E_NO_LAYOUT;
+    if (n_windows >= (1u << 31)) return GCI_E_INVALID;
+    GCI_TRY(set_windows(ctx, h_windows, n_windows));
+    ctx->win_flank = INT32_MIN;
+    HIPCHK(hipMemsetAsync(d_n_keys, 0, 8, ctx->stream));
+    if (n_windows) HIPCHK(hipMemsetAsync(d_stats, 0, (size_t)n_windows * 16, ctx->stream));
+    const int64_t nt = ctx->win_tiles;
+    if (nt == 0) return GCI_OK;
+    if (nt > 0x7FFFFFFFll) return GCI_E_INVALID;
+    GCI_TRY(gci_ensure(ctx, ctx->class_sums, (size_t)2 * nt * 8));                    // (sum, count) per tile
+    hipLaunchKernelGGL(k_depth_classes, dim3((uint32_t)nt), dim3(BLOCK), 0, ctx->stream, d_depth, (const gci_window*)ctx->win.p,
+                       (const int64_t*)ctx->win_tile_first.p, (int32_t)n_windows, low_below, (unsigned long long*)d_keys, cap, d_n_keys,
+                       (long long*)ctx->class_sums.p);
+    LAUNCHCHK("k_depth_classes");
+    hipLaunchKernelGGL(k_reduce_class_stats, dim3(n_windows, REDUCE_SPLIT), dim3(BLOCK), 0, ctx->stream,
+                       (const long long*)ctx->class_sums.p, (const int64_t*)ctx->win_tile_first.p, (unsigned long long*)d_stats);
+    LAUNCHCHK("k_reduce_class_stats");
+    return GCI_OK;
 }
 
 // ============================================================================================

@@ -1024,15 +1024,21 @@ class Engine:
             out.append(np.stack([r[0::2], r[1::2]], axis=1) if b > a else np.zeros((0, 2), dtype=np.int64))
         return out
 
-    def _scan(self, call, n_windows: int) -> List[np.ndarray]:
+    def _scan(self, call, n_windows: int, counts: Optional[Buffer] = None):
+        """call(keys, cap) until every key fitted, the buffer grown to what the counters ask for.  counts: the call's counters when it
+        fills several key arrays of `cap` keys each, back to back (one counter per array) -> the runs per array; None: one array,
+        counted in self._count -> its runs."""
+        n_arrays = 1 if counts is None else int(counts.shape[0])
         cap = 1 << 16
         while True:
-            keys = self.T.empty(cap, self.T.int64, self.device)
+            keys = self.T.empty(n_arrays * cap, self.T.int64, self.device)
             call(keys, cap)
-            n = int(self._count.item())
-            if n <= cap:
-                return self._keys_to_runs(keys[:n].cpu().numpy().view(np.uint64), n_windows)
-            cap = n
+            n = (self._count if counts is None else counts).cpu().numpy().view(np.uint32)
+            if int(n.max()) <= cap:
+                break
+            cap = int(n.max())
+        runs = [self._keys_to_runs(keys[x * cap:x * cap + int(n[x])].cpu().numpy().view(np.uint64), n_windows) for x in range(n_arrays)]
+        return runs[0] if counts is None else runs
 
     def issue_scan(self, track: Buffer, lo: float, hi: float, flank: int) -> List[np.ndarray]:
         """Raw maximal runs of lo < depth <= hi inside [flank, L - flank) of every contig, as
@@ -1053,6 +1059,24 @@ class Engine:
                                                       self._p(keys), cap, self._p(self._count)),
                       "gci_issue_scan_windows")
         return self._scan(call, len(windows))
+
+    def depth_classes(self, track: Buffer, windows: Sequence[Tuple[int, int]], low_below: int = 5
+                      ) -> Tuple[List[np.ndarray], List[np.ndarray], np.ndarray]:
+        """gci_depth_classes over [begin, end) windows of track elements: per window the runs of depth 0 and the runs of
+        0 < depth < low_below, each int64 [k, 2] of (start, exclusive end) relative to the window's beginning, and int64 [n, 2] of
+        (sum, count) of the depths > 0 -- one read of the windows (depth_plotter_v2.py)."""
+        nw = len(windows)
+        arr = (Window * max(nw, 1))()
+        for i, (a, b) in enumerate(windows):
+            arr[i].begin, arr[i].end = int(a), int(b)
+        stats = self.T.zeros(max(2 * nw, 1), self.T.int64, self.device)
+        counts = self.T.zeros(2, self.T.int32, self.device)
+
+        def call(keys, cap):
+            self._chk(self.lib.gci_depth_classes(self.ctx, self._p(track), arr, nw, int(low_below), self._p(keys), cap,
+                                                 self._p(counts), self._p(stats)), "gci_depth_classes")
+        zero, low = self._scan(call, nw, counts)
+        return zero, low, stats.cpu().numpy()[:2 * nw].reshape(nw, 2)
 
     # ---- R7 ----------------------------------------------------------------------------------
     def depth_text(self, track: Buffer, out: Optional[Buffer] = None) -> Tuple[Buffer, np.ndarray]:

@@ -103,11 +103,18 @@ def _line_at(text: np.ndarray, at: int) -> bytes:
         k *= 4
 
 
-def header_segments(text: np.ndarray, keys: np.ndarray, tile_line0: np.ndarray):
+def header_name_v2(line: bytes) -> str:
+    """The sequence a header line names for utility/depth_plotter_v2.py: everything behind the '>' of the stripped line."""
+    return line.decode("utf-8").strip()[1:]
+
+
+def header_segments(text: np.ndarray, keys: np.ndarray, tile_line0: np.ndarray, plotter_v2: bool = False):
     """The header lines of a text found by gci_depth_text_index -> (names in first-appearance order, their lengths, a callback
     segs(offsets) -> int64 [n_headers, 3] (first data line, data lines, track element of the first or -1)), or None when the text
     does not begin with a header line (the reference then raises: the slow path reproduces that).  A name that appears again
-    restarts its contig: its last segment wins and it keeps its first place (parse_depth's dict)."""
+    restarts its contig: its last segment wins and it keeps its first place (parse_depth's dict).
+    plotter_v2: the names by depth_plotter_v2.py's expression, and None also for a name that appears again (that utility draws a
+    sequence once per header: the lock-step read below takes such a file)."""
     total_lines = int(tile_line0[-1])
     if keys.shape[0] == 0:
         return None
@@ -116,9 +123,12 @@ def header_segments(text: np.ndarray, keys: np.ndarray, tile_line0: np.ndarray):
     line = tile_line0[off >> 12].astype(np.int64) + (keys & np.uint64(0xFFF)).astype(np.int64)
     if int(line[0]) != 0:
         return None
-    names = [header_name(_line_at(text, int(o))) for o in off.tolist()]
+    name_of = header_name_v2 if plotter_v2 else header_name
+    names = [name_of(_line_at(text, int(o))) for o in off.tolist()]
     if any(nm == "" for nm in names):
         return None                        # (a header naming '' is kept apart by parse_depth's `target != ''`: the slow path)
+    if plotter_v2 and len(set(names)) != len(names):
+        return None
     n_data = np.diff(np.concatenate([line, [total_lines]])) - 1
     last = {nm: k for k, nm in enumerate(names)}
     order = list(dict.fromkeys(names))
@@ -151,6 +161,86 @@ def parse_depth_lines(lines) -> Dict[str, object]:
             depths[target].append(int(item))
     depths[target] = np.array(depths[target])
     return depths
+
+
+# ---- utility/depth_plotter_v2.py: its reader steps through the HiFi and the ONT file one line of each at a time ---------------------
+
+def open_depth_lines(path: str):
+    """A depth file as text lines, as depth_plotter_v2.py opens it: gzip only when the name ends in `.gz`."""
+    return gzip.open(path, "rt") if path.endswith(".gz") else open(path, "rt")
+
+
+def lockstep_sequences(hifi_lines, ont_lines, wanted, n_targets: int, say=print):
+    """The sequences depth_plotter_v2.py's SynchronizedDepthReader yields, for ANY pair of files (either may be None): the slow path of
+    depth_plotter_v2 for files the device path does not take -- text outside the strict grammar, names that repeat, two files whose
+    headers do not line up.  One line of each file per step; what follows from that is kept:
+      * a header line in either file closes the sequence read so far and opens the next one, named by the HiFi header when both
+        lines are headers; the other file's data line of that step is dropped;
+      * a header that names nothing ('>') opens nothing, and is no data either;
+      * a data line that is no integer counts as 0;
+      * the file that ends first ends the read (a line already taken from the HiFi file in that step is dropped);
+      * a sequence is yielded when wanted(name), once; when n_targets of them were yielded the read stops.
+    -> (name, HiFi depths, ONT depths) as lists of int; the reader's transcript goes through say()."""
+    def number(word: str) -> int:
+        try:
+            return int(word)
+        except ValueError:
+            return 0
+
+    if hifi_lines is not None and ont_lines is not None:
+        steps = zip(hifi_lines, ont_lines)
+    elif hifi_lines is not None:
+        steps = ((line, None) for line in hifi_lines)
+    else:
+        steps = ((None, line) for line in (ont_lines if ont_lines is not None else ()))
+    done = set()
+    name, hifi, ont = None, [], []
+    try:
+        for pair in steps:
+            words = [None if line is None else line.strip() for line in pair]
+            heads = [None if w is None or not w.startswith(">") else w[1:] for w in words]
+            opened = heads[0] or heads[1]
+            if not opened:
+                for w, h, depths in zip(words, heads, (hifi, ont)):
+                    if w is not None and h is None:
+                        depths.append(number(w))
+                continue
+            if name and wanted(name):
+                done.add(name)
+                say(f"Processing sequence: {name}, remaining target sequences: {n_targets - len(done)}")
+                yield name, hifi, ont
+                if n_targets and len(done) >= n_targets:
+                    say("All target sequences have been processed, stopping reading")
+                    break
+            name, hifi, ont = opened, [], []
+        if name and wanted(name) and name not in done:
+            done.add(name)
+            say(f"Processing last sequence: {name}")
+            yield name, hifi, ont
+    finally:
+        say(f"File reading ended, processed {len(done)} sequences in total")
+
+
+def conforming_sequences(names, wanted, n_targets: int, say=print):
+    """lockstep_sequences for files whose headers line up (one file, or two with the same names and lengths in the same order, every
+    name once and none empty): which of `names` are yielded, and the same transcript, from the header sequence alone."""
+    done = 0
+    try:
+        for k, name in enumerate(names):
+            if not wanted(name):
+                continue
+            done += 1
+            if k + 1 == len(names):
+                say(f"Processing last sequence: {name}")
+                yield name
+                return
+            say(f"Processing sequence: {name}, remaining target sequences: {n_targets - done}")
+            yield name
+            if n_targets and done >= n_targets:
+                say("All target sequences have been processed, stopping reading")
+                return
+    finally:
+        say(f"File reading ended, processed {done} sequences in total")
 
 
 # ---- this project's own .depth.gz read without inflating it: host halves of the compressed-domain read (k_depth_gz.hip) --------------

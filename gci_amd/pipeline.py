@@ -1616,6 +1616,51 @@ def sliding_window_average_depth(depths: DepthTracks, target: str, window_size=5
     return pos, val
 
 
+def depth_profile_v2(tracks: DepthTracks, items: Sequence[Tuple[str, int, int]], window_size: int, low_below: int = 5):
+    """What utility/depth_plotter_v2.py computes from depths[target][start:end + 1] for every (target, start, end INCLUSIVE) of
+    `items` (0 <= start <= end < length), over a track in HBM, in TWO device calls for all of them: ONE gci_depth_classes (the zero
+    runs, the low runs, the sum and the number of the bases with depth > 0) and ONE gci_range_sums (the window sums).  Per item a
+    dict, positions relative to `start`:
+        zero, low   int64 [k, 2]: inclusive (first, last) of every run of depth == 0 / of 0 < depth < low_below
+        means, starts, ends   the utility's windows -- a stretch between two zero runs is cut into pieces of window_size from its
+                    first base on, the last piece shorter; no window is empty -- as float64 means (sum / bases, both below 2^53:
+                    np.mean of the int64 slice) and inclusive int64 bounds
+        sum_pos, n_pos   the sum of the depths > 0 and how many there are.
+    The utility walks every base three times in Python for the same."""
+    tracks._bind()
+    w = int(window_size)
+    wins = []
+    for target, start, end in items:
+        o = int(tracks.engine.offsets[tracks.targets.index(target)])
+        wins.append((o + int(start), o + int(end) + 1))
+    if not wins:
+        return []
+    zeros, lows, stats = tracks.engine.depth_classes(tracks.track, wins, low_below)
+    plans, ranges = [], []
+    for (a, b), zero in zip(wins, zeros):
+        edges = np.concatenate([[0], zero.reshape(-1), [b - a]]).astype(np.int64)      # the stretches between the zero runs
+        p, q = edges[0::2], edges[1::2]
+        keep = q > p
+        p, q = p[keep], q[keep]
+        per = (q - p + w - 1) // w                                                     # windows per stretch
+        of = np.repeat(np.arange(p.shape[0]), per)
+        k = np.arange(int(per.sum()), dtype=np.int64) - np.repeat(np.cumsum(per) - per, per)
+        begins = p[of] + k * w
+        ends = np.minimum(begins + w, q[of])
+        plans.append((begins, ends))
+        ranges.append(np.stack([begins + a, ends + a], axis=1))
+    sums = tracks.engine.range_sums(tracks.track, np.concatenate(ranges))
+    out, at = [], 0
+    for (begins, ends), zero, low, st in zip(plans, zeros, lows, stats):
+        n = begins.shape[0]
+        means = sums[at:at + n].astype(np.float64) / (ends - begins).astype(np.float64)
+        at += n
+        incl = np.array([0, -1], dtype=np.int64)
+        out.append({"zero": zero.reshape(-1, 2) + incl, "low": low.reshape(-1, 2) + incl, "means": means, "starts": begins,
+                    "ends": ends - 1, "sum_pos": int(st[0]), "n_pos": int(st[1])})
+    return out
+
+
 def pre_plot_base(depths_list: Sequence[DepthTracks], max_depths: Sequence[float], window_size=50000, start=0,
                   region: Optional[Tuple[str, int, int]] = None):
     """pre_plot_base of the reference (GCI.py:708-739).  region = (target, start, end) is the reference's
@@ -1757,7 +1802,7 @@ def _read_depth_members(engine: Engine, path: str, buf: bytearray, ref_lengths):
     return DepthTracks(engine, targets_length, track), targets_length
 
 
-def read_depth_tracks(engine: Engine, path: str, ref_lengths: Optional[Dict[str, int]] = None
+def read_depth_tracks(engine: Engine, path: str, ref_lengths: Optional[Dict[str, int]] = None, plotter_v2: bool = False
                       ) -> Tuple[Optional[DepthTracks], Dict[str, int]]:
     """parse_depth of the reference's GCI_score.py for a `.depth.gz` file -> (DepthTracks, {contig: length}).  A file this project
     wrote itself is read in the compressed domain (_read_depth_members; GCI_DEPTH_READ=text switches that off).  Any other file is inflated
@@ -1765,35 +1810,51 @@ def read_depth_tracks(engine: Engine, path: str, ref_lengths: Optional[Dict[str,
     lines (gci_depth_text_index), the host resolves the header lines into contigs and the device writes the track
     (gci_depth_text_parse).  Text outside the strict grammar, and a file the native inflate refuses, take the reference's own
     statements on the host (rare: hand-made files).  ref_lengths: when a contig of the file is not among them nothing is
-    uploaded and the tracks are None (the caller refuses the file)."""
+    uploaded and the tracks are None (the caller refuses the file).
+    plotter_v2: the reader of depth_plotter_v2.py -- a path that does not end in `.gz` is plain text (its bytes are the text, and from
+    there on it is the text path; every other caller gunzips the file whatever its name, as its utility does), the names by that
+    utility's expression, and (None, {}) instead of the host
+    statements of GCI_score.py wherever the file is not wholly inside the strict grammar with every name once (the caller then
+    reads it line by line, depthfile.lockstep_sequences)."""
     from .formats import depthfile
     with open(path, "rb") as f:
         buf = bytearray(os.path.getsize(path))
         f.readinto(buf)
-    with phases.wall("depth_gz_members"):
-        got = _read_depth_members(engine, path, buf, ref_lengths)
-    if got is not None:
-        return got
-    raw = np.frombuffer(buf, dtype=np.uint8)
-    del buf
-    try:
-        with phases.wall("depth_gz_inflate"):
-            gz = hostio.GzipText(raw, hostio.pick_threads(1))
-    except GciError:
-        import gzip
-        with gzip.open(path, "rb") as f:                 # raises what the reference's read raises (BadGzipFile, EOFError, zlib.error)
-            depths = depthfile.parse_depth_lines(f)
-        return _checked_upload(engine, depths, ref_lengths)
-    del raw
-    with phases.wall("depth_gz_export"), gz:                 # (the members' text into one host array; the members freed)
-        text = gz.export()
+    plain = plotter_v2 and not path.endswith(".gz")          # (that utility alone goes by the name; the others gunzip whatever it is)
+    if plain:
+        phases.note("depth_read:" + path, "text")
+        text = np.frombuffer(buf, dtype=np.uint8)
+    else:
+        with phases.wall("depth_gz_members"):
+            got = _read_depth_members(engine, path, buf, ref_lengths)
+        if got is not None:
+            return got
+        raw = np.frombuffer(buf, dtype=np.uint8)
+        del buf
+        try:
+            with phases.wall("depth_gz_inflate"):
+                gz = hostio.GzipText(raw, hostio.pick_threads(1))
+        except GciError:
+            if plotter_v2:
+                return None, {}
+            import gzip
+            with gzip.open(path, "rb") as f:                 # raises what the reference's read raises (BadGzipFile, EOFError, zlib.error)
+                depths = depthfile.parse_depth_lines(f)
+            return _checked_upload(engine, depths, ref_lengths)
+        del raw
+        with phases.wall("depth_gz_export"), gz:                 # (the members' text into one host array; the members freed)
+            text = gz.export()
+    if plotter_v2 and text.shape[0] == 0:
+        return None, {}
     with phases.wall("depth_text_upload"):
         d_text = engine.upload_staged(text) if text.shape[0] >= (256 << 20) else engine.to_device(text)
     with phases.wall("depth_text_parse"):
         d_line0, line0, keys, bad = engine.depth_text_index(d_text)
-        found = depthfile.header_segments(text, keys, line0) if bad == (1 << 64) - 1 else None
+        found = depthfile.header_segments(text, keys, line0, plotter_v2) if bad == (1 << 64) - 1 else None
         if found is None:
             del d_text, d_line0
+            if plotter_v2:
+                return None, {}
             import io
             return _checked_upload(engine, depthfile.parse_depth_lines(io.BytesIO(text.tobytes())), ref_lengths)
         names, lengths, segs = found

@@ -15,6 +15,7 @@
  *   gci_depth_text_*    write_depth (text body)       GCI.py:110-117
  *   gci_depth_sum       np.mean numerator             GCI.py:862-868
  *   gci_range_sums      sliding_window_average_depth  GCI.py:660-705 (window sums)
+ *   gci_depth_classes   analyze_depth_regions         utility/depth_plotter_v2.py (zero / low runs, non-zero statistics)
  *   gci_fasta_n_scan    get_Ns_ref                    GCI.py:27-35
  *   gci_paf_filter_device   filter(), PAF path        GCI.py:211-254  (+ helpers 49-61, 64-96)
  *
@@ -370,6 +371,13 @@ int gci_issue_scan(gci_ctx* ctx, const int32_t* d_depth, double lo, double hi, i
 int gci_issue_scan_windows(gci_ctx* ctx, const int32_t* d_depth, const gci_window* h_windows,
                            uint32_t n_windows, double lo, double hi, uint64_t* d_keys, uint32_t cap,
                            uint32_t* d_n_keys);
+
+/* depth_plotter_v2.py, DataProcessor.analyze_depth_regions + the non-zero statistics of plot_single_sequence, in ONE read of
+ * the windows: class 0 = (d == 0), class 1 = (0 < d < low_below).  d_keys: 2 x cap keys, d_n_keys: 2 counters, per class the keys
+ * gci_issue_scan_windows would give for that predicate (same key format, same closing rule at the window end).
+ * d_stats: n_windows x 2 int64, zeroed by the call: the sum of the depths > 0 and the number of bases with depth > 0. */
+int gci_depth_classes(gci_ctx* ctx, const int32_t* d_depth, const gci_window* h_windows, uint32_t n_windows, int32_t low_below,
+                      uint64_t* d_keys, uint32_t cap, uint32_t* d_n_keys, int64_t* d_stats);
 
 /* ---- R7: depth text -------------------------------------------------------------------------
  * size: d_contig_off[c] = byte offset of contig c's lines in the text, d_contig_off[n_contigs] =
