@@ -10,10 +10,13 @@ from __future__ import annotations
 import ctypes
 import os
 import subprocess
-from ctypes import POINTER, c_char_p, c_double, c_int, c_int32, c_int64, c_size_t, c_uint32, c_uint64, c_void_p
+from ctypes import c_char_p, c_int, c_uint32, c_void_p
 from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
+
+from . import _lib                         # (prototypes and structs alone: importing it loads no library)
+from ._lib import JoinFile as _JoinFile, Window as _Window
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(_HERE, "csrc", "cpu", "gci_cpu.cpp")
@@ -31,57 +34,14 @@ class CpuError(RuntimeError):
         self.status, self.rec = status, rec
 
 
-class _JoinFile(ctypes.Structure):
-    _fields_ = [("d_recs", c_void_p), ("n_recs", c_uint32), ("name_delta", c_uint32), ("d_name_base", c_void_p), ("d_name_off", c_void_p)]
-
-
-class _Window(ctypes.Structure):
-    _fields_ = [("begin", c_int64), ("end", c_int64)]
-
-
-# the seam set: the same names and argument lists as in gci_amd/_lib.py (include/gci_hip.h), + gci_cpu_option
-EXPORTS = [
-    ("gci_abi_version", c_int, []),
-    ("gci_ctx_create", c_int, [c_int, c_void_p, c_int, POINTER(c_void_p)]),
-    ("gci_ctx_destroy", c_int, [c_void_p]),
-    ("gci_sync", c_int, [c_void_p]),
-    ("gci_strerror", c_char_p, [c_int]),
-    ("gci_last_error", c_char_p, [c_void_p]),
-    ("gci_malloc", c_int, [c_void_p, c_size_t, POINTER(c_void_p)]),
-    ("gci_free", c_int, [c_void_p, c_void_p]),
-    ("gci_memcpy_h2d", c_int, [c_void_p, c_void_p, c_void_p, c_size_t]),
-    ("gci_memcpy_d2h", c_int, [c_void_p, c_void_p, c_void_p, c_size_t]),
-    ("gci_memset", c_int, [c_void_p, c_void_p, c_int, c_size_t]),
-    ("gci_layout_set", c_int, [c_void_p, c_int32, c_void_p]),
-    ("gci_layout_total", c_int64, [c_void_p]),
-    ("gci_layout_offsets", c_int, [c_void_p, c_void_p]),
-    ("gci_name_hash", c_uint64, [c_void_p, c_uint32]),
-    ("gci_decode_status", c_int, [c_uint64, POINTER(c_uint32)]),
-    ("gci_bam_filter", c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_void_p, c_int32, c_int, c_int, c_double, c_double,
-                               c_uint32, c_void_p, c_void_p]),
-    ("gci_name_join", c_int, [c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p]),
-    ("gci_depth_build", c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_int, c_void_p]),
-    ("gci_gap_mask", c_int, [c_void_p, c_void_p, c_void_p, c_uint32]),
-    ("gci_max2", c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
-    ("gci_issue_scan", c_int, [c_void_p, c_void_p, c_double, c_double, c_int, c_void_p, c_uint32, c_void_p]),
-    ("gci_issue_scan_windows", c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_double, c_double, c_void_p, c_uint32, c_void_p]),
-    ("gci_depth_classes", c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_int32, c_void_p, c_uint32, c_void_p, c_void_p]),
-    ("gci_depth_text_size", c_int, [c_void_p, c_void_p, c_void_p]),
-    ("gci_depth_text_write", c_int, [c_void_p, c_void_p, c_void_p, c_uint64]),
-    ("gci_depth_sum", c_int, [c_void_p, c_void_p, c_void_p]),
-    ("gci_range_sums", c_int, [c_void_p, c_void_p, c_void_p, c_uint64, c_void_p]),
-    ("gci_cpu_option", c_int, [c_void_p, c_char_p, c_int]),
-    ("gci_depth_deflate_from_build", c_int, [c_void_p, c_void_p]),
-    ("gci_depth_deflate_size", c_int, [c_void_p] * 4 + [c_uint32] + [c_void_p] * 4),
-    ("gci_depth_deflate_write", c_int, [c_void_p] * 4 + [c_uint32] + [c_void_p] * 5 + [c_uint64]),
-    ("gci_depth_text_index", c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p]),
-    ("gci_depth_text_parse", c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_void_p, c_uint32, c_void_p, c_uint64]),
-    ("gci_sdepth_index", c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p]),
-    ("gci_sdepth_parse", c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint64, c_void_p, c_uint32, c_void_p, c_uint64]),
-    ("gci_depth_gz_scan", c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_void_p]),
-    ("gci_depth_gz_runs", c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_void_p]),
-    ("gci_depth_gz_expand", c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint64]),
-]
+# the seam set: the argument lists are those of gci_amd/_lib.py (include/gci_hip.h), looked up by name; + gci_cpu_option
+_SEAMS = """gci_abi_version gci_ctx_create gci_ctx_destroy gci_sync gci_strerror gci_last_error gci_malloc gci_free gci_memcpy_h2d
+gci_memcpy_d2h gci_memset gci_layout_set gci_layout_total gci_layout_offsets gci_name_hash gci_decode_status gci_bam_filter gci_name_join
+gci_depth_build gci_gap_mask gci_max2 gci_issue_scan gci_issue_scan_windows gci_depth_classes gci_depth_text_size gci_depth_text_write
+gci_depth_sum gci_range_sums gci_depth_deflate_from_build gci_depth_deflate_size gci_depth_deflate_write gci_depth_text_index
+gci_depth_text_parse gci_sdepth_index gci_sdepth_parse gci_depth_gz_scan gci_depth_gz_runs gci_depth_gz_expand""".split()
+_PROTO = {name: (name, res, args) for name, res, args in _lib.EXPORTS}
+EXPORTS = [_PROTO[name] for name in _SEAMS] + [("gci_cpu_option", c_int, [c_void_p, c_char_p, c_int])]
 
 
 def needs_build() -> bool:
@@ -327,29 +287,52 @@ class CpuEngine:
         self._chk(self.lib.gci_range_sums(self.ctx, _p(track), _p(r), r.shape[0], _p(s)), "gci_range_sums")
         return s
 
-    # ---- the depth text back to a track (k_depth_parse.hip's twin)
-    def depth_text_index(self, text: np.ndarray) -> Tuple[np.ndarray, np.ndarray, int]:
-        """-> (uint32 line starts per 4096-byte tile, sorted uint64 header keys (offset << 12 | rank in tile), smallest offset of a
-        data line outside the strict grammar or 2**64 - 1)."""
+    # ---- text back to a track (k_depth_parse.hip's and k_sdepth.hip's twins)
+    def _text_index(self, call, text: np.ndarray, cap: int) -> Tuple[np.ndarray, np.ndarray, int]:
+        """call(text, tiles, keys, cap, n_keys, bad) until every key fitted -> (uint32 line starts per 4096-byte tile, the sorted keys,
+        the smallest offending offset or 2**64 - 1)."""
         text = np.ascontiguousarray(text, dtype=np.uint8)
-        tiles = np.zeros(max((text.shape[0] + 4095) // 4096, 1), dtype=np.uint32)
-        cap = 1 << 10
+        n_tiles = (text.shape[0] + 4095) // 4096
+        tiles = np.zeros(max(n_tiles, 1), dtype=np.uint32)
         while True:
-            keys = np.zeros(cap, dtype=np.uint64)
-            nh, bad = np.zeros(1, dtype=np.uint32), np.zeros(1, dtype=np.uint64)
-            self._chk(self.lib.gci_depth_text_index(self.ctx, _p(text), text.shape[0], _p(tiles), _p(keys), cap, _p(nh), _p(bad)),
-                      "gci_depth_text_index")
-            if int(nh[0]) <= cap:
-                return tiles[:(text.shape[0] + 4095) // 4096], np.sort(keys[:int(nh[0])]), int(bad[0])
-            cap = int(nh[0])
+            keys = np.zeros(max(cap, 1), dtype=np.uint64)
+            nk, bad = np.zeros(1, dtype=np.uint32), np.zeros(1, dtype=np.uint64)
+            call(text, tiles, keys, cap, nk, bad)
+            if int(nk[0]) <= cap:
+                return tiles[:n_tiles], np.sort(keys[:int(nk[0])]), int(bad[0])
+            cap = int(nk[0])
 
-    def depth_text_parse(self, text: np.ndarray, tile_line0: np.ndarray, segs: np.ndarray, track: np.ndarray) -> np.ndarray:
+    def _text_parse(self, fn, what: str, text: np.ndarray, tile_line0: np.ndarray, base: tuple, segs: np.ndarray, track: np.ndarray) -> np.ndarray:
+        """fn(ctx, text, n, tile_line0, *base, segs, n_segs, track, track_n)"""
         text = np.ascontiguousarray(text, dtype=np.uint8)
         line0 = np.ascontiguousarray(tile_line0, dtype=np.uint64)
         segs = np.ascontiguousarray(segs, dtype=np.int64).reshape(-1, 3)
-        self._chk(self.lib.gci_depth_text_parse(self.ctx, _p(text), text.shape[0], _p(line0), _p(segs), segs.shape[0], _p(track),
-                                                track.shape[0]), "gci_depth_text_parse")
+        self._chk(fn(self.ctx, _p(text), text.shape[0], _p(line0), *base, _p(segs), segs.shape[0], _p(track), track.shape[0]), what)
         return track
+
+    def depth_text_index(self, text: np.ndarray) -> Tuple[np.ndarray, np.ndarray, int]:
+        """-> (uint32 line starts per 4096-byte tile, sorted uint64 header keys (offset << 12 | rank in tile), smallest offset of a
+        data line outside the strict grammar or 2**64 - 1)."""
+        def call(text, tiles, keys, cap, nk, bad):
+            self._chk(self.lib.gci_depth_text_index(self.ctx, _p(text), text.shape[0], _p(tiles), _p(keys), cap, _p(nk), _p(bad)),
+                      "gci_depth_text_index")
+        return self._text_index(call, text, 1 << 10)
+
+    def depth_text_parse(self, text: np.ndarray, tile_line0: np.ndarray, segs: np.ndarray, track: np.ndarray) -> np.ndarray:
+        return self._text_parse(self.lib.gci_depth_text_parse, "gci_depth_text_parse", text, tile_line0, (), segs, track)
+
+    def sdepth_index(self, text: np.ndarray, prev_name: bytes = b"", cap: int = 1 << 10) -> Tuple[np.ndarray, np.ndarray, int]:
+        """-> (uint32 line starts per 4096-byte tile, sorted uint64 keys (offset << 12 | rank in tile) of the lines whose name differs
+        from the line in front -- the first line: from prev_name --, smallest offset of a line outside the strict grammar or 2**64 - 1)."""
+        prev = np.frombuffer(bytes(prev_name) or b"\0", dtype=np.uint8)
+
+        def call(text, tiles, keys, cap, nk, bad):
+            self._chk(self.lib.gci_sdepth_index(self.ctx, _p(text), text.shape[0], _p(prev), len(prev_name), _p(tiles), _p(keys), cap, _p(nk),
+                                                _p(bad)), "gci_sdepth_index")
+        return self._text_index(call, text, cap)
+
+    def sdepth_parse(self, text: np.ndarray, tile_line0: np.ndarray, segs: np.ndarray, track: np.ndarray, line_base: int = 0) -> np.ndarray:
+        return self._text_parse(self.lib.gci_sdepth_parse, "gci_sdepth_parse", text, tile_line0, (int(line_base),), segs, track)
 
     # ---- this project's own .depth.gz to a track without inflating it (k_depth_gz.hip's twin)
     def depth_gz_scan(self, raw: np.ndarray, cand_pos: np.ndarray) -> np.ndarray:
@@ -380,27 +363,3 @@ class CpuEngine:
     def depth_gz_track(self, raw: np.ndarray, members: np.ndarray, track: np.ndarray) -> np.ndarray:
         """The members' lines into `track` at each member's elem0 (device.Engine.depth_gz_track's twin)."""
         return self.depth_gz_expand(self.depth_gz_runs(raw, members), members, track)
-
-    # ---- samtools depth text to a track (k_sdepth.hip's twin)
-    def sdepth_index(self, text: np.ndarray, prev_name: bytes = b"", cap: int = 1 << 10) -> Tuple[np.ndarray, np.ndarray, int]:
-        """-> (uint32 line starts per 4096-byte tile, sorted uint64 keys (offset << 12 | rank in tile) of the lines whose name differs
-        from the line in front -- the first line: from prev_name --, smallest offset of a line outside the strict grammar or 2**64 - 1)."""
-        text = np.ascontiguousarray(text, dtype=np.uint8)
-        tiles = np.zeros(max((text.shape[0] + 4095) // 4096, 1), dtype=np.uint32)
-        prev = np.frombuffer(bytes(prev_name) or b"\0", dtype=np.uint8)
-        while True:
-            keys = np.zeros(max(cap, 1), dtype=np.uint64)
-            nk, bad = np.zeros(1, dtype=np.uint32), np.zeros(1, dtype=np.uint64)
-            self._chk(self.lib.gci_sdepth_index(self.ctx, _p(text), text.shape[0], _p(prev), len(prev_name), _p(tiles), _p(keys), cap, _p(nk),
-                                                _p(bad)), "gci_sdepth_index")
-            if int(nk[0]) <= cap:
-                return tiles[:(text.shape[0] + 4095) // 4096], np.sort(keys[:int(nk[0])]), int(bad[0])
-            cap = int(nk[0])
-
-    def sdepth_parse(self, text: np.ndarray, tile_line0: np.ndarray, segs: np.ndarray, track: np.ndarray, line_base: int = 0) -> np.ndarray:
-        text = np.ascontiguousarray(text, dtype=np.uint8)
-        line0 = np.ascontiguousarray(tile_line0, dtype=np.uint64)
-        segs = np.ascontiguousarray(segs, dtype=np.int64).reshape(-1, 3)
-        self._chk(self.lib.gci_sdepth_parse(self.ctx, _p(text), text.shape[0], _p(line0), int(line_base), _p(segs), segs.shape[0], _p(track),
-                                            track.shape[0]), "gci_sdepth_parse")
-        return track

@@ -997,7 +997,37 @@ int gci_depth_gz_expand(gci_ctx* ctx, const gci_dgz_run* runs, const gci_dgz_mem
 /* ---- depth text -> track (k_depth_parse.hip): the same tiles, line ownership, keys and status word, on host threads ------------ */
 namespace {
 constexpr uint64_t PARSE_TILE = 4096;
-inline bool line_start(const uint8_t* text, uint64_t i) { return i == 0 || text[i - 1] == '\n'; }
+inline uint64_t parse_tiles(uint64_t n) { return (n + PARSE_TILE - 1) / PARSE_TILE; }
+// f(offset, rank) for every line whose first byte is in the tile, in order; -> the number of those lines
+template <typename F>
+uint32_t for_each_line(const uint8_t* text, uint64_t n, uint64_t tile, F f)
+{
+    uint32_t rank = 0;
+    for (uint64_t i = tile * PARSE_TILE; i < std::min(n, (tile + 1) * PARSE_TILE); i++)
+        if (i == 0 || text[i - 1] == '\n') f(i, rank++);
+    return rank;
+}
+inline void note_first_bad(std::atomic<uint64_t>& first_bad, uint64_t i)
+{
+    uint64_t cur = first_bad.load();
+    while (i < cur && !first_bad.compare_exchange_weak(cur, i)) {}
+}
+inline void push_key(std::atomic<uint32_t>& slots, uint64_t* keys, uint32_t cap, uint64_t i, uint32_t rank)
+{
+    const uint32_t s = slots.fetch_add(1);
+    if (s < cap) keys[s] = (i << 12) | rank;
+}
+// the element of the track `line` goes to, through the last segment whose first line is <= line; -1: none
+int64_t seg_dest(const int64_t* segs, uint32_t n_segs, uint64_t line, uint64_t track_n)
+{
+    uint32_t a = 0, b = n_segs;
+    while (a < b) { const uint32_t m = (a + b) / 2; if ((uint64_t)segs[3 * m] <= line) a = m + 1; else b = m; }
+    if (a == 0) return -1;
+    const int64_t* s = segs + 3 * (a - 1);
+    if (s[2] < 0 || (int64_t)line >= s[0] + s[1]) return -1;
+    const int64_t e = s[2] + ((int64_t)line - s[0]);
+    return (uint64_t)e < track_n ? e : -1;
+}
 // [0-9]{1,10} then '\n' or the end of the text, value <= INT32_MAX -> value, or -1
 int64_t strict_value(const uint8_t* text, uint64_t i, uint64_t n)
 {
@@ -1016,22 +1046,12 @@ int gci_depth_text_index(gci_ctx* ctx, const uint8_t* text, uint64_t n, uint32_t
     if (!ctx || !n_hdr || !bad || (n && (!text || !tile_lines)) || (cap && !keys)) return GCI_E_INVALID;
     std::atomic<uint32_t> slots{0};
     std::atomic<uint64_t> first_bad{~0ull};
-    parallel_blocks(ctx->threads, (n + PARSE_TILE - 1) / PARSE_TILE, 64, [&](uint64_t lo, uint64_t hi) {
-        for (uint64_t t = lo; t < hi; t++) {
-            uint32_t rank = 0;
-            for (uint64_t i = t * PARSE_TILE; i < std::min(n, (t + 1) * PARSE_TILE); i++) {
-                if (!line_start(text, i)) continue;
-                if (text[i] == '>') {
-                    const uint32_t s = slots.fetch_add(1);
-                    if (s < cap) keys[s] = (i << 12) | rank;
-                } else if (strict_value(text, i, n) < 0) {
-                    uint64_t cur = first_bad.load();
-                    while (i < cur && !first_bad.compare_exchange_weak(cur, i)) {}
-                }
-                rank++;
-            }
-            tile_lines[t] = rank;
-        }
+    parallel_blocks(ctx->threads, parse_tiles(n), 64, [&](uint64_t lo, uint64_t hi) {
+        for (uint64_t t = lo; t < hi; t++)
+            tile_lines[t] = for_each_line(text, n, t, [&](uint64_t i, uint32_t rank) {
+                if (text[i] == '>') push_key(slots, keys, cap, i, rank);
+                else if (strict_value(text, i, n) < 0) note_first_bad(first_bad, i);
+            });
     });
     *n_hdr = slots.load();
     *bad = first_bad.load();
@@ -1043,25 +1063,15 @@ int gci_depth_text_parse(gci_ctx* ctx, const uint8_t* text, uint64_t n, const ui
 {
     if (!ctx || (n && (!text || !tile_line0)) || (n_segs && !segs) || (track_n && !track)) return GCI_E_INVALID;
     if (!n || !n_segs || !track_n) return GCI_OK;
-    parallel_blocks(ctx->threads, (n + PARSE_TILE - 1) / PARSE_TILE, 64, [&](uint64_t lo, uint64_t hi) {
-        for (uint64_t t = lo; t < hi; t++) {
-            uint64_t g = tile_line0[t];
-            for (uint64_t i = t * PARSE_TILE; i < std::min(n, (t + 1) * PARSE_TILE); i++) {
-                if (!line_start(text, i)) continue;
-                const uint64_t line = g++;
-                if (text[i] == '>') continue;
-                uint32_t a = 0, b = n_segs;                 // the last segment whose first data line is <= line
-                while (a < b) { const uint32_t m = (a + b) / 2; if ((uint64_t)segs[3 * m] <= line) a = m + 1; else b = m; }
-                if (a == 0) continue;
-                const int64_t* s = segs + 3 * (a - 1);
-                if (s[2] < 0 || (int64_t)line >= s[0] + s[1]) continue;
-                const int64_t e = s[2] + ((int64_t)line - s[0]);
-                if ((uint64_t)e >= track_n) continue;
+    parallel_blocks(ctx->threads, parse_tiles(n), 64, [&](uint64_t lo, uint64_t hi) {
+        for (uint64_t t = lo; t < hi; t++)
+            for_each_line(text, n, t, [&](uint64_t i, uint32_t rank) {
+                const int64_t e = text[i] == '>' ? -1 : seg_dest(segs, n_segs, tile_line0[t] + rank, track_n);
+                if (e < 0) return;
                 uint32_t v = 0;
                 for (uint64_t d = 0; d < 10 && i + d < n && text[i + d] >= '0' && text[i + d] <= '9'; d++) v = v * 10 + (uint32_t)(text[i + d] - '0');
                 track[e] = (int32_t)v;
-            }
-        }
+            });
     });
     return GCI_OK;
 }
@@ -1114,15 +1124,10 @@ int gci_sdepth_index(gci_ctx* ctx, const uint8_t* text, uint64_t n, const uint8_
         return GCI_E_INVALID;
     std::atomic<uint32_t> slots{0};
     std::atomic<uint64_t> first_bad{~0ull};
-    parallel_blocks(ctx->threads, (n + PARSE_TILE - 1) / PARSE_TILE, 64, [&](uint64_t lo, uint64_t hi) {
-        for (uint64_t t = lo; t < hi; t++) {
-            uint32_t rank = 0;
-            for (uint64_t i = t * PARSE_TILE; i < std::min(n, (t + 1) * PARSE_TILE); i++) {
-                if (!line_start(text, i)) continue;
-                if (!sd_strict_line(text, i, n)) {
-                    uint64_t cur = first_bad.load();
-                    while (i < cur && !first_bad.compare_exchange_weak(cur, i)) {}
-                }
+    parallel_blocks(ctx->threads, parse_tiles(n), 64, [&](uint64_t lo, uint64_t hi) {
+        for (uint64_t t = lo; t < hi; t++)
+            tile_lines[t] = for_each_line(text, n, t, [&](uint64_t i, uint32_t rank) {
+                if (!sd_strict_line(text, i, n)) note_first_bad(first_bad, i);
                 bool same;
                 if (i == 0) {
                     same = sd_same_name(prev_name, prev_len, true, text, 0, n);
@@ -1131,14 +1136,8 @@ int gci_sdepth_index(gci_ctx* ctx, const uint8_t* text, uint64_t n, const uint8_
                     while (q > 0 && i - q < SD_LINE_MAX + 1 && text[q - 1] != '\n') q--;
                     same = i - q <= SD_LINE_MAX && (q == 0 || text[q - 1] == '\n') && sd_same_name(text + q, 0, false, text, i, n);
                 }
-                if (!same) {
-                    const uint32_t s = slots.fetch_add(1);
-                    if (s < cap) keys[s] = (i << 12) | rank;
-                }
-                rank++;
-            }
-            tile_lines[t] = rank;
-        }
+                if (!same) push_key(slots, keys, cap, i, rank);
+            });
     });
     *n_keys = slots.load();
     *bad = first_bad.load();
@@ -1150,27 +1149,18 @@ int gci_sdepth_parse(gci_ctx* ctx, const uint8_t* text, uint64_t n, const uint64
 {
     if (!ctx || (n && (!text || !tile_line0)) || (n_segs && !segs) || (track_n && !track)) return GCI_E_INVALID;
     if (!n || !n_segs || !track_n) return GCI_OK;
-    parallel_blocks(ctx->threads, (n + PARSE_TILE - 1) / PARSE_TILE, 64, [&](uint64_t lo, uint64_t hi) {
-        for (uint64_t t = lo; t < hi; t++) {
-            uint64_t g = line_base + tile_line0[t];
-            for (uint64_t i = t * PARSE_TILE; i < std::min(n, (t + 1) * PARSE_TILE); i++) {
-                if (!line_start(text, i)) continue;
-                const uint64_t line = g++;
-                uint32_t a = 0, b = n_segs;                 // the last segment whose first line is <= line
-                while (a < b) { const uint32_t m = (a + b) / 2; if ((uint64_t)segs[3 * m] <= line) a = m + 1; else b = m; }
-                if (a == 0) continue;
-                const int64_t* s = segs + 3 * (a - 1);
-                if (s[2] < 0 || (int64_t)line >= s[0] + s[1]) continue;
-                const int64_t e = s[2] + ((int64_t)line - s[0]);
-                if ((uint64_t)e >= track_n) continue;
+    parallel_blocks(ctx->threads, parse_tiles(n), 64, [&](uint64_t lo, uint64_t hi) {
+        for (uint64_t t = lo; t < hi; t++)
+            for_each_line(text, n, t, [&](uint64_t i, uint32_t rank) {
+                const int64_t e = seg_dest(segs, n_segs, line_base + tile_line0[t] + rank, track_n);
+                if (e < 0) return;
                 uint64_t end = i;                           // the depth column: the digits in front of the line's end
                 while (end < n && text[end] != '\n') end++;
                 uint32_t v = 0, mul = 1;
                 for (uint64_t d = 1; d <= 10 && d <= end && text[end - d] >= '0' && text[end - d] <= '9'; d++, mul *= 10)
                     v += (uint32_t)(text[end - d] - '0') * mul;
                 track[e] = (int32_t)v;
-            }
-        }
+            });
     });
     return GCI_OK;
 }

@@ -15,6 +15,7 @@
 
 #include "../../include/gci_hip.h"
 #include "gci_common.h"
+#include "gci_wave.hpp"
 
 #define TILE GCI_TILE
 #define TEXT_LUT 1000                    // depths below this come out of a 4-byte-per-entry table
@@ -226,50 +227,6 @@ __device__ __forceinline__ void count_span(const IvlSpan& s, unsigned long long*
     else {
         if (s.has_b) atomicAdd(tile_cd + s.tile_b, 1ull);
         atomicAdd(tile_cd + s.tile_bc, minus1);
-    }
-}
-
-// ---- wave-level scans and sums -------------------------------------------------------------------
-// 32-bit values go through DPP (one v_add_*_dpp per step: row_shr 1/2/4/8 inside each 16-lane row, then
-// row_bcast:15 into rows 1 and 3, row_bcast:31 into rows 2 and 3); 64-bit values through ds_bpermute.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ int32_t dpp_add(int32_t v)
-{
-    return v + __builtin_amdgcn_update_dpp(0, v, CTRL, ROW_MASK, 0xF, true);
-}
-
-__device__ __forceinline__ int32_t wave_inclusive_i32(int32_t v)
-{
-    v = dpp_add<0x111, 0xF>(v);
-    v = dpp_add<0x112, 0xF>(v);
-    v = dpp_add<0x114, 0xF>(v);
-    v = dpp_add<0x118, 0xF>(v);
-    v = dpp_add<0x142, 0xA>(v);
-    v = dpp_add<0x143, 0xC>(v);
-    return v;
-}
-
-template <typename T>
-__device__ __forceinline__ T wave_inclusive(T v, int lane)
-{
-    if constexpr (sizeof(T) == 4) {
-        return (T)wave_inclusive_i32((int32_t)v);
-    } else {
-#pragma unroll
-        for (int d = 1; d < 64; d <<= 1) { T n = __shfl_up(v, d, 64); if (lane >= d) v += n; }
-        return v;
-    }
-}
-
-template <typename T>
-__device__ __forceinline__ T wave_sum(T v)
-{
-    if constexpr (sizeof(T) == 4) {
-        return (T)__builtin_amdgcn_readlane(wave_inclusive_i32((int32_t)v), 63);
-    } else {
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-        return v;
     }
 }
 
@@ -536,35 +493,11 @@ __device__ __forceinline__ void text_tile(const int4 (&v)[4], int64_t valid, uin
 }
 
 // ---------------------------------------------------------------------------------------------
-// small kernels used by more than one translation unit
+// small kernels launched from more than one translation unit (k_track.hip has them)
 // ---------------------------------------------------------------------------------------------
 
-// per-contig reduction of the per-tile sums: REDUCE_SPLIT workgroups per contig, each adds its share with one
-// 64-bit atomic (sums must be zeroed first)
-#define REDUCE_SPLIT 32
-__attribute__((unused)) static __global__ __launch_bounds__(BLOCK) void k_reduce_tiles(const long long* __restrict__ tile_sum,
-                                                        const int64_t* __restrict__ tile_first,
-                                                        unsigned long long* __restrict__ sums)
-{
-    __shared__ long long part[BLOCK / 64];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int64_t a = tile_first[blockIdx.x], b = tile_first[blockIdx.x + 1];
-    long long s = 0;
-    for (int64_t i = a + (int64_t)blockIdx.y * BLOCK + t; i < b; i += (int64_t)REDUCE_SPLIT * BLOCK) s += tile_sum[i];
-    s = wave_sum<long long>(s);
-    if (lane == 0) part[wave] = s;
-    __syncthreads();
-    if (t == 0) {
-        const long long v = part[0] + part[1] + part[2] + part[3];
-        if (v) atomicAdd(sums + blockIdx.x, (unsigned long long)v);
-    }
-}
-
-__attribute__((unused)) static __global__ void k_contig_text_off(const uint64_t* __restrict__ tile_off, const int64_t* __restrict__ tile_first,
-                                  int32_t n_contigs, int64_t n_tiles, uint64_t* __restrict__ contig_off)
-{
-    const int32_t c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c > n_contigs) return;
-    contig_off[c] = c == n_contigs ? tile_off[n_tiles] : tile_off[tile_first[c]];
-}
-
+#define REDUCE_SPLIT 32                  // workgroups per contig of k_reduce_tiles, and of the same reduction fused into k_depth.hip's scan
+// sums[c] += the sum of tile_sum over the tiles of contig c, for every contig of the layout (sums must be zeroed first)
+int gci_launch_reduce_tiles(gci_ctx* ctx, const long long* tile_sum, unsigned long long* sums);
+// contig_off[c] = tile_off[tile_first[c]] for c < n_contigs, contig_off[n_contigs] = tile_off[n_tiles]
+int gci_launch_contig_text_off(gci_ctx* ctx, const uint64_t* tile_off, uint64_t* contig_off);

@@ -1233,18 +1233,14 @@ extern "C" int gci_depth_build_begin(gci_ctx* ctx, const gci_ivl* d_ivl, const u
         } else {
             if (o->d_sums) {
                 ProfScope _ps(ctx, GCI_PROF_DEPTH_SUM);
-                hipLaunchKernelGGL(k_reduce_tiles, dim3(ctx->n_contigs, REDUCE_SPLIT), dim3(BLOCK), 0, ctx->stream,
-                                   (const long long*)ctx->tile_sum.p, tf, (unsigned long long*)o->d_sums);
-                LAUNCHCHK("k_reduce_tiles");
+                GCI_TRY(gci_launch_reduce_tiles(ctx, (const long long*)ctx->tile_sum.p, (unsigned long long*)o->d_sums));
             }
             if (o->want_text) {
                 ProfScope _ps(ctx, GCI_PROF_TEXT_COUNT);
                 GCI_TRY((device_exclusive_scan<uint32_t, unsigned long long>(ctx, (const uint32_t*)ctx->tile_u32.p,
                                                                              (unsigned long long*)ctx->tile_u64.p,
                                                                              (unsigned long long*)ctx->blk_u64.p, nt, true)));
-                hipLaunchKernelGGL(k_contig_text_off, dim3((ctx->n_contigs + 1 + 63) / 64), dim3(64), 0, ctx->stream,
-                                   (const uint64_t*)ctx->tile_u64.p, tf, ctx->n_contigs, nt, o->d_contig_text_off);
-                LAUNCHCHK("k_contig_text_off");
+                GCI_TRY(gci_launch_contig_text_off(ctx, (const uint64_t*)ctx->tile_u64.p, o->d_contig_text_off));
             }
         }
     }

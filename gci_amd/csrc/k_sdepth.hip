@@ -24,39 +24,14 @@
 // index is the tile's first line + the '\n's in front of it in the tile - 1 (a line that began in an earlier tile: first line -
 // 1).  16 bytes of halo in front are enough for that.  Values go to LDS by rank and are stored with consecutive lanes on
 // consecutive lines: the track is written coalesced.
-#include "gci_ctx.hpp"
+#include "gci_text_tiles.hpp"
 
 namespace {
 
-constexpr int SBLOCK = 256;
-constexpr uint32_t STILE = 4096;                   // bytes per tile (as k_depth_parse.hip)
 constexpr uint32_t SD_LINE_MAX = 255;              // bytes of a line with its '\n': the bound of the grammar
 constexpr uint32_t IHALO = 256;                    // pass 1: bytes staged in front of and behind the tile
 constexpr uint32_t PHALO = 16;                     // pass 2: bytes staged in front of the tile
-constexpr uint32_t MAX_ENDS = STILE / 6 + 4;       // valid text: every line but a last one without '\n' has >= 6 bytes
-
-__device__ __forceinline__ uint4 load16(const uint8_t* __restrict__ text, uint64_t n, int64_t at)
-{
-    if (at >= 0 && (uint64_t)at + 16 <= n) return *reinterpret_cast<const uint4*>(text + at);
-    union { uint4 v; uint8_t b[16]; } u;
-    for (int k = 0; k < 16; k++) u.b[k] = (at + k >= 0 && (uint64_t)(at + k) < n) ? text[at + k] : (uint8_t)0;
-    return u.v;
-}
-
-// exclusive prefix of `cnt` over the workgroup and the workgroup's total
-__device__ __forceinline__ uint32_t block_exclusive(uint32_t cnt, uint32_t& total)
-{
-    __shared__ uint32_t part[SBLOCK / 64];
-    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
-    const uint32_t inc = (uint32_t)wave_inclusive<int32_t>((int32_t)cnt, lane);
-    if (lane == 63) part[wave] = inc;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < SBLOCK / 64; w++) { before += w < wave ? part[w] : 0u; all += part[w]; }
-    total = all;
-    return before + inc - cnt;
-}
+constexpr uint32_t MAX_ENDS = TEXT_TILE / 6 + 4;   // valid text: every line but a last one without '\n' has >= 6 bytes
 
 __device__ __forceinline__ bool name_end(uint32_t c) { return c == '\t' || c == '\n'; }
 
@@ -107,34 +82,22 @@ __device__ __forceinline__ bool same_as_prev(const uint8_t* __restrict__ b, uint
     return false;
 }
 
-struct IndexText {
-    uint4 v[(IHALO + STILE + IHALO) / 16];         // [0 .. 15]: in front of the tile, [16 .. 271]: the tile, [272 .. 287]: behind
-};
-
-__global__ __launch_bounds__(SBLOCK) void k_sdepth_index(const uint8_t* __restrict__ text, uint64_t n, const uint8_t* __restrict__ prev,
-                                                         uint32_t prev_len, uint32_t* __restrict__ tile_lines,
-                                                         unsigned long long* __restrict__ keys, uint32_t cap, uint32_t* __restrict__ n_keys,
-                                                         unsigned long long* __restrict__ bad)
+__global__ __launch_bounds__(TEXT_BLOCK) void k_sdepth_index(const uint8_t* __restrict__ text, uint64_t n, const uint8_t* __restrict__ prev,
+                                                             uint32_t prev_len, uint32_t* __restrict__ tile_lines,
+                                                             unsigned long long* __restrict__ keys, uint32_t cap, uint32_t* __restrict__ n_keys,
+                                                             unsigned long long* __restrict__ bad)
 {
-    __shared__ IndexText s;
-    __shared__ uint16_t s_start[STILE];              // LDS position of the tile's line starts, by rank
+    __shared__ TileText<IHALO, IHALO> s;
+    __shared__ uint16_t s_start[TEXT_TILE];          // LDS position of the tile's line starts, by rank
+    __shared__ uint32_t wtot[TEXT_BLOCK / 64];
     const int t = threadIdx.x;
-    const uint64_t tile0 = (uint64_t)blockIdx.x * STILE;
-    s.v[IHALO / 16 + t] = load16(text, n, (int64_t)(tile0 + 16u * t));
-    if (t < (int)(IHALO / 16)) s.v[t] = load16(text, n, (int64_t)tile0 - (int64_t)IHALO + 16 * t);
-    else if (t < (int)(2 * IHALO / 16)) s.v[(IHALO + STILE) / 16 + (t - IHALO / 16)] = load16(text, n, (int64_t)(tile0 + STILE) + 16 * (t - (int)(IHALO / 16)));
-    __syncthreads();
-    const uint8_t* b = reinterpret_cast<const uint8_t*>(s.v);
+    const uint64_t tile0 = stage_tile(text, n, s);
+    const uint8_t* b = s.bytes();
     const uint32_t p0 = IHALO + 16u * t;
     const uint64_t at = tile0 + 16u * t;
-    uint32_t mask = 0;
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-        const bool start = (at + k == 0) || b[p0 + k - 1] == '\n';
-        mask |= (at + k < n && start) ? (1u << k) : 0u;
-    }
+    const uint32_t mask = line_starts(b + IHALO, tile0, n);
     uint32_t total;
-    const uint32_t rank0 = block_exclusive((uint32_t)__builtin_popcount(mask), total);
+    const uint32_t rank0 = block_exclusive<uint32_t, TEXT_BLOCK / 64>((uint32_t)__builtin_popcount(mask), wtot, total);
     if (t == 0) tile_lines[blockIdx.x] = total;
     uint32_t rank = rank0;
     for (uint32_t m = mask; m; m &= m - 1u, rank++) s_start[rank] = (uint16_t)(p0 + (uint32_t)__builtin_ctz(m));
@@ -162,39 +125,26 @@ __global__ __launch_bounds__(SBLOCK) void k_sdepth_index(const uint8_t* __restri
             }
             same = q != 0xFFFFFFFFu && p - q <= SD_LINE_MAX && same_name(b, q, p, i, n);
         }
-        if (!same) {
-            const uint32_t slot = atomicAdd(n_keys, 1u);
-            if (slot < cap) keys[slot] = ((unsigned long long)i << 12) | rank;
-        }
+        if (!same) push_key(keys, cap, n_keys, i, rank);
     }
 }
 
-struct ParseText {
-    uint4 v[(PHALO + STILE) / 16];                 // [0]: the 16 bytes in front of the tile, [1 .. 256]: the tile
-};
-
-__global__ __launch_bounds__(SBLOCK) void k_sdepth_parse(const uint8_t* __restrict__ text, uint64_t n, const uint64_t* __restrict__ tile_line0,
-                                                         uint64_t line_base, const int64_t* __restrict__ segs, uint32_t n_segs,
-                                                         int32_t* __restrict__ track, uint64_t track_n)
+__global__ __launch_bounds__(TEXT_BLOCK) void k_sdepth_parse(const uint8_t* __restrict__ text, uint64_t n, const uint64_t* __restrict__ tile_line0,
+                                                             uint64_t line_base, const int64_t* __restrict__ segs, uint32_t n_segs,
+                                                             int32_t* __restrict__ track, uint64_t track_n)
 {
-    __shared__ ParseText s;
+    __shared__ TileText<PHALO, 0> s;
     __shared__ int32_t s_val[MAX_ENDS];
     __shared__ int64_t s_dst[MAX_ENDS];
+    __shared__ uint32_t wtot[TEXT_BLOCK / 64];
     __shared__ int32_t s_seg0;
     const int t = threadIdx.x;
-    const uint64_t tile0 = (uint64_t)blockIdx.x * STILE;
-    s.v[1 + t] = load16(text, n, (int64_t)(tile0 + 16u * t));
-    if (t == 0) s.v[0] = load16(text, n, (int64_t)tile0 - 16);
-    __syncthreads();
-    const uint8_t* b = reinterpret_cast<const uint8_t*>(s.v);
+    const uint64_t tile0 = stage_tile(text, n, s);
+    const uint8_t* b = s.bytes();
     // the line that holds the tile's first byte: the first line of the tile if it begins there, else the one in front of it
     const bool begins = tile0 == 0 || b[PHALO - 1] == '\n';
     const uint64_t g0 = line_base + tile_line0[blockIdx.x] - (begins ? 0u : 1u);
-    if (t == 0) {                                    // the last segment whose first line is at or before g0
-        uint32_t lo = 0, hi = n_segs;
-        while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if ((uint64_t)segs[3 * mid] <= g0) lo = mid + 1; else hi = mid; }
-        s_seg0 = (int32_t)lo - 1;
-    }
+    if (t == 0) s_seg0 = seg_search(segs, n_segs, g0);
     const uint32_t p0 = PHALO + 16u * t;
     const uint64_t at = tile0 + 16u * t;
     // line ends among this lane's bytes: a '\n' (the digits end in front of it), and the text's last byte when it is no '\n'
@@ -209,41 +159,29 @@ __global__ __launch_bounds__(SBLOCK) void k_sdepth_parse(const uint8_t* __restri
     }
     // (a line end with r '\n's of the tile in front of it closes line g0 + r)
     uint32_t total_nl;
-    const uint32_t before = block_exclusive((uint32_t)__builtin_popcount(nl), total_nl);      // (its barrier also publishes s_seg0)
+    const uint32_t before = block_exclusive<uint32_t, TEXT_BLOCK / 64>((uint32_t)__builtin_popcount(nl), wtot, total_nl);   // (its barrier also publishes s_seg0)
     int32_t seg = s_seg0;
-    uint32_t total_ends = total_nl + ((tile0 + STILE >= n && n && text[n - 1] != '\n') ? 1u : 0u);
+    const uint32_t total_ends = total_nl + ((tile0 + TEXT_TILE >= n && n && text[n - 1] != '\n') ? 1u : 0u);
     for (uint32_t m = ends; m; m &= m - 1u) {
         const uint32_t k = (uint32_t)__builtin_ctz(m);
         const uint32_t r = before + (uint32_t)__builtin_popcount(nl & ((1u << k) - 1u));
         const uint64_t g = g0 + r;
         uint32_t e = p0 + k;                         // one behind the last digit
         if (!((nl >> k) & 1u)) e++;
-        while (seg + 1 < (int32_t)n_segs && (uint64_t)segs[3 * (seg + 1)] <= g) seg++;
-        int64_t dst = -1;
-        int32_t val = 0;
-        if (seg >= 0) {
-            const int64_t first = segs[3 * seg], cnt = segs[3 * seg + 1], base = segs[3 * seg + 2];
-            if (base >= 0 && (int64_t)g >= first && (int64_t)g < first + cnt) {
-                uint32_t v = 0, mul = 1;
-                for (uint32_t d = 1; d <= 10u && d <= e; d++) {
-                    const uint32_t c = (uint32_t)b[e - d] - '0';
-                    if (c > 9u) break;
-                    v += c * mul;
-                    mul *= 10u;
-                }
-                const int64_t el = base + ((int64_t)g - first);
-                if ((uint64_t)el < track_n) { dst = el; val = (int32_t)v; }
+        seg_advance(segs, n_segs, seg, g);
+        const int64_t dst = seg_dest(segs, seg, g, track_n);
+        uint32_t v = 0, mul = 1;
+        if (dst >= 0) {                              // backwards from the line end
+            for (uint32_t d = 1; d <= 10u && d <= e; d++) {
+                const uint32_t c = (uint32_t)b[e - d] - '0';
+                if (c > 9u) break;
+                v += c * mul;
+                mul *= 10u;
             }
         }
-        if (r < MAX_ENDS) { s_val[r] = val; s_dst[r] = dst; }
-        else if (dst >= 0) track[dst] = val;         // (only text outside the grammar has this many lines in a tile)
+        rank_put<MAX_ENDS>(s_val, s_dst, r, (int32_t)v, dst, track);
     }
-    __syncthreads();
-    const uint32_t staged = total_ends < MAX_ENDS ? total_ends : MAX_ENDS;
-    for (uint32_t r = t; r < staged; r += SBLOCK) {
-        const int64_t dst = s_dst[r];
-        if (dst >= 0) track[dst] = s_val[r];
-    }
+    rank_flush<MAX_ENDS>(s_val, s_dst, total_ends, track);
 }
 
 }  // namespace
@@ -257,9 +195,9 @@ extern "C" int gci_sdepth_index(gci_ctx* ctx, const uint8_t* d_text, uint64_t n_
     HIPCHK(hipMemsetAsync(d_n_keys, 0, 4, ctx->stream));
     HIPCHK(hipMemsetAsync(d_bad, 0xFF, 8, ctx->stream));
     if (!n_bytes) return GCI_OK;
-    const uint64_t tiles = (n_bytes + STILE - 1) / STILE;
-    if (tiles > 0x7FFFFFFFull || (n_bytes >> 51)) return GCI_E_INVALID;
-    hipLaunchKernelGGL(k_sdepth_index, dim3((uint32_t)tiles), dim3(SBLOCK), 0, ctx->stream, d_text, n_bytes, d_prev_name, prev_len,
+    const int64_t tiles = text_tiles(n_bytes, true);
+    if (tiles < 0) return GCI_E_INVALID;
+    hipLaunchKernelGGL(k_sdepth_index, dim3((uint32_t)tiles), dim3(TEXT_BLOCK), 0, ctx->stream, d_text, n_bytes, d_prev_name, prev_len,
                        d_tile_lines, (unsigned long long*)d_keys, cap, d_n_keys, (unsigned long long*)d_bad);
     LAUNCHCHK("k_sdepth_index");
     return GCI_OK;
@@ -271,9 +209,9 @@ extern "C" int gci_sdepth_parse(gci_ctx* ctx, const uint8_t* d_text, uint64_t n_
     if (!ctx || (n_bytes && (!d_text || !d_tile_line0)) || (n_segs && !d_segs) || (track_n && !d_track) || ((uintptr_t)d_text & 15u))
         return GCI_E_INVALID;
     if (!n_bytes || !n_segs || !track_n) return GCI_OK;
-    const uint64_t tiles = (n_bytes + STILE - 1) / STILE;
-    if (tiles > 0x7FFFFFFFull) return GCI_E_INVALID;
-    hipLaunchKernelGGL(k_sdepth_parse, dim3((uint32_t)tiles), dim3(SBLOCK), 0, ctx->stream, d_text, n_bytes, d_tile_line0, line_base,
+    const int64_t tiles = text_tiles(n_bytes, false);
+    if (tiles < 0) return GCI_E_INVALID;
+    hipLaunchKernelGGL(k_sdepth_parse, dim3((uint32_t)tiles), dim3(TEXT_BLOCK), 0, ctx->stream, d_text, n_bytes, d_tile_line0, line_base,
                        d_segs, n_segs, d_track, track_n);
     LAUNCHCHK("k_sdepth_parse");
     return GCI_OK;

@@ -83,6 +83,33 @@ __global__ __launch_bounds__(BLOCK) void k_tile_sum(const int32_t* __restrict__ 
     if (t == 0) tile_sum[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
 }
 
+// per-contig reduction of the per-tile sums: REDUCE_SPLIT workgroups per contig, each adds its share with one
+// 64-bit atomic (sums must be zeroed first)
+__global__ __launch_bounds__(BLOCK) void k_reduce_tiles(const long long* __restrict__ tile_sum, const int64_t* __restrict__ tile_first,
+                                                        unsigned long long* __restrict__ sums)
+{
+    __shared__ long long part[BLOCK / 64];
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int64_t a = tile_first[blockIdx.x], b = tile_first[blockIdx.x + 1];
+    long long s = 0;
+    for (int64_t i = a + (int64_t)blockIdx.y * BLOCK + t; i < b; i += (int64_t)REDUCE_SPLIT * BLOCK) s += tile_sum[i];
+    s = wave_sum<long long>(s);
+    if (lane == 0) part[wave] = s;
+    __syncthreads();
+    if (t == 0) {
+        const long long v = part[0] + part[1] + part[2] + part[3];
+        if (v) atomicAdd(sums + blockIdx.x, (unsigned long long)v);
+    }
+}
+
+int gci_launch_reduce_tiles(gci_ctx* ctx, const long long* tile_sum, unsigned long long* sums)
+{
+    hipLaunchKernelGGL(k_reduce_tiles, dim3(ctx->n_contigs, REDUCE_SPLIT), dim3(BLOCK), 0, ctx->stream, tile_sum,
+                       (const int64_t*)ctx->d_tile_first.p, sums);
+    LAUNCHCHK("k_reduce_tiles");
+    return GCI_OK;
+}
+
 extern "C" int gci_depth_sum(gci_ctx* ctx, const int32_t* d_depth, int64_t* d_sums)
 {
     if (!ctx || !d_depth || !d_sums) return GCI_E_INVALID;
@@ -93,10 +120,7 @@ extern "C" int gci_depth_sum(gci_ctx* ctx, const int32_t* d_depth, int64_t* d_su
     hipLaunchKernelGGL(k_tile_sum, dim3((uint32_t)ctx->n_tiles), dim3(BLOCK), 0, ctx->stream, d_depth,
                        (long long*)ctx->tile_sum.p);
     LAUNCHCHK("k_tile_sum");
-    hipLaunchKernelGGL(k_reduce_tiles, dim3(ctx->n_contigs, REDUCE_SPLIT), dim3(BLOCK), 0, ctx->stream,
-                       (const long long*)ctx->tile_sum.p, (const int64_t*)ctx->d_tile_first.p, (unsigned long long*)d_sums);
-    LAUNCHCHK("k_reduce_tiles");
-    return GCI_OK;
+    return gci_launch_reduce_tiles(ctx, (const long long*)ctx->tile_sum.p, (unsigned long long*)d_sums);
 }
 
 // ============================================================================================
@@ -503,12 +527,9 @@ extern "C" int gci_two_type_tail(gci_ctx* ctx, int32_t* d_a, int32_t* d_b, int32
     hipLaunchKernelGGL(k_two_type_tail, dim3((uint32_t)ctx->n_tiles), dim3(BLOCK), 0, ctx->stream, A);
     LAUNCHCHK("k_two_type_tail");
     if (d_sums)
-        for (int x = 0; x < 3; x++) {
-            hipLaunchKernelGGL(k_reduce_tiles, dim3(ctx->n_contigs, REDUCE_SPLIT), dim3(BLOCK), 0, ctx->stream,
-                               (const long long*)ctx->tail_sums.p + (size_t)x * ctx->n_tiles, (const int64_t*)ctx->d_tile_first.p,
-                               (unsigned long long*)d_sums + (size_t)x * ctx->n_contigs);
-            LAUNCHCHK("k_reduce_tiles");
-        }
+        for (int x = 0; x < 3; x++)
+            GCI_TRY(gci_launch_reduce_tiles(ctx, (const long long*)ctx->tail_sums.p + (size_t)x * ctx->n_tiles,
+                                            (unsigned long long*)d_sums + (size_t)x * ctx->n_contigs));
     return GCI_OK;
 }
 
@@ -565,6 +586,22 @@ __global__ __launch_bounds__(BLOCK) void k_text_write(const int32_t* __restrict_
     else text_tile<false>(v, valid, stage, wtot, lut, out, tile_off[blockIdx.x], cap, t, lane, wave);
 }
 
+__global__ void k_contig_text_off(const uint64_t* __restrict__ tile_off, const int64_t* __restrict__ tile_first, int32_t n_contigs,
+                                  int64_t n_tiles, uint64_t* __restrict__ contig_off)
+{
+    const int32_t c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c > n_contigs) return;
+    contig_off[c] = c == n_contigs ? tile_off[n_tiles] : tile_off[tile_first[c]];
+}
+
+int gci_launch_contig_text_off(gci_ctx* ctx, const uint64_t* tile_off, uint64_t* contig_off)
+{
+    hipLaunchKernelGGL(k_contig_text_off, dim3((ctx->n_contigs + 1 + 63) / 64), dim3(64), 0, ctx->stream, tile_off,
+                       (const int64_t*)ctx->d_tile_first.p, ctx->n_contigs, ctx->n_tiles, contig_off);
+    LAUNCHCHK("k_contig_text_off");
+    return GCI_OK;
+}
+
 extern "C" int gci_depth_text_size(gci_ctx* ctx, const int32_t* d_depth, uint64_t* d_contig_off)
 {
     if (!ctx || !d_depth || !d_contig_off) return GCI_E_INVALID;
@@ -579,11 +616,7 @@ extern "C" int gci_depth_text_size(gci_ctx* ctx, const int32_t* d_depth, uint64_
     GCI_TRY((device_exclusive_scan<uint32_t, unsigned long long>(ctx, (const uint32_t*)ctx->tile_u32.p,
                                                                  (unsigned long long*)ctx->tile_u64.p,
                                                                  (unsigned long long*)ctx->blk_u64.p, nt, true)));
-    hipLaunchKernelGGL(k_contig_text_off, dim3((ctx->n_contigs + 1 + 63) / 64), dim3(64), 0, ctx->stream,
-                       (const uint64_t*)ctx->tile_u64.p, (const int64_t*)ctx->d_tile_first.p, ctx->n_contigs, nt,
-                       d_contig_off);
-    LAUNCHCHK("k_contig_text_off");
-    return GCI_OK;
+    return gci_launch_contig_text_off(ctx, (const uint64_t*)ctx->tile_u64.p, d_contig_off);
 }
 
 extern "C" int gci_depth_text_write(gci_ctx* ctx, const int32_t* d_depth, uint8_t* d_out, uint64_t cap)

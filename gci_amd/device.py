@@ -893,19 +893,17 @@ class Engine:
             cap = nk
         return kept.cpu().numpy().view(np.uint32)[:tiles], np.sort(keys[:nk].cpu().numpy().view(np.uint64))
 
-    def depth_text_index(self, d_text: Buffer) -> Tuple[Buffer, np.ndarray, np.ndarray, int]:
-        """gci_depth_text_index + the exclusive scan of its tile counts (gci_dev_u32_scan_u64) over depth text in HBM
-        -> (device uint64 [n_tiles + 1] first line index of every tile, the same on the host, sorted uint64 header keys
-        (byte offset << 12 | rank in its tile), smallest byte offset of a data line outside the strict grammar or 2**64 - 1)."""
+    def _text_index(self, call, d_text: Buffer, cap: int) -> Tuple[Buffer, np.ndarray, np.ndarray, int]:
+        """call(n, counts, keys, cap, n_keys, bad) until every key fitted, then the exclusive scan of the tile counts
+        (gci_dev_u32_scan_u64) -> (device uint64 [n_tiles + 1] first line index of every tile, the same on the host, the sorted
+        uint64 keys, the smallest offending byte offset or 2**64 - 1)."""
         n = int(d_text.shape[0])
         tiles = (n + 4095) // 4096
         counts = self.T.empty(max(tiles, 1), self.T.int32, self.device)
         bad = self.T.empty(1, self.T.int64, self.device)
-        cap = 1 << 12
         while True:
-            keys = self.T.empty(cap, self.T.int64, self.device)
-            self._chk(self.lib.gci_depth_text_index(self.ctx, self._p(d_text), n, self._p(counts), self._p(keys), cap, self._p(self._count),
-                                                    self._p(bad)), "gci_depth_text_index")
+            keys = self.T.empty(max(cap, 1), self.T.int64, self.device)
+            call(n, counts, keys, cap, self._count, bad)
             nk = int(self._count.item())
             if nk <= cap:
                 break
@@ -916,13 +914,26 @@ class Engine:
         h_line0 = line0.cpu().numpy().view(np.uint64)
         return line0, h_line0, np.sort(keys[:nk].cpu().numpy().view(np.uint64)), int(bad.cpu().numpy().view(np.uint64)[0])
 
-    def depth_text_parse(self, d_text: Buffer, d_line0: Buffer, segs: np.ndarray, track: Buffer) -> Buffer:
-        """gci_depth_text_parse: segs = int64 [n, 3] (first data line, data lines, track element of the first or -1), sorted."""
+    def _text_parse(self, fn, what: str, d_text: Buffer, d_line0: Buffer, base: tuple, segs: np.ndarray, track: Buffer) -> Buffer:
+        """fn(ctx, text, n, tile_line0, *base, segs, n_segs, track, track_n); segs = int64 [n, 3], sorted, uploaded here."""
         segs = np.ascontiguousarray(segs, dtype=np.int64).reshape(-1, 3)
         d_segs = self.to_device(segs) if segs.shape[0] else None
-        self._chk(self.lib.gci_depth_text_parse(self.ctx, self._p(d_text), int(d_text.shape[0]), self._p(d_line0), self._p(d_segs),
-                                                int(segs.shape[0]), self._p(track), int(track.shape[0])), "gci_depth_text_parse")
+        self._chk(fn(self.ctx, self._p(d_text), int(d_text.shape[0]), self._p(d_line0), *base, self._p(d_segs), int(segs.shape[0]),
+                     self._p(track), int(track.shape[0])), what)
         return track
+
+    def depth_text_index(self, d_text: Buffer) -> Tuple[Buffer, np.ndarray, np.ndarray, int]:
+        """gci_depth_text_index + the exclusive scan of its tile counts (gci_dev_u32_scan_u64) over depth text in HBM
+        -> (device uint64 [n_tiles + 1] first line index of every tile, the same on the host, sorted uint64 header keys
+        (byte offset << 12 | rank in its tile), smallest byte offset of a data line outside the strict grammar or 2**64 - 1)."""
+        def call(n, counts, keys, cap, n_keys, bad):
+            self._chk(self.lib.gci_depth_text_index(self.ctx, self._p(d_text), n, self._p(counts), self._p(keys), cap, self._p(n_keys),
+                                                    self._p(bad)), "gci_depth_text_index")
+        return self._text_index(call, d_text, 1 << 12)
+
+    def depth_text_parse(self, d_text: Buffer, d_line0: Buffer, segs: np.ndarray, track: Buffer) -> Buffer:
+        """gci_depth_text_parse: segs = int64 [n, 3] (first data line, data lines, track element of the first or -1), sorted."""
+        return self._text_parse(self.lib.gci_depth_text_parse, "gci_depth_text_parse", d_text, d_line0, (), segs, track)
 
     # ---- this project's own .depth.gz to a track without inflating it (k_depth_gz.hip) ------------------------------------
     def depth_gz_scan(self, d_raw: Buffer, cand_pos: np.ndarray) -> np.ndarray:
@@ -967,33 +978,17 @@ class Engine:
         first line index of every tile, the same on the host, sorted uint64 keys (byte offset << 12 | rank in its tile) of the
         lines whose name differs from the line in front -- the first line: from prev_name --, smallest byte offset of a line
         outside the strict grammar or 2**64 - 1)."""
-        n = int(d_text.shape[0])
-        tiles = (n + 4095) // 4096
-        counts = self.T.empty(max(tiles, 1), self.T.int32, self.device)
-        bad = self.T.empty(1, self.T.int64, self.device)
         d_prev = self.to_device(np.frombuffer(bytes(prev_name), dtype=np.uint8)) if prev_name else None
-        while True:
-            keys = self.T.empty(max(cap, 1), self.T.int64, self.device)
+
+        def call(n, counts, keys, cap, n_keys, bad):
             self._chk(self.lib.gci_sdepth_index(self.ctx, self._p(d_text), n, self._p(d_prev), len(prev_name), self._p(counts), self._p(keys),
-                                                cap, self._p(self._count), self._p(bad)), "gci_sdepth_index")
-            nk = int(self._count.item())
-            if nk <= cap:
-                break
-            cap = nk
-        line0 = self.T.empty(tiles + 1, self.T.int64, self.device)
-        self._chk(self.lib.gci_dev_u32_scan_u64(self.device.index or 0, self._p(counts), tiles, self._p(line0),
-                                                ctypes.c_void_p(self.stream.cuda_stream)), "gci_dev_u32_scan_u64")
-        h_line0 = line0.cpu().numpy().view(np.uint64)
-        return line0, h_line0, np.sort(keys[:nk].cpu().numpy().view(np.uint64)), int(bad.cpu().numpy().view(np.uint64)[0])
+                                                cap, self._p(n_keys), self._p(bad)), "gci_sdepth_index")
+        return self._text_index(call, d_text, cap)
 
     def sdepth_parse(self, d_text: Buffer, d_line0: Buffer, segs: np.ndarray, track: Buffer, line_base: int = 0) -> Buffer:
         """gci_sdepth_parse: segs = int64 [n, 3] (first line in the file, lines, track element of the first or -1), sorted; line_base =
         the lines of the file in front of d_text."""
-        segs = np.ascontiguousarray(segs, dtype=np.int64).reshape(-1, 3)
-        d_segs = self.to_device(segs) if segs.shape[0] else None
-        self._chk(self.lib.gci_sdepth_parse(self.ctx, self._p(d_text), int(d_text.shape[0]), self._p(d_line0), int(line_base), self._p(d_segs),
-                                            int(segs.shape[0]), self._p(track), int(track.shape[0])), "gci_sdepth_parse")
-        return track
+        return self._text_parse(self.lib.gci_sdepth_parse, "gci_sdepth_parse", d_text, d_line0, (int(line_base),), segs, track)
 
     def range_sums(self, track: Buffer, ranges: np.ndarray) -> np.ndarray:
         """Sum of the depths in each [begin, end) of track element indices (int64 [n, 2]) -> int64 [n]."""

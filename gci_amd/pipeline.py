@@ -1778,6 +1778,19 @@ def depth_members_plan(engine, path: str, buf, to_engine):
     return plan
 
 
+def _depth_file_track(engine: Engine, names, lengths, ref_lengths):
+    """The contigs of a depth file laid out on the device -> ({contig: length}, the zeroed track).  The track is None, and nothing
+    is laid out, when ref_lengths is given and lacks one of the contigs; a contig an int32 index cannot span is refused."""
+    from .formats import depthfile
+    targets_length = dict(zip(names, lengths))
+    if ref_lengths is not None and any(t not in ref_lengths for t in targets_length):
+        return targets_length, None
+    if any(L > depthfile.INT32_MAX for L in lengths):
+        sys.exit("ERROR!!! A contig of the depth file is longer than 2^31 - 1 bases, which is not supported")
+    engine.set_layout(lengths)
+    return targets_length, engine.T.zeros(max(engine.total, 1), engine.T.int32, engine.device)     # (the padding behind every contig too)
+
+
 def _read_depth_members(engine: Engine, path: str, buf: bytearray, ref_lengths):
     """read_depth_tracks for a file of this project's own writer: its bytes to HBM as they are, the members decoded into runs and
     the runs expanded into the track (k_depth_gz.hip).  No text on the host or the device.  -> None: not such a file."""
@@ -1791,13 +1804,9 @@ def _read_depth_members(engine: Engine, path: str, buf: bytearray, ref_lengths):
     if plan is None:
         return None
     (names, lengths, members), d_raw = plan
-    targets_length = dict(zip(names, lengths))
-    if ref_lengths is not None and any(t not in ref_lengths for t in targets_length):
+    targets_length, track = _depth_file_track(engine, names, lengths, ref_lengths)
+    if track is None:
         return None, targets_length
-    if any(L > depthfile.INT32_MAX for L in lengths):
-        sys.exit("ERROR!!! A contig of the depth file is longer than 2^31 - 1 bases, which is not supported")
-    engine.set_layout(lengths)
-    track = engine.T.zeros(max(engine.total, 1), engine.T.int32, engine.device)     # (the padding behind every contig too)
     engine.depth_gz_track(d_raw, depthfile.place_members(members, engine.offsets), track)
     return DepthTracks(engine, targets_length, track), targets_length
 
@@ -1858,13 +1867,9 @@ def read_depth_tracks(engine: Engine, path: str, ref_lengths: Optional[Dict[str,
             import io
             return _checked_upload(engine, depthfile.parse_depth_lines(io.BytesIO(text.tobytes())), ref_lengths)
         names, lengths, segs = found
-        targets_length = dict(zip(names, lengths))
-        if ref_lengths is not None and any(t not in ref_lengths for t in targets_length):
+        targets_length, track = _depth_file_track(engine, names, lengths, ref_lengths)
+        if track is None:
             return None, targets_length
-        if any(L > depthfile.INT32_MAX for L in lengths):
-            sys.exit("ERROR!!! A contig of the depth file is longer than 2^31 - 1 bases, which is not supported")
-        engine.set_layout(lengths)
-        track = engine.T.zeros(max(engine.total, 1), engine.T.int32, engine.device)     # (the padding behind every contig too)
         engine.depth_text_parse(d_text, d_line0, segs(engine.offsets), track)
         del d_text, d_line0
     return DepthTracks(engine, targets_length, track), targets_length

@@ -427,7 +427,7 @@ int gci_range_sums(gci_ctx* ctx, const int32_t* d_depth, const int64_t* d_ranges
 int gci_fasta_n_scan(gci_ctx* ctx, const uint8_t* d_text, uint64_t n_bytes, const int64_t* d_body, uint32_t n_records,
                      uint32_t* d_tile_kept, uint64_t* d_keys, uint32_t cap, uint32_t* d_n_keys);
 
-/* ---- depth text -> track: the parse of utility/GCI_score.py:11-39 (k_depth_parse.hip) -------------------------------------
+/* ---- depth text -> track: the parse of utility/GCI_score.py:11-39 (k_depth_parse.hip; tiles, ranks: gci_text_tiles.hpp) --
  * d_text: inflated `.depth.gz` text, ('>' name '\n' (decimal '\n')^L)*.  Tiles of 4096 bytes; a line belongs to the tile that
  * holds its first byte (offset 0 and every byte behind a '\n'; a last line without '\n' counts).  Two passes, no chain between
  * workgroups:
@@ -444,7 +444,7 @@ int gci_depth_text_index(gci_ctx* ctx, const uint8_t* d_text, uint64_t n_bytes, 
 int gci_depth_text_parse(gci_ctx* ctx, const uint8_t* d_text, uint64_t n_bytes, const uint64_t* d_tile_line0, const int64_t* d_segs,
                          uint32_t n_segs, int32_t* d_track, uint64_t track_n);
 
-/* ---- samtools depth text -> track: the line loop of utility/convert_samtools_depth.py:12-19 (k_sdepth.hip) ----------------------
+/* ---- samtools depth text -> track: the line loop of utility/convert_samtools_depth.py:12-19 (k_sdepth.hip, gci_text_tiles.hpp) --
  * d_text: the text of `samtools depth -a`, (name '\t' position '\t' depth '\n')*, 16-byte aligned.  Tiles and line ownership as
  * above.  The strict grammar: name = 1 or more bytes 0x21 .. 0x7E; position = [0-9]{1,10}; depth = 0 or [1-9][0-9]{0,9} with a
  * value <= INT32_MAX; the line closed by '\n' or the end of the text and, its '\n' included, at most 255 bytes long.

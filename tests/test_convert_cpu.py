@@ -142,6 +142,25 @@ def test_cpu_twin_matches_the_python_statement_on_random_texts(cpu_engine, seed)
     check_against_statement(cpu_engine, text)
 
 
+# More lines in a tile than text inside the grammar can have (empty lines: a byte each).  The product never parses such text --
+# the index pass reports it -- but the exports take it, and a parse that stages a tile's lines by rank must still place every one.
+CROWDED = b"x\t1\t5\n" + b"\n" * 5000 + b"".join(b"x\t%d\t%d\n" % (k, k % 1000) for k in range(600))
+CROWDED_LINES, CROWDED_BAD, CROWDED_KEYS = 5601, 6, 3
+CROWDED_WANT = np.concatenate([[5], np.zeros(5000, dtype=np.int32), np.arange(600, dtype=np.int32) % 1000]).astype(np.int32)
+
+
+def test_more_lines_in_a_tile_than_the_grammar_allows(cpu_engine):
+    assert len(CROWDED) == 10786
+    arr = np.frombuffer(CROWDED, dtype=np.uint8)
+    tiles, keys, bad = cpu_engine.sdepth_index(arr)
+    assert tiles.shape[0] == 3 and int(tiles.sum()) == CROWDED_LINES == len(lines_of(CROWDED))
+    assert bad == CROWDED_BAD == strict_bad(CROWDED) and keys.shape[0] == CROWDED_KEYS
+    cpu_engine.set_layout([CROWDED_LINES])
+    segs = np.array([[0, CROWDED_LINES, 0]], dtype=np.int64)
+    track = cpu_engine.sdepth_parse(arr, line0_of(tiles), segs, cpu_engine.new_track())
+    assert np.array_equal(cpu_engine.contig(track, 0), CROWDED_WANT)
+
+
 def test_name_changes_on_the_first_and_the_last_line_of_a_tile(cpu_engine):
     # every line 16 bytes: 256 lines fill a tile exactly, line 256 k is a tile's first and line 256 k - 1 a tile's last
     def line(name, k):

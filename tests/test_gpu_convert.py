@@ -93,6 +93,28 @@ def test_device_matches_the_cpu_twin_at_tile_edges_bounds_and_seams(engine):
     assert device_equals_twin(engine, bad_text) == strict_bad(bad_text) != NONE
 
 
+def test_device_parse_of_more_lines_in_a_tile_than_the_grammar_allows(engine):
+    """The by-rank store's overflow branch: a tile with more lines than its staging arrays hold (test_convert_cpu.CROWDED)."""
+    from gci_amd import cpu
+    from test_convert_cpu import CROWDED, CROWDED_BAD, CROWDED_KEYS, CROWDED_LINES, CROWDED_WANT
+    arr = np.frombuffer(CROWDED, dtype=np.uint8)
+    twin = cpu.CpuEngine(threads=2)
+    c_tiles, c_keys, c_bad = twin.sdepth_index(arr)
+    d_text = engine.to_device(arr)
+    d_line0, line0, keys, bad = engine.sdepth_index(d_text)
+    assert bad == c_bad == CROWDED_BAD
+    assert np.array_equal(keys, c_keys) and keys.shape[0] == CROWDED_KEYS
+    assert np.array_equal(line0, line0_of(c_tiles)) and int(line0[-1]) == CROWDED_LINES
+    engine.set_layout([CROWDED_LINES])
+    twin.set_layout([CROWDED_LINES])
+    segs = np.array([[0, CROWDED_LINES, 0]], dtype=np.int64)
+    track = engine.T.zeros(max(engine.total, 1), engine.T.int32, engine.device)
+    engine.sdepth_parse(d_text, d_line0, segs, track)
+    got = track.cpu().numpy()[:engine.total]
+    assert np.array_equal(got, twin.sdepth_parse(arr, line0, segs, twin.new_track()))
+    assert np.array_equal(twin.contig(got, 0), CROWDED_WANT)
+
+
 def test_device_key_overflow_and_retry(engine):
     text = b"".join(b"%s\t%d\t%d\n" % (b"x" if k % 2 else b"y", k, k % 9) for k in range(30_000))
     assert device_equals_twin(engine, text, cap=4) == NONE

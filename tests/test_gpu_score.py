@@ -121,6 +121,31 @@ def test_device_parse_matches_the_cpu_twin(engine, seed):
     assert np.array_equal(track.cpu().numpy()[:engine.total], want)
 
 
+def test_device_parse_of_more_lines_in_a_tile_than_the_grammar_allows(engine):
+    """The by-rank store's overflow branch: a tile with more lines than its staging arrays hold (test_score_cpu.CROWDED)."""
+    from gci_amd import cpu
+    from gci_amd.formats import depthfile
+    from test_score_cpu import CROWDED, CROWDED_BAD, CROWDED_TILES, CROWDED_WANT
+    arr = np.frombuffer(CROWDED, dtype=np.uint8)
+    twin = cpu.CpuEngine(threads=2)
+    c_tiles, c_keys, c_bad = twin.depth_text_index(arr)
+    d_text = engine.to_device(arr)
+    d_line0, line0, keys, bad = engine.depth_text_index(d_text)
+    assert bad == c_bad == CROWDED_BAD
+    assert np.array_equal(keys, c_keys) and keys.shape[0] == 2
+    assert np.diff(line0.astype(np.int64)).tolist() == c_tiles.tolist() == CROWDED_TILES
+    names, lengths, segs = depthfile.header_segments(arr, keys, line0)
+    assert list(names) == ["a", "b"] and list(lengths) == [6200, 10]
+    engine.set_layout(lengths)
+    twin.set_layout(lengths)
+    track = engine.T.zeros(max(engine.total, 1), engine.T.int32, engine.device)
+    engine.depth_text_parse(d_text, d_line0, segs(engine.offsets), track)
+    got = track.cpu().numpy()[:engine.total]
+    assert np.array_equal(got, twin.depth_text_parse(arr, line0, segs(twin.offsets), twin.new_track()))
+    for c, nm in enumerate(names):
+        assert np.array_equal(twin.contig(got, c), CROWDED_WANT[nm]), nm
+
+
 def test_device_grammar_check_reports_the_first_bad_line(engine):
     from gci_amd import cpu
     rng = np.random.default_rng(7)

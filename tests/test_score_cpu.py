@@ -128,6 +128,30 @@ def test_grammar_violation_at_every_byte_offset_is_reported_where_its_line_begin
             assert int(tiles.sum()) == len(t.split(b"\n")) - (1 if t.endswith(b"\n") else 0)
 
 
+# More lines in a tile than text inside the grammar can have (empty lines: a byte each).  The product never parses such text --
+# the index pass reports it -- but the exports take it, and a parse that stages a tile's lines by rank must still place every one.
+CROWDED = b">a\n" + b"\n" * 5000 + b"".join(b"%d\n" % (k % 1000) for k in range(1200)) + b">b\n" + b"3\n" * 10
+CROWDED_TILES = [4094, 1732, 386]
+CROWDED_BAD = 3
+CROWDED_WANT = {"a": np.concatenate([np.zeros(5000, dtype=np.int32), np.arange(1200, dtype=np.int32) % 1000]),
+                "b": np.full(10, 3, dtype=np.int32)}
+
+
+def test_more_lines_in_a_tile_than_the_grammar_allows(cpu_engine):
+    from gci_amd.formats import depthfile
+    assert len(CROWDED) == 9606
+    arr = np.frombuffer(CROWDED, dtype=np.uint8)
+    tiles, keys, bad = cpu_engine.depth_text_index(arr)
+    assert tiles.tolist() == CROWDED_TILES and bad == CROWDED_BAD == _strict_bad(CROWDED) and keys.shape[0] == 2
+    line0 = np.concatenate([[0], np.cumsum(tiles.astype(np.uint64))]).astype(np.uint64)
+    names, lengths, segs = depthfile.header_segments(arr, keys, line0)
+    assert list(names) == ["a", "b"] and list(lengths) == [6200, 10]
+    cpu_engine.set_layout(lengths)
+    track = cpu_engine.depth_text_parse(arr, line0, segs(cpu_engine.offsets), cpu_engine.new_track())
+    for c, nm in enumerate(names):
+        assert np.array_equal(cpu_engine.contig(track, c), CROWDED_WANT[nm]), nm
+
+
 def test_header_segments_send_odd_texts_to_the_slow_path():
     from gci_amd.formats import depthfile
     from gci_amd import cpu
