@@ -184,7 +184,8 @@ extern "C" int gci_route_records(gci_ctx* ctx, const gci_join_file* h_file, uint
                                  uint8_t* d_out_names, uint32_t name_slot, uint64_t* d_status)
 {
     if (name_slot < 16 || name_slot > 65536 || (name_slot & 15u)) return GCI_E_INVALID;
-    if (!ctx || !h_file || !d_out_names || (h_file->n_recs && (!h_file->d_recs || !h_file->d_name_base || !h_file->d_name_off)))
+    if (!ctx || !h_file || (cap && !d_out_names) ||                      // (cap 0: there are no name slots, the array is empty)
+        (h_file->n_recs && (!h_file->d_recs || !h_file->d_name_base || !h_file->d_name_off)))
         return GCI_E_INVALID;
     RouteSrc S;
     memset(&S, 0, sizeof S);
@@ -208,7 +209,7 @@ extern "C" int gci_route_hits(gci_ctx* ctx, const uint8_t* d_hits, uint32_t n, c
                               uint8_t* d_out_hits, uint8_t* d_out_names, uint32_t name_slot, uint64_t* d_status)
 {
     if (name_slot < 16 || name_slot > 65536 || (name_slot & 15u)) return GCI_E_INVALID;
-    if (!ctx || !d_out_names || (n && (!d_hits || !d_name_base))) return GCI_E_INVALID;
+    if (!ctx || (cap && !d_out_names) || (n && (!d_hits || !d_name_base))) return GCI_E_INVALID;
     RouteSrc S;
     memset(&S, 0, sizeof S);
     S.hits = reinterpret_cast<const gci_paf_hit*>(d_hits); S.name_base = d_name_base; S.n = n;

@@ -299,7 +299,8 @@ int gci_hash_conflicts(gci_ctx* ctx, const uint64_t* d_buckets, uint32_t n_parts
  *                       slot 0 of a bucket = {contig = -1, start = count}
  *   gci_route_seal_intervals  receiving side: contig -> d_cmap[contig] (the rank's track layout), -1 beyond the count: the
  *                       buffer of n_parts * (cap + 1) intervals goes to gci_depth_build_* as it is
- * A count beyond cap or a name longer than name_slot sets *d_status to GCI_E_CAPACITY (grow the buckets). */
+ * A count beyond cap or a name longer than name_slot sets *d_status to GCI_E_CAPACITY (grow the buckets).  With cap = 0 there
+ * are no name slots and d_out_names may be NULL (gci_route_records, gci_route_hits): the headers still get the true counts. */
 int gci_route_records(gci_ctx* ctx, const gci_join_file* h_file, uint32_t n_parts, uint32_t cap, gci_rec* d_out_recs,
                       uint8_t* d_out_names, uint32_t name_slot, uint64_t* d_status);
 int gci_route_seal_records(gci_ctx* ctx, gci_rec* d_recs, uint32_t n_parts, uint32_t cap, uint64_t* d_status);
