@@ -19,6 +19,7 @@ GCI_TILE = 4096
 GCI_MAX_JOIN_FILES = 16
 PAGE_MAX_REC, PAGE_MAX_BYTES, PAGE_BYTES_DEFAULT = 1024, 32768, 24576
 REC_PASS, REC_HQ = 1, 2
+BG_RUNS_PER_BLOCK = 256      # GCI_BG_RUNS_PER_BLOCK: runs (lines) a workgroup of the bedGraph text passes takes
 PROF_COUNT = 19
 PROF_DEPTH_SCAN = 5          # k_tile_build: the pass that writes the depth track (+ text)
 PROF_TILE_PASS1 = 13
@@ -124,6 +125,11 @@ EXPORTS = [
     ("gci_issue_scan_windows", c_int, [c_void_p, c_void_p, POINTER(Window), c_uint32, c_double, c_double, c_void_p,
                                        c_uint32, c_void_p]),
     ("gci_depth_classes", c_int, [c_void_p, c_void_p, POINTER(Window), c_uint32, c_int32, c_void_p, c_uint32, c_void_p, c_void_p]),
+    ("gci_depth_runs_count", c_int, [c_void_p, c_void_p, POINTER(Window), c_uint32, c_void_p]),
+    ("gci_depth_runs_write", c_int, [c_void_p, c_void_p, c_void_p, c_uint64]),
+    ("gci_bedgraph_size", c_int, [c_void_p, c_void_p, c_void_p, POINTER(Window), c_uint32, c_void_p, c_void_p, c_void_p]),
+    ("gci_bedgraph_write", c_int, [c_void_p, c_void_p, c_void_p, POINTER(Window), c_uint32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, c_uint64]),
     ("gci_depth_text_size", c_int, [c_void_p, c_void_p, c_void_p]),
     ("gci_depth_text_write", c_int, [c_void_p, c_void_p, c_void_p, c_uint64]),
     ("gci_depth_sum", c_int, [c_void_p, c_void_p, c_void_p]),

@@ -25,6 +25,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libgci_cpu.so")
 REC_DTYPE = np.dtype([("name_hash", "<u8"), ("contig", "<i4"), ("start", "<i4"), ("end", "<i4"), ("qlen", "<i4"),
                       ("rec_idx", "<u4"), ("mapq", "u1"), ("flags", "u1"), ("name_len", "<u2")])
 IVL_DTYPE = np.dtype([("contig", "<i4"), ("start", "<i4"), ("end", "<i4"), ("pad", "<i4")])
+RUN_DTYPE = np.dtype([("start", "<u4"), ("depth", "<i4")])          # gci_depth_run
 GCI_TILE = 4096
 
 
@@ -39,7 +40,8 @@ _SEAMS = """gci_abi_version gci_ctx_create gci_ctx_destroy gci_sync gci_strerror
 gci_memcpy_d2h gci_memset gci_layout_set gci_layout_total gci_layout_offsets gci_name_hash gci_decode_status gci_bam_filter gci_name_join
 gci_depth_build gci_gap_mask gci_max2 gci_issue_scan gci_issue_scan_windows gci_depth_classes gci_depth_text_size gci_depth_text_write
 gci_depth_sum gci_range_sums gci_depth_deflate_from_build gci_depth_deflate_size gci_depth_deflate_write gci_depth_text_index
-gci_depth_text_parse gci_sdepth_index gci_sdepth_parse gci_depth_gz_scan gci_depth_gz_runs gci_depth_gz_expand""".split()
+gci_depth_text_parse gci_sdepth_index gci_sdepth_parse gci_depth_gz_scan gci_depth_gz_runs gci_depth_gz_expand gci_depth_runs_count
+gci_depth_runs_write gci_bedgraph_size gci_bedgraph_write""".split()
 _PROTO = {name: (name, res, args) for name, res, args in _lib.EXPORTS}
 EXPORTS = [_PROTO[name] for name in _SEAMS] + [("gci_cpu_option", c_int, [c_void_p, c_char_p, c_int])]
 
@@ -242,6 +244,47 @@ class CpuEngine:
             bounds = np.searchsorted(win, np.arange(nw + 1))
             out.append([np.stack([rel[a:b:2], rel[a + 1:b:2]], axis=1) for a, b in zip(bounds[:-1], bounds[1:])])
         return out[0], out[1], stats
+
+    # ---- depth_to_bedgraph.py (k_bedgraph.hip's twins)
+    def _depth_runs(self, track: np.ndarray, w, nw: int) -> Tuple[np.ndarray, np.ndarray]:
+        run0 = np.zeros(nw + 1, dtype=np.uint64)
+        self._chk(self.lib.gci_depth_runs_count(self.ctx, _p(track), w, nw, _p(run0)), "gci_depth_runs_count")
+        runs = np.zeros(max(int(run0[nw]), 1), dtype=RUN_DTYPE)
+        self._chk(self.lib.gci_depth_runs_write(self.ctx, _p(track), _p(runs), int(run0[nw])), "gci_depth_runs_write")
+        return runs, run0
+
+    def depth_runs(self, track: np.ndarray, windows: Sequence[Tuple[int, int]]) -> Tuple[np.ndarray, np.ndarray]:
+        """device.Engine.depth_runs' twin: (RUN_DTYPE [total], uint64 [n + 1] first run of every window, then the total)."""
+        nw = len(windows)
+        w = (_Window * max(nw, 1))(*[_Window(int(a), int(b)) for a, b in windows])
+        runs, run0 = self._depth_runs(track, w, nw)
+        return runs[:int(run0[nw])], run0
+
+    def bedgraph(self, track: np.ndarray, windows: Sequence[Tuple[int, int]], names: Sequence[bytes], coord0: Sequence[int]
+                 ) -> Tuple[memoryview, np.ndarray]:
+        """device.Engine.bedgraph's twin: (the text, uint64 [n + 1] first byte of every window, then the total)."""
+        return self.bedgraph_text(self.bedgraph_runs(track, windows), names, coord0)
+
+    def bedgraph_runs(self, track: np.ndarray, windows: Sequence[Tuple[int, int]]):
+        nw = len(windows)
+        w = (_Window * max(nw, 1))(*[_Window(int(a), int(b)) for a, b in windows])
+        return (w, nw) + self._depth_runs(track, w, nw)
+
+    def bedgraph_text(self, held, names: Sequence[bytes], coord0: Sequence[int]) -> Tuple[memoryview, np.ndarray]:
+        w, nw, runs, run0 = held
+        coord = np.ascontiguousarray(coord0, dtype=np.int64)
+        name_len = np.array([len(x) for x in names], dtype=np.uint32)
+        if coord.shape[0] != nw or name_len.shape[0] != nw:
+            raise CpuError(-1, "bedgraph: one name and one coordinate per window")
+        name_off = np.zeros(max(nw, 1), dtype=np.uint64)
+        name_off[1:nw] = np.cumsum(name_len[:-1], dtype=np.uint64)
+        blob = np.frombuffer(b"".join(names) or b"\0", dtype=np.uint8)
+        byte0 = np.zeros(nw + 1, dtype=np.uint64)
+        self._chk(self.lib.gci_bedgraph_size(self.ctx, _p(runs), _p(run0), w, nw, _p(coord), _p(name_len), _p(byte0)), "gci_bedgraph_size")
+        out = np.zeros(max(int(byte0[nw]), 1), dtype=np.uint8)
+        self._chk(self.lib.gci_bedgraph_write(self.ctx, _p(runs), _p(run0), w, nw, _p(coord), _p(blob), _p(name_off), _p(name_len), _p(out),
+                                              int(byte0[nw])), "gci_bedgraph_write")
+        return memoryview(out[:int(byte0[nw])]), byte0
 
     # ---- R7, R15
     def depth_text(self, track: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:

@@ -30,6 +30,15 @@ struct gci_ctx {
     int32_t n_contigs = 0;
     std::vector<int64_t> len, off;
     int64_t total = 0;
+    // depth_to_bedgraph.py: the last gci_depth_runs_count (its clamped windows in pieces, the runs in front of every piece) and
+    // the last gci_bedgraph_size (whose text it measured)
+    struct BgPiece { int64_t begin, lo, hi; uint64_t run0; };
+    std::vector<BgPiece> bg_pieces;
+    const void* bg_track = nullptr;
+    uint64_t bg_runs_total = 0;
+    const void* bg_text_run0 = nullptr;
+    const void* bg_text_runs = nullptr;
+    uint32_t bg_text_windows = 0;
 };
 
 namespace {
@@ -236,6 +245,51 @@ uint32_t decimal_width(int32_t v)
     return w;
 }
 
+// depth_to_bedgraph.py: a window clamped to the track as the issue scan clamps it; the decimal width of a coordinate and its digits;
+// the bytes of every window's lines  name '\t' start '\t' end '\t' depth '\n'
+gci_window bg_clamp(const gci_ctx* ctx, gci_window w)
+{
+    w.begin = std::max<int64_t>(w.begin, 0);
+    w.end = std::min<int64_t>(w.end, ctx->total);
+    if (w.end < w.begin) w.end = w.begin;
+    return w;
+}
+
+uint32_t bg_width(uint64_t v)
+{
+    uint32_t w = 0;
+    do { w++; v /= 10; } while (v);
+    return w;
+}
+
+uint8_t* bg_put(uint8_t* p, uint64_t v)
+{
+    const uint32_t w = bg_width(v);
+    for (uint32_t d = w; d-- > 0;) { p[d] = (uint8_t)('0' + v % 10); v /= 10; }
+    return p + w;
+}
+
+int bg_window_bytes(gci_ctx* ctx, const gci_depth_run* runs, const uint64_t* win_run0, const gci_window* h_windows, uint32_t n_windows,
+                    const int64_t* h_coord0, const uint32_t* h_name_len, std::vector<uint64_t>& bytes)
+{
+    bytes.assign(n_windows, 0);
+    for (uint32_t w = 0; w < n_windows; w++) {
+        const gci_window c = bg_clamp(ctx, h_windows[w]);
+        if (c.end - c.begin > 0xFFFFFFFFll || h_coord0[w] < 0 || h_name_len[w] > 65535u) return GCI_E_INVALID;
+    }
+    parallel_blocks(ctx->threads, n_windows, 1, [&](uint64_t w, uint64_t) {
+        const gci_window c = bg_clamp(ctx, h_windows[w]);
+        uint64_t s = 0;
+        for (uint64_t k = win_run0[w]; k < win_run0[w + 1]; k++) {
+            const uint64_t rel_end = k + 1 < win_run0[w + 1] ? (uint64_t)runs[k + 1].start : (uint64_t)(c.end - c.begin);
+            s += h_name_len[w] + 4u + bg_width((uint64_t)h_coord0[w] + runs[k].start) + bg_width((uint64_t)h_coord0[w] + rel_end) +
+                 decimal_width(runs[k].depth);
+        }
+        bytes[w] = s;
+    });
+    return GCI_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -309,6 +363,7 @@ int gci_layout_set(gci_ctx* ctx, int32_t n_contigs, const int64_t* h_lengths)
     }
     ctx->total = at > 0 ? at : GCI_TILE;
     ctx->n_contigs = n_contigs;
+    ctx->bg_track = nullptr; ctx->bg_text_run0 = nullptr;
     return GCI_OK;
 }
 int64_t gci_layout_total(gci_ctx* ctx) { return ctx ? ctx->total : 0; }
@@ -669,6 +724,111 @@ int gci_range_sums(gci_ctx* ctx, const int32_t* depth, const int64_t* ranges, ui
             int64_t s = 0;
             for (int64_t i = ranges[2 * r]; i < ranges[2 * r + 1]; i++) s += depth[i];
             sums[r] = s;
+        }
+    });
+    return GCI_OK;
+}
+
+/* ---- depth_to_bedgraph.py: the constant-depth runs of every window, in order, and their bedGraph lines (k_bedgraph.hip's twins) ---- */
+int gci_depth_runs_count(gci_ctx* ctx, const int32_t* depth, const gci_window* h_windows, uint32_t n_windows, uint64_t* win_run0)
+{
+    if (!ctx || !depth || !win_run0 || (n_windows && !h_windows)) return GCI_E_INVALID;
+    const int st = need_layout(ctx);
+    if (st) return st;
+    if (n_windows >= (1u << 31)) return GCI_E_INVALID;
+    ctx->bg_track = nullptr;
+    std::vector<gci_ctx::BgPiece> pieces;
+    std::vector<uint64_t> first_piece((size_t)n_windows + 1);
+    for (uint32_t w = 0; w < n_windows; w++) {
+        const gci_window c = bg_clamp(ctx, h_windows[w]);
+        if (c.end - c.begin > 0xFFFFFFFFll) return GCI_E_INVALID;
+        first_piece[w] = pieces.size();
+        for (int64_t a = c.begin; a < c.end; a += (int64_t)1 << 22) pieces.push_back({c.begin, a, std::min(c.end, a + ((int64_t)1 << 22)), 0});
+    }
+    first_piece[n_windows] = pieces.size();
+    parallel_blocks(ctx->threads, pieces.size(), 1, [&](uint64_t k, uint64_t) {
+        gci_ctx::BgPiece& pc = pieces[k];
+        uint64_t n = 0;
+        for (int64_t i = pc.lo; i < pc.hi; i++) n += (i == pc.begin || depth[i] != depth[i - 1]) ? 1u : 0u;
+        pc.run0 = n;
+    });
+    uint64_t at = 0;
+    for (auto& pc : pieces) { const uint64_t n = pc.run0; pc.run0 = at; at += n; }
+    for (uint32_t w = 0; w <= n_windows; w++) win_run0[w] = first_piece[w] < pieces.size() ? pieces[first_piece[w]].run0 : at;
+    ctx->bg_pieces.swap(pieces);
+    ctx->bg_runs_total = at;
+    ctx->bg_track = depth;
+    return GCI_OK;
+}
+
+int gci_depth_runs_write(gci_ctx* ctx, const int32_t* depth, gci_depth_run* runs, uint64_t cap)
+{
+    if (!ctx || !depth || (cap && !runs)) return GCI_E_INVALID;
+    const int st = need_layout(ctx);
+    if (st) return st;
+    if (!ctx->bg_track || ctx->bg_track != depth) return GCI_E_INVALID;
+    if (cap < ctx->bg_runs_total) return GCI_E_CAPACITY;
+    parallel_blocks(ctx->threads, ctx->bg_pieces.size(), 1, [&](uint64_t k, uint64_t) {
+        const gci_ctx::BgPiece pc = ctx->bg_pieces[k];
+        uint64_t o = pc.run0;
+        for (int64_t i = pc.lo; i < pc.hi; i++)
+            if (i == pc.begin || depth[i] != depth[i - 1]) { runs[o].start = (uint32_t)(i - pc.begin); runs[o].depth = depth[i]; o++; }
+    });
+    return GCI_OK;
+}
+
+int gci_bedgraph_size(gci_ctx* ctx, const gci_depth_run* runs, const uint64_t* win_run0, const gci_window* h_windows, uint32_t n_windows,
+                      const int64_t* h_coord0, const uint32_t* h_name_len, uint64_t* win_byte0)
+{
+    if (!ctx || !win_run0 || !win_byte0 || (n_windows && (!h_windows || !h_coord0 || !h_name_len))) return GCI_E_INVALID;
+    const int st = need_layout(ctx);
+    if (st) return st;
+    if (n_windows >= (1u << 31)) return GCI_E_INVALID;
+    ctx->bg_text_run0 = nullptr;
+    if (win_run0[n_windows] && (!runs || !n_windows)) return GCI_E_INVALID;
+    std::vector<uint64_t> bytes;
+    const int r = bg_window_bytes(ctx, runs, win_run0, h_windows, n_windows, h_coord0, h_name_len, bytes);
+    if (r) return r;
+    uint64_t at = 0;
+    for (uint32_t w = 0; w < n_windows; w++) { win_byte0[w] = at; at += bytes[w]; }
+    win_byte0[n_windows] = at;
+    ctx->bg_text_run0 = win_run0;
+    ctx->bg_text_runs = runs;
+    ctx->bg_text_windows = n_windows;
+    return GCI_OK;
+}
+
+int gci_bedgraph_write(gci_ctx* ctx, const gci_depth_run* runs, const uint64_t* win_run0, const gci_window* h_windows, uint32_t n_windows,
+                       const int64_t* h_coord0, const uint8_t* names, const uint64_t* h_name_off, const uint32_t* h_name_len, uint8_t* out,
+                       uint64_t cap)
+{
+    if (!ctx || !win_run0 || (cap && !out) || (n_windows && (!h_windows || !h_coord0 || !h_name_off || !h_name_len))) return GCI_E_INVALID;
+    const int st = need_layout(ctx);
+    if (st) return st;
+    if (!ctx->bg_text_run0 || ctx->bg_text_run0 != win_run0 || ctx->bg_text_runs != runs || ctx->bg_text_windows != n_windows) return GCI_E_INVALID;
+    std::vector<uint64_t> bytes;
+    const int r = bg_window_bytes(ctx, runs, win_run0, h_windows, n_windows, h_coord0, h_name_len, bytes);
+    if (r) return r;
+    std::vector<uint64_t> at((size_t)n_windows + 1, 0);
+    for (uint32_t w = 0; w < n_windows; w++) at[w + 1] = at[w] + bytes[w];
+    if (cap < at[n_windows]) return GCI_E_CAPACITY;
+    for (uint32_t w = 0; w < n_windows; w++) if (bytes[w] && h_name_len[w] && !names) return GCI_E_INVALID;
+    parallel_blocks(ctx->threads, n_windows, 1, [&](uint64_t w, uint64_t) {
+        const gci_window c = bg_clamp(ctx, h_windows[w]);
+        uint8_t* p = out + at[w];
+        for (uint64_t k = win_run0[w]; k < win_run0[w + 1]; k++) {
+            const uint64_t rel_end = k + 1 < win_run0[w + 1] ? (uint64_t)runs[k + 1].start : (uint64_t)(c.end - c.begin);
+            memcpy(p, names + h_name_off[w], h_name_len[w]);
+            p += h_name_len[w];
+            *p++ = '\t';
+            p = bg_put(p, (uint64_t)h_coord0[w] + runs[k].start);
+            *p++ = '\t';
+            p = bg_put(p, (uint64_t)h_coord0[w] + rel_end);
+            *p++ = '\t';
+            const int32_t d = runs[k].depth;
+            if (d < 0) *p++ = '-';
+            p = bg_put(p, d < 0 ? (uint64_t)(-(int64_t)d) : (uint64_t)d);
+            *p++ = '\n';
         }
     });
     return GCI_OK;

@@ -112,6 +112,16 @@ struct gci_ctx {
     int win_flank = INT32_MIN;              // flank the cached per-contig windows were built for
     uint32_t win_n = 0;
     int64_t win_tiles = 0;
+    uint64_t win_epoch = 0;                 // counts gci_set_windows(): what a pass keeps about "the windows of the call before it"
+    // k_bedgraph.hip: runs per window tile and their scan, of the last gci_depth_runs_count; the window table, bytes per block of runs
+    // and their scan, of the last gci_bedgraph_size
+    DevBuf bg_tile_cnt, bg_tile_off, bg_blk, bg_wtab, bg_blk_bytes, bg_blk_off, bg_blk2;
+    uint64_t bg_runs_epoch = 0, bg_runs_total = 0;      // (epoch 0: no count call yet)
+    const void* bg_runs_track = nullptr;
+    const void* bg_text_runs = nullptr;                 // the size call's d_runs (nullptr: no size call yet), d_win_run0, n_windows
+    const void* bg_text_run0 = nullptr;
+    uint32_t bg_text_windows = 0;
+    uint64_t bg_text_n_runs = 0, bg_text_total = 0;
     void* h_pinned = nullptr;               // staging for small uploads
     size_t h_pinned_cap = 0;
     // optional per-kernel HIP-event timing (gci_profile_*)
@@ -501,3 +511,5 @@ __device__ __forceinline__ void text_tile(const int4 (&v)[4], int64_t valid, uin
 int gci_launch_reduce_tiles(gci_ctx* ctx, const long long* tile_sum, unsigned long long* sums);
 // contig_off[c] = tile_off[tile_first[c]] for c < n_contigs, contig_off[n_contigs] = tile_off[n_tiles]
 int gci_launch_contig_text_off(gci_ctx* ctx, const uint64_t* tile_off, uint64_t* contig_off);
+// the windows of an issue scan, clamped to the track, with their tiles: ctx->win, win_tile_first (n_win + 1 entries), win_n, win_tiles
+int gci_set_windows(gci_ctx* ctx, const gci_window* h_win, uint32_t n_win);

@@ -188,7 +188,7 @@ static int issue_scan_launch(gci_ctx* ctx, const int32_t* d_depth, uint32_t n_wi
     return GCI_OK;
 }
 
-static int set_windows(gci_ctx* ctx, const gci_window* h_win, uint32_t n_win)
+int gci_set_windows(gci_ctx* ctx, const gci_window* h_win, uint32_t n_win)
 {
     std::vector<gci_window> ws;
     std::vector<int64_t> first;
@@ -211,6 +211,7 @@ static int set_windows(gci_ctx* ctx, const gci_window* h_win, uint32_t n_win)
     GCI_TRY(gci_upload_small(ctx, ctx->win_tile_first.p, first.data(), first.size() * 8));
     ctx->win_n = n_win;
     ctx->win_tiles = tiles;
+    ctx->win_epoch++;
     return GCI_OK;
 }
 
@@ -221,7 +222,7 @@ extern "C" int gci_issue_scan_windows(gci_ctx* ctx, const int32_t* d_depth, cons
     if (!ctx || !d_depth || !d_n_keys || (cap && !d_keys) || (n_windows && !h_windows)) return GCI_E_INVALID;
     if (!ctx->n_contigs) return GCI_E_NO_LAYOUT;
     if (n_windows >= (1u << 31)) return GCI_E_INVALID;
-    GCI_TRY(set_windows(ctx, h_windows, n_windows));
+    GCI_TRY(gci_set_windows(ctx, h_windows, n_windows));
     ctx->win_flank = INT32_MIN;
     return issue_scan_launch(ctx, d_depth, n_windows, ctx->win_tiles, lo, hi, d_keys, cap, d_n_keys);
 }
@@ -241,7 +242,7 @@ extern "C" int gci_issue_scan(gci_ctx* ctx, const int32_t* d_depth, double lo, d
             ws[c].begin = ctx->off[c] + a;
             ws[c].end = ctx->off[c] + b;
         }
-        GCI_TRY(set_windows(ctx, ws.data(), (uint32_t)ctx->n_contigs));
+        GCI_TRY(gci_set_windows(ctx, ws.data(), (uint32_t)ctx->n_contigs));
         ctx->win_flank = flank;
     }
     return issue_scan_launch(ctx, d_depth, ctx->win_n, ctx->win_tiles, lo, hi, d_keys, cap, d_n_keys);
@@ -338,7 +339,7 @@ extern "C" int gci_depth_classes(gci_ctx* ctx, const int32_t* d_depth, const gci
     if (!ctx || !d_depth || !d_n_keys || (cap && !d_keys) || (n_windows && (!h_windows || !d_stats))) return GCI_E_INVALID;
     if (!ctx->n_contigs) return GCI_E_NO_LAYOUT;
     if (n_windows >= (1u << 31)) return GCI_E_INVALID;
-    GCI_TRY(set_windows(ctx, h_windows, n_windows));
+    GCI_TRY(gci_set_windows(ctx, h_windows, n_windows));
     ctx->win_flank = INT32_MIN;
     HIPCHK(hipMemsetAsync(d_n_keys, 0, 8, ctx->stream));
     if (n_windows) HIPCHK(hipMemsetAsync(d_stats, 0, (size_t)n_windows * 16, ctx->stream));

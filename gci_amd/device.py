@@ -24,6 +24,7 @@ REC_DTYPE = np.dtype([("name_hash", "<u8"), ("contig", "<i4"), ("start", "<i4"),
                       ("rec_idx", "<u4"), ("mapq", "u1"), ("flags", "u1"), ("name_len", "<u2")])
 assert REC_DTYPE.itemsize == 32
 IVL_DTYPE = np.dtype([("contig", "<i4"), ("start", "<i4"), ("end", "<i4"), ("pad", "<i4")])
+RUN_DTYPE = np.dtype([("start", "<u4"), ("depth", "<i4")])          # gci_depth_run
 
 _M64 = (1 << 64) - 1
 Buffer = Any                  # a device buffer of the engine's provider: hbm.Buf or Buffer
@@ -1072,6 +1073,75 @@ class Engine:
                                                  self._p(counts), self._p(stats)), "gci_depth_classes")
         zero, low = self._scan(call, nw, counts)
         return zero, low, stats.cpu().numpy()[:2 * nw].reshape(nw, 2)
+
+    # ---- depth_to_bedgraph.py: the constant-depth runs of windows, in order, and their bedGraph text (k_bedgraph.hip) ----
+    @staticmethod
+    def _window_array(windows: Sequence[Tuple[int, int]]):
+        arr = (Window * max(len(windows), 1))()
+        for i, (a, b) in enumerate(windows):
+            arr[i].begin, arr[i].end = int(a), int(b)
+        return arr
+
+    def _depth_runs(self, track: Buffer, arr, nw: int) -> Tuple[Buffer, Buffer, np.ndarray]:
+        """-> (the runs, the per-window run offsets) on the device and the offsets on the host; the run buffer is sized from the count
+        call and allocated after it."""
+        d_run0 = self.T.empty(nw + 1, self.T.int64, self.device)
+        self._chk(self.lib.gci_depth_runs_count(self.ctx, self._p(track), arr, nw, self._p(d_run0)), "gci_depth_runs_count")
+        run0 = d_run0.cpu().numpy().view(np.uint64)
+        total = int(run0[nw])
+        d_runs = self.T.empty(max(total, 1), self.T.int64, self.device)
+        self._chk(self.lib.gci_depth_runs_write(self.ctx, self._p(track), self._p(d_runs), total), "gci_depth_runs_write")
+        return d_runs, d_run0, run0
+
+    def depth_runs(self, track: Buffer, windows: Sequence[Tuple[int, int]]) -> Tuple[np.ndarray, np.ndarray]:
+        """The maximal runs of equal depth inside each [begin, end) window of track elements (a run never crosses a window's edge),
+        window after window and ascending inside a window -> (RUN_DTYPE [total]: start relative to the window's beginning and depth,
+        uint64 [n + 1]: every window's first run, then the total)."""
+        nw = len(windows)
+        d_runs, _, run0 = self._depth_runs(track, self._window_array(windows), nw)
+        return d_runs.cpu().numpy().view(RUN_DTYPE)[:int(run0[nw])], run0
+
+    def bedgraph(self, track: Buffer, windows: Sequence[Tuple[int, int]], names: Sequence[bytes], coord0: Sequence[int]
+                 ) -> Tuple[Any, np.ndarray]:
+        """The bedGraph lines `name\\tstart\\tend\\tdepth\\n` of every run of every window, in the windows' order: names[w] byte for
+        byte, start / end = coord0[w] + the run's bounds relative to the window's beginning (coord0[w] >= 0: the contig coordinate of
+        the window's first base) -> (the text as a memoryview of the engine's pinned staging buffer, valid until the next call that
+        uses it, uint64 [n + 1]: every window's first byte, then the total).  One round: bedgraph_runs, then bedgraph_text."""
+        return self.bedgraph_text(self.bedgraph_runs(track, windows), names, coord0)
+
+    def bedgraph_runs(self, track: Buffer, windows: Sequence[Tuple[int, int]]):
+        """First half of bedgraph(): the runs of the windows, left on the device -> what bedgraph_text takes."""
+        arr = self._window_array(windows)
+        return (arr, len(windows)) + self._depth_runs(track, arr, len(windows))
+
+    def bedgraph_text(self, held, names: Sequence[bytes], coord0: Sequence[int]) -> Tuple[Any, np.ndarray]:
+        """Second half of bedgraph(): the text of the runs bedgraph_runs left on the device; the text buffer is sized from the size
+        call and allocated after it."""
+        arr, nw, d_runs, d_run0, _ = held
+        coord = np.ascontiguousarray(coord0, dtype=np.int64)
+        name_len = np.array([len(x) for x in names], dtype=np.uint32)
+        if coord.shape[0] != nw or name_len.shape[0] != nw:
+            raise GciError(_lib.GCI_E_INVALID, "bedgraph: one name and one coordinate per window")
+        name_off = np.zeros(max(nw, 1), dtype=np.uint64)
+        name_off[1:nw] = np.cumsum(name_len[:-1], dtype=np.uint64)
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)                                   # noqa: E731
+        d_byte0 = self.T.empty(nw + 1, self.T.int64, self.device)
+        self._chk(self.lib.gci_bedgraph_size(self.ctx, self._p(d_runs), self._p(d_run0), arr, nw, vp(coord), vp(name_len),
+                                             self._p(d_byte0)), "gci_bedgraph_size")
+        byte0 = d_byte0.cpu().numpy().view(np.uint64)
+        total = int(byte0[nw])
+        if total == 0:
+            return memoryview(b""), byte0
+        d_names = self.to_device(np.frombuffer(b"".join(names) or b"\0", dtype=np.uint8))
+        out = self.T.empty(total, self.T.uint8, self.device)
+        self._chk(self.lib.gci_bedgraph_write(self.ctx, self._p(d_runs), self._p(d_run0), arr, nw, vp(coord), self._p(d_names),
+                                              vp(name_off), vp(name_len), self._p(out), total), "gci_bedgraph_write")
+        if self._members_host is None or int(self._members_host.shape[0]) < total:          # (depth_deflate's pinned staging)
+            self._members_host = self.T.pinned(max(total + (total >> 3), 1 << 20))
+        host = self._members_host[:total]
+        host.copy_(out, non_blocking=True)
+        self.sync()
+        return memoryview(host.numpy()), byte0
 
     # ---- R7 ----------------------------------------------------------------------------------
     def depth_text(self, track: Buffer, out: Optional[Buffer] = None) -> Tuple[Buffer, np.ndarray]:

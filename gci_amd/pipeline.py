@@ -1967,3 +1967,38 @@ def convert_samtools_depth(engine: Optional[Engine], path: str, prefix: str) -> 
             depthfile.convert_samtools_host(path, out)
     phases.note("convert_samtools_depth_path", taken)
     return taken
+
+
+# ==============================================================================================
+# depth_to_bedgraph.py: a track in HBM as bedGraph lines (k_bedgraph.hip)
+# ==============================================================================================
+
+def depth_bedgraph(tracks: DepthTracks, items: Optional[Sequence[Tuple[str, int, int]]] = None, out=None):
+    """The bedGraph text of `tracks`: per (target, start, end) of `items` -- end EXCLUSIVE, 0 <= start <= end <= length; None: every
+    contig whole, in the track's order --, in the order given, one line `name\\tstart\\tend\\tdepth\\n` per maximal run of equal depth
+    inside [start, end), ascending, in 0-based half-open contig coordinates.  A run never crosses an item's edge, an empty item gives
+    no line, zero-depth runs are written like any other; no `track` line, no header.  One device round (Engine.bedgraph_runs, then
+    Engine.bedgraph_text).  The text goes to the open binary file `out`, or comes back as bytes."""
+    tracks._bind()
+    if items is None:
+        items = [(t, 0, L) for t, L in zip(tracks.targets, tracks.lengths)]
+    at = {t: (int(o), int(L)) for t, o, L in zip(tracks.targets, tracks.engine.offsets, tracks.lengths)}
+    wins, names, coord0 = [], [], []
+    for target, start, end in items:
+        o, L = at[target]
+        start, end = int(start), int(end)
+        if not 0 <= start <= end <= L:
+            raise ValueError(f"depth_bedgraph: [{start}, {end}) is not inside {target} (length {L})")
+        wins.append((o + start, o + end))
+        names.append(target.encode())
+        coord0.append(start)
+    with phases.wall("bedgraph_runs"):
+        held = tracks.engine.bedgraph_runs(tracks.track, wins)
+    with phases.wall("bedgraph_text"):
+        text, _ = tracks.engine.bedgraph_text(held, names, coord0)
+    del held
+    if out is None:
+        return bytes(text)
+    with phases.wall("bedgraph_write_file"):
+        out.write(text)
+    return None

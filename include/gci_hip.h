@@ -17,6 +17,7 @@
  *   gci_range_sums      sliding_window_average_depth  GCI.py:660-705 (window sums)
  *   gci_depth_classes   analyze_depth_regions         utility/depth_plotter_v2.py (zero / low runs, non-zero statistics)
  *   gci_fasta_n_scan    get_Ns_ref                    GCI.py:27-35
+ *   gci_depth_runs_*, gci_bedgraph_*   depth_to_bedgraph.py: a track as bedGraph lines (no counterpart in the reference)
  *   gci_paf_filter_device   filter(), PAF path        GCI.py:211-254  (+ helpers 49-61, 64-96)
  *
  * Conventions
@@ -379,6 +380,34 @@ int gci_issue_scan_windows(gci_ctx* ctx, const int32_t* d_depth, const gci_windo
  * d_stats: n_windows x 2 int64, zeroed by the call: the sum of the depths > 0 and the number of bases with depth > 0. */
 int gci_depth_classes(gci_ctx* ctx, const int32_t* d_depth, const gci_window* h_windows, uint32_t n_windows, int32_t low_below,
                       uint64_t* d_keys, uint32_t cap, uint32_t* d_n_keys, int64_t* d_stats);
+
+/* ---- depth_to_bedgraph.py: the constant-depth runs of a set of windows, in order, and their bedGraph text (k_bedgraph.hip) ------
+ * Element p of window [B, E) starts a run iff p == B or depth[p] != depth[p - 1]: a run never crosses a window's edge.  Windows are
+ * clamped to the track as gci_issue_scan_windows clamps them; a window of more than 2^32 - 1 elements is GCI_E_INVALID.
+ *   gci_depth_runs_count  d_win_run0[w] = index of window w's first run among the runs of all windows (window after window,
+ *                         ascending inside a window), d_win_run0[n_windows] = the total.  Synchronises.
+ *   gci_depth_runs_write  the runs of the windows of the count call in front of it on this context (same track, nothing between
+ *                         the two that sets windows: else GCI_E_INVALID) to d_runs[0 .. total): start relative to the window's
+ *                         beginning, and the depth.  cap < total: GCI_E_CAPACITY, nothing is written.
+ * The text: per run one line  name '\t' start '\t' end '\t' depth '\n'  with start = h_coord0[w] + run start, end = h_coord0[w] +
+ * the next run's start (the window's length behind its last run), both decimal without sign (h_coord0 >= 0), the depth a signed
+ * decimal, the name h_name_len[w] (<= 65535) bytes at d_names + h_name_off[w].  A block of GCI_BG_RUNS_PER_BLOCK consecutive runs
+ * is one workgroup's.
+ *   gci_bedgraph_size     d_win_byte0[w] = byte offset of window w's first line, d_win_byte0[n_windows] = total bytes.  Synchronises.
+ *   gci_bedgraph_write    the text of the size call in front of it on this context (same d_runs, d_win_run0 and n_windows: else
+ *                         GCI_E_INVALID) to d_out[0 .. total).  cap < total: GCI_E_CAPACITY, nothing is written. */
+#define GCI_BG_RUNS_PER_BLOCK 256
+typedef struct gci_depth_run {
+    uint32_t start;
+    int32_t depth;
+} gci_depth_run;
+int gci_depth_runs_count(gci_ctx* ctx, const int32_t* d_depth, const gci_window* h_windows, uint32_t n_windows, uint64_t* d_win_run0);
+int gci_depth_runs_write(gci_ctx* ctx, const int32_t* d_depth, gci_depth_run* d_runs, uint64_t cap);
+int gci_bedgraph_size(gci_ctx* ctx, const gci_depth_run* d_runs, const uint64_t* d_win_run0, const gci_window* h_windows,
+                      uint32_t n_windows, const int64_t* h_coord0, const uint32_t* h_name_len, uint64_t* d_win_byte0);
+int gci_bedgraph_write(gci_ctx* ctx, const gci_depth_run* d_runs, const uint64_t* d_win_run0, const gci_window* h_windows,
+                       uint32_t n_windows, const int64_t* h_coord0, const uint8_t* d_names, const uint64_t* h_name_off,
+                       const uint32_t* h_name_len, uint8_t* d_out, uint64_t cap);
 
 /* ---- R7: depth text -------------------------------------------------------------------------
  * size: d_contig_off[c] = byte offset of contig c's lines in the text, d_contig_off[n_contigs] =
