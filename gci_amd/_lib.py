@@ -20,6 +20,9 @@ GCI_MAX_JOIN_FILES = 16
 PAGE_MAX_REC, PAGE_MAX_BYTES, PAGE_BYTES_DEFAULT = 1024, 32768, 24576
 REC_PASS, REC_HQ = 1, 2
 BG_RUNS_PER_BLOCK = 256      # GCI_BG_RUNS_PER_BLOCK: runs (lines) a workgroup of the bedGraph text passes takes
+HIST_MAX_BINS = 65536         # GCI_HIST_MAX_BINS: the largest n_bins of gci_depth_hist
+HIST_CHUNK_TILES = 64         # GCI_HIST_CHUNK_TILES: tiles of one window a workgroup of k_depth_hist accumulates before it flushes
+HIST_LDS_BINS = 4096          # GCI_HIST_LDS_BINS (k_hist.hip): the bins a workgroup keeps in LDS; those above go to global memory per run
 PROF_COUNT = 19
 PROF_DEPTH_SCAN = 5          # k_tile_build: the pass that writes the depth track (+ text)
 PROF_TILE_PASS1 = 13
@@ -125,6 +128,7 @@ EXPORTS = [
     ("gci_issue_scan_windows", c_int, [c_void_p, c_void_p, POINTER(Window), c_uint32, c_double, c_double, c_void_p,
                                        c_uint32, c_void_p]),
     ("gci_depth_classes", c_int, [c_void_p, c_void_p, POINTER(Window), c_uint32, c_int32, c_void_p, c_uint32, c_void_p, c_void_p]),
+    ("gci_depth_hist", c_int, [c_void_p, c_void_p, POINTER(Window), c_uint32, c_uint32, c_void_p, c_void_p]),
     ("gci_depth_runs_count", c_int, [c_void_p, c_void_p, POINTER(Window), c_uint32, c_void_p]),
     ("gci_depth_runs_write", c_int, [c_void_p, c_void_p, c_void_p, c_uint64]),
     ("gci_bedgraph_size", c_int, [c_void_p, c_void_p, c_void_p, POINTER(Window), c_uint32, c_void_p, c_void_p, c_void_p]),

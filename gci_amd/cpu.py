@@ -41,7 +41,7 @@ gci_memcpy_d2h gci_memset gci_layout_set gci_layout_total gci_layout_offsets gci
 gci_depth_build gci_gap_mask gci_max2 gci_issue_scan gci_issue_scan_windows gci_depth_classes gci_depth_text_size gci_depth_text_write
 gci_depth_sum gci_range_sums gci_depth_deflate_from_build gci_depth_deflate_size gci_depth_deflate_write gci_depth_text_index
 gci_depth_text_parse gci_sdepth_index gci_sdepth_parse gci_depth_gz_scan gci_depth_gz_runs gci_depth_gz_expand gci_depth_runs_count
-gci_depth_runs_write gci_bedgraph_size gci_bedgraph_write""".split()
+gci_depth_runs_write gci_bedgraph_size gci_bedgraph_write gci_depth_hist""".split()
 _PROTO = {name: (name, res, args) for name, res, args in _lib.EXPORTS}
 EXPORTS = [_PROTO[name] for name in _SEAMS] + [("gci_cpu_option", c_int, [c_void_p, c_char_p, c_int])]
 
@@ -285,6 +285,18 @@ class CpuEngine:
         self._chk(self.lib.gci_bedgraph_write(self.ctx, _p(runs), _p(run0), w, nw, _p(coord), _p(blob), _p(name_off), _p(name_len), _p(out),
                                               int(byte0[nw])), "gci_bedgraph_write")
         return memoryview(out[:int(byte0[nw])]), byte0
+
+    # ---- depth_dist.py (k_hist.hip's twin)
+    HIST_LDS_BINS = _lib.HIST_LDS_BINS
+
+    def depth_hist(self, track: np.ndarray, windows: Sequence[Tuple[int, int]], n_bins: int) -> Tuple[np.ndarray, np.ndarray]:
+        """device.Engine.depth_hist's twin: (uint64 [n, n_bins + 2], int64 [n, 4] of sum, min, max, elements)."""
+        nw, n_bins = len(windows), int(n_bins)
+        w = (_Window * max(nw, 1))(*[_Window(int(a), int(b)) for a, b in windows])
+        hist = np.zeros((nw, n_bins + 2), dtype=np.uint64)
+        stats = np.zeros((nw, 4), dtype=np.int64)
+        self._chk(self.lib.gci_depth_hist(self.ctx, _p(track), w, nw, n_bins, _p(hist), _p(stats)), "gci_depth_hist")
+        return hist, stats
 
     # ---- R7, R15
     def depth_text(self, track: np.ndarray) -> Tuple[np.ndarray, np.ndarray]:

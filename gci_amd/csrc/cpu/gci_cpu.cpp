@@ -729,6 +729,43 @@ int gci_range_sums(gci_ctx* ctx, const int32_t* depth, const int64_t* ranges, ui
     return GCI_OK;
 }
 
+/* ---- depth_dist.py: the depth histogram and the sum / min / max / count of every window (k_depth_hist's twin) ------------------------ */
+int gci_depth_hist(gci_ctx* ctx, const int32_t* depth, const gci_window* h_windows, uint32_t n_windows, uint32_t n_bins, uint64_t* hist,
+                   int64_t* stats)
+{
+    if (!ctx || !depth || (n_windows && (!h_windows || !stats || (n_bins && !hist)))) return GCI_E_INVALID;
+    if (n_bins > GCI_HIST_MAX_BINS) return GCI_E_INVALID;
+    const int st = need_layout(ctx);
+    if (st) return st;
+    if (n_windows >= (1u << 31)) return GCI_E_INVALID;
+    const size_t cols = (size_t)n_bins + 2;
+    if (hist) memset(hist, 0, (size_t)n_windows * cols * 8);
+    // the windows clamped to the track, in pieces of 4 M elements; a piece counts into a histogram of its own and adds it once
+    struct Piece { uint32_t w; int64_t lo, hi; };
+    std::vector<Piece> pieces;
+    for (uint32_t w = 0; w < n_windows; w++) {
+        const gci_window c = bg_clamp(ctx, h_windows[w]);
+        stats[4 * (size_t)w] = 0; stats[4 * (size_t)w + 1] = INT32_MAX; stats[4 * (size_t)w + 2] = INT32_MIN; stats[4 * (size_t)w + 3] = c.end - c.begin;
+        for (int64_t a = c.begin; a < c.end; a += (int64_t)1 << 22) pieces.push_back({w, a, std::min(c.end, a + ((int64_t)1 << 22))});
+    }
+    parallel_blocks(ctx->threads, pieces.size(), 1, [&](uint64_t k, uint64_t) {
+        const Piece pc = pieces[k];
+        std::vector<uint64_t> h(hist ? cols : 0);
+        int64_t sum = 0, lo = INT32_MAX, hi = INT32_MIN;
+        for (int64_t i = pc.lo; i < pc.hi; i++) {
+            const int32_t d = depth[i];
+            sum += d; lo = std::min<int64_t>(lo, d); hi = std::max<int64_t>(hi, d);
+            if (hist) h[d < 0 ? (size_t)n_bins + 1 : (uint32_t)d >= n_bins ? (size_t)n_bins : (size_t)d]++;
+        }
+        int64_t* s = stats + 4 * (size_t)pc.w;
+        __atomic_fetch_add(s, sum, __ATOMIC_RELAXED);
+        for (int64_t seen = __atomic_load_n(s + 1, __ATOMIC_RELAXED); lo < seen && !__atomic_compare_exchange_n(s + 1, &seen, lo, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED);) {}
+        for (int64_t seen = __atomic_load_n(s + 2, __ATOMIC_RELAXED); hi > seen && !__atomic_compare_exchange_n(s + 2, &seen, hi, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED);) {}
+        for (size_t b = 0; b < h.size(); b++) if (h[b]) __atomic_fetch_add(hist + (size_t)pc.w * cols + b, h[b], __ATOMIC_RELAXED);
+    });
+    return GCI_OK;
+}
+
 /* ---- depth_to_bedgraph.py: the constant-depth runs of every window, in order, and their bedGraph lines (k_bedgraph.hip's twins) ---- */
 int gci_depth_runs_count(gci_ctx* ctx, const int32_t* depth, const gci_window* h_windows, uint32_t n_windows, uint64_t* win_run0)
 {

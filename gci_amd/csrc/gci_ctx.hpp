@@ -122,6 +122,7 @@ struct gci_ctx {
     const void* bg_text_run0 = nullptr;
     uint32_t bg_text_windows = 0;
     uint64_t bg_text_n_runs = 0, bg_text_total = 0;
+    DevBuf hist_chunk_first;                // k_hist.hip: the first chunk (workgroup) of every window of the last gci_depth_hist
     void* h_pinned = nullptr;               // staging for small uploads
     size_t h_pinned_cap = 0;
     // optional per-kernel HIP-event timing (gci_profile_*)

@@ -1143,6 +1143,22 @@ class Engine:
         self.sync()
         return memoryview(host.numpy()), byte0
 
+    # ---- depth_dist.py: the depth histogram and the sum / min / max / count of windows, one read (k_hist.hip) ----
+    HIST_LDS_BINS = _lib.HIST_LDS_BINS               # bins a workgroup of k_depth_hist keeps in LDS (GCI_HIST_LDS_BINS)
+
+    def depth_hist(self, track: Buffer, windows: Sequence[Tuple[int, int]], n_bins: int) -> Tuple[np.ndarray, np.ndarray]:
+        """gci_depth_hist over [begin, end) windows of track elements -> (uint64 [n, n_bins + 2]: per window the elements with depth
+        == b in column b, with depth >= n_bins in column n_bins, with depth < 0 in column n_bins + 1; int64 [n, 4]: sum, min, max,
+        elements -- 0, INT32_MAX, INT32_MIN, 0 for an empty window).  n_bins == 0: the statistics and over / under alone."""
+        nw, n_bins = len(windows), int(n_bins)
+        cols = n_bins + 2
+        d_hist = self.T.empty(max(nw * cols, 1), self.T.int64, self.device)
+        d_stats = self.T.empty(max(4 * nw, 1), self.T.int64, self.device)
+        self._chk(self.lib.gci_depth_hist(self.ctx, self._p(track), self._window_array(windows), nw, n_bins, self._p(d_hist),
+                                          self._p(d_stats)), "gci_depth_hist")
+        hist = d_hist.cpu().numpy().view(np.uint64)[:nw * cols].reshape(nw, cols)
+        return hist, d_stats.cpu().numpy()[:4 * nw].reshape(nw, 4)
+
     # ---- R7 ----------------------------------------------------------------------------------
     def depth_text(self, track: Buffer, out: Optional[Buffer] = None) -> Tuple[Buffer, np.ndarray]:
         """-> (uint8 text of all contigs back to back, int64 [n_contigs + 1] byte offsets)."""

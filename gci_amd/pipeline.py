@@ -2002,3 +2002,48 @@ def depth_bedgraph(tracks: DepthTracks, items: Optional[Sequence[Tuple[str, int,
     with phases.wall("bedgraph_write_file"):
         out.write(text)
     return None
+
+
+# ==============================================================================================
+# depth_dist.py: the depth histogram and the statistics of a track in HBM (k_hist.hip)
+# ==============================================================================================
+
+DIST_HIST_BUDGET = 256 << 20          # bytes of histogram (items x (n_bins + 2) x 8) one device round may hold; more items: more rounds
+
+
+def _dist_batches(n_items: int, cols: int):
+    per = max(1, DIST_HIST_BUDGET // (cols * 8))
+    return [(a, min(n_items, a + per)) for a in range(0, n_items, per)]
+
+
+def depth_distribution(tracks: DepthTracks, items: Optional[Sequence[Tuple[str, int, int]]] = None, max_depth: int = 65535
+                       ) -> Tuple[np.ndarray, np.ndarray]:
+    """The depth distribution of `tracks` per (target, start, end) of `items` -- as in depth_bedgraph: end EXCLUSIVE, None: every contig
+    whole -> (hist uint64 [n, n_bins + 2], stats int64 [n, 4]) as Engine.depth_hist gives them: column d < n_bins the bases of depth d,
+    column n_bins those of depth >= n_bins, column n_bins + 1 those of depth < 0; sum, min, max, bases.  Two device rounds: a
+    statistics-only one for the largest depth, then the histogram with n_bins = min(largest max + 1, max_depth + 1) (1 if every item
+    is empty).  A round's items go in batches whose histogram stays under DIST_HIST_BUDGET bytes.  No formatting here."""
+    if not 0 <= int(max_depth) < _lib.HIST_MAX_BINS:
+        raise ValueError(f"depth_distribution: max_depth {max_depth} is not in [0, {_lib.HIST_MAX_BINS - 1}]")
+    tracks._bind()
+    if items is None:
+        items = [(t, 0, L) for t, L in zip(tracks.targets, tracks.lengths)]
+    at = {t: (int(o), int(L)) for t, o, L in zip(tracks.targets, tracks.engine.offsets, tracks.lengths)}
+    wins = []
+    for target, start, end in items:
+        o, L = at[target]
+        start, end = int(start), int(end)
+        if not 0 <= start <= end <= L:
+            raise ValueError(f"depth_distribution: [{start}, {end}) is not inside {target} (length {L})")
+        wins.append((o + start, o + end))
+    n = len(wins)
+    with phases.wall("dist_stats"):
+        stats = [tracks.engine.depth_hist(tracks.track, wins[a:b], 0)[1] for a, b in _dist_batches(n, 2)]
+    stats = np.concatenate(stats) if stats else np.zeros((0, 4), dtype=np.int64)
+    full = stats[:, 3] > 0
+    n_bins = max(1, min(int(stats[full, 2].max()) + 1, int(max_depth) + 1)) if full.any() else 1
+    with phases.wall("dist_hist"):
+        parts = [tracks.engine.depth_hist(tracks.track, wins[a:b], n_bins) for a, b in _dist_batches(n, n_bins + 2)]
+    if not parts:
+        return np.zeros((0, n_bins + 2), dtype=np.uint64), stats
+    return np.concatenate([h for h, _ in parts]), np.concatenate([s for _, s in parts])

@@ -18,6 +18,7 @@
  *   gci_depth_classes   analyze_depth_regions         utility/depth_plotter_v2.py (zero / low runs, non-zero statistics)
  *   gci_fasta_n_scan    get_Ns_ref                    GCI.py:27-35
  *   gci_depth_runs_*, gci_bedgraph_*   depth_to_bedgraph.py: a track as bedGraph lines (no counterpart in the reference)
+ *   gci_depth_hist      depth_dist.py: the depth histogram, sum, min, max and count of windows (no counterpart in the reference)
  *   gci_paf_filter_device   filter(), PAF path        GCI.py:211-254  (+ helpers 49-61, 64-96)
  *
  * Conventions
@@ -408,6 +409,23 @@ int gci_bedgraph_size(gci_ctx* ctx, const gci_depth_run* d_runs, const uint64_t*
 int gci_bedgraph_write(gci_ctx* ctx, const gci_depth_run* d_runs, const uint64_t* d_win_run0, const gci_window* h_windows,
                        uint32_t n_windows, const int64_t* h_coord0, const uint8_t* d_names, const uint64_t* h_name_off,
                        const uint32_t* h_name_len, uint8_t* d_out, uint64_t cap);
+
+/* ---- depth_dist.py: the depth histogram and the sum / min / max / count of a set of windows, in one read (k_hist.hip) -------------
+ * Windows are [begin, end) in track elements, clamped to the track as gci_issue_scan_windows clamps them; they may overlap, repeat,
+ * share a tile or be empty.
+ *   d_stats  n_windows x 4 int64, initialised by the call: the sum of the depths, the minimum, the maximum and the number of
+ *            elements of the clamped window; an empty window gives 0, INT32_MAX, INT32_MIN, 0.
+ *   d_hist   n_windows x (n_bins + 2) uint64, zeroed by the call: column b < n_bins counts the elements with depth == b, column
+ *            n_bins ("over") those with depth >= n_bins, column n_bins + 1 ("under") those with depth < 0: every element of a window
+ *            lands in exactly one column.
+ * n_bins == 0 is a statistics-only pass: d_hist holds over / under only and may be NULL (nothing is counted then).  n_bins >
+ * GCI_HIST_MAX_BINS, a NULL d_hist with n_bins > 0 and windows, a NULL d_stats with windows: GCI_E_INVALID; a refused call writes
+ * nothing.  All results are integers and exact.  A workgroup accumulates GCI_HIST_CHUNK_TILES consecutive 4096-element tiles of ONE
+ * window in LDS before it adds its non-zero bins to d_hist. */
+#define GCI_HIST_MAX_BINS 65536
+#define GCI_HIST_CHUNK_TILES 64
+int gci_depth_hist(gci_ctx* ctx, const int32_t* d_depth, const gci_window* h_windows, uint32_t n_windows, uint32_t n_bins,
+                   uint64_t* d_hist, int64_t* d_stats);
 
 /* ---- R7: depth text -------------------------------------------------------------------------
  * size: d_contig_off[c] = byte offset of contig c's lines in the text, d_contig_off[n_contigs] =
