@@ -1,5 +1,5 @@
-// k_inflate.hip -- N1 on the GPU: BGZF members inflated by the device and the BAM record walk without its serial chain
-// (what pysam / htslib do for the reference at GCI.py:150-151).
+// k_inflate.hip -- N1 on the GPU: BGZF members inflated by the device (what pysam / htslib do for the reference at
+// GCI.py:150-151; the record walk over the inflated stream is k_records.hip).
 //
 // gci_bgzf_inflate_device.  DEFLATE is a serial bit stream: the parallelism of a BGZF file is ACROSS its members (gzip
 // members of at most 64 KiB, RFC 1951 / 1952: 56 k for a chr19 40x HiFi file, millions for a genome).  A first version gave
@@ -18,35 +18,16 @@
 // them (L = 8: 14 workgroups).  Stored, fixed and dynamic blocks.  Every member's output length is checked here, its CRC-32
 // by k_bgzf_crc: one wave per member over the finished output, every lane the CRC register of its share, the shares
 // concatenated with the GF(2) rule crc(A||B) = crc(A) * x^(8|B|) + crc(B) (as htslib verifies every block).
-//
-// gci_bam_record_offsets_device: the offsets of the records of an inflated BAM stream WITHOUT walking the block_size
-// chain serially (137 k dependent loads of ~1 us each at chr19): every byte position is tested for "a record could
-// start here" (block_size, refID, pos, l_read_name, l_seq, next_refID, next_pos consistent with the format -- SEQ / QUAL
-// bytes never pass), each candidate's successor (offset + 4 + block_size) is looked up among the candidates, and the
-// candidates reachable from the first record are found by pointer doubling.  The chain must end exactly at the end of
-// the stream (or, for a chunk, in a record that runs past it); otherwise -- a record the strict test rejects -- the call
-// reports GCI_E_MALFORMED and the caller takes the host path.
-#include "gci_ctx.hpp"
+#include "gci_crc_gf2.hpp"
+#include "gci_deflate_codes.hpp"
 #include <stdlib.h>
 
 namespace {
 
+using namespace deflate_codes;
+
 #define LIT_BITS 8
 
-__constant__ uint8_t c_clen_order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
-
-constexpr uint32_t CRC_POLY = 0xEDB88320u;      // reflected: bit 31 holds x^0
-
-constexpr uint32_t gf_mul_c(uint32_t a, uint32_t b)
-{
-    uint32_t r = 0;
-    for (int i = 0; i < 32; i++) {
-        r ^= (a & 0x80000000u) ? b : 0u;
-        a <<= 1;
-        b = (b >> 1) ^ ((b & 1u) ? CRC_POLY : 0u);
-    }
-    return r;
-}
 struct XPow8 { uint32_t v[32]; };
 constexpr XPow8 make_xpow8()                       // v[k] = x^(8 * 2^k) mod P, reflected (x^8 = 0x00800000)
 {
@@ -56,27 +37,6 @@ constexpr XPow8 make_xpow8()                       // v[k] = x^(8 * 2^k) mod P, 
     return t;
 }
 __constant__ XPow8 c_xpow8 = make_xpow8();
-
-__device__ __forceinline__ uint32_t gf_mul(uint32_t a, uint32_t b)   // a * b mod P over GF(2), reflected representation
-{
-    uint32_t r = 0;
-    for (int i = 0; i < 32; i++) {
-        r ^= (a & 0x80000000u) ? b : 0u;
-        a <<= 1;
-        b = (b >> 1) ^ ((b & 1u) ? CRC_POLY : 0u);
-    }
-    return r;
-}
-
-// Canonical Huffman code of one alphabet (RFC 1951 3.2.2), without a loop over the code lengths: with c = the next 15 bits
-// read as a code (first bit highest), the codes of length l are exactly limit[l-1] <= c < limit[l], limit[l] = (first code
-// of length l + their number) << (15 - l) -- non-decreasing in l -- so the length is 1 + the number of limits <= c (16: no
-// such code), and the symbol is sorted[off[l] + (c >> (15 - l))], off[l] = index of the first symbol of length l in
-// `sorted` - its code.  next[l]: one past the last symbol of length l in `sorted`.
-// The literal / length alphabet also has a primary table indexed by the next LIT_BITS bits of the stream (codes are packed
-// from their most significant bit, i.e. bit reversed in the LSB-first bit buffer): entry = symbol | length << 9, 0 = the
-// code is longer (or unused).
-struct alignas(16) Canon { uint16_t limit[16]; int16_t off[16]; uint16_t next[16]; };
 
 // What one member's decoder keeps in LDS: 1.3 KB, which is what bounds the members a CU decodes at a time.  The code
 // lengths of a block are only needed until its codes are built and share the primary table's space.
@@ -93,56 +53,6 @@ struct alignas(16) LaneTabs {
     Canon lit_cn, dist_cn;
 };
 static_assert(sizeof(uint16_t) << LIT_BITS >= 352, "the code lengths must fit under the primary table");
-
-__device__ __forceinline__ uint32_t bit_reverse(uint32_t v, int n) { return __brev(v) >> (32 - n); }
-
-// lens[0 .. n) -> limits, offsets and the symbols sorted by code; false: a set zlib (and with it htslib) refuses -- an
-// over-subscribed one always; an incomplete one (code space `left` over) unless `incomplete` allows it: CODE_COMPLETE never (the
-// code-length code), CODE_ONE when the set has no code at all or exactly one code of length 1 (the lit/len and distance codes of a
-// dynamic block), CODE_ANY always (the fixed distance code: 30 codes of 5 bits)
-enum { CODE_COMPLETE = 0, CODE_ONE = 1, CODE_ANY = 2 };
-template <typename SortedPtr>
-__device__ bool build_code(const uint8_t* lens, int n, Canon& cn, SortedPtr sorted, int incomplete)
-{
-    for (int l = 0; l < 16; l++) cn.next[l] = 0;
-    for (int i = 0; i < n; i++) cn.next[lens[i]]++;
-    uint32_t code = 0, idx = 0, left = 1u << 15, prev = 0;
-    bool ok = true;
-    cn.limit[0] = 0; cn.off[0] = 0; cn.next[0] = 0;
-    for (int l = 1; l < 16; l++) {
-        const uint32_t cnt = cn.next[l];
-        code = (code + prev) << 1;
-        cn.limit[l] = (uint16_t)((code + cnt) << (15 - l));
-        cn.off[l] = (int16_t)((int)idx - (int)code);
-        cn.next[l] = (uint16_t)idx;
-        idx += cnt; prev = cnt;
-        const uint32_t need = cnt << (15 - l);                           // sum count[l] * 2^(15 - l) must not exceed 2^15
-        if (need > left) ok = false; else left -= need;
-    }
-    if (!ok) return false;
-    if (left && incomplete != CODE_ANY && !(incomplete == CODE_ONE && (idx == 0u || (idx == 1u && left == 1u << 14)))) return false;
-    for (int s = 0; s < n; s++) {
-        const int l = lens[s];
-        if (l) sorted[cn.next[l]++] = (uint16_t)s;
-    }
-    return true;
-}
-
-// the primary table of the codes of at most LIT_BITS bits, from the sorted symbols (the code lengths are gone by now)
-template <int BITS, typename SortedPtr>
-__device__ void build_table(const Canon& cn, SortedPtr sorted, uint16_t* table)
-{
-    for (int i = 0; i < (1 << BITS); i++) table[i] = 0;
-    uint32_t idx = 0;
-    for (int l = 1; l <= BITS; l++) {
-        const uint32_t end = cn.next[l];
-        const int off = cn.off[l];
-        for (; idx < end; idx++) {
-            const uint32_t e = (uint32_t)sorted[idx] | ((uint32_t)l << 9);
-            for (uint32_t k = bit_reverse((uint32_t)((int)idx - off), l); k < (1u << BITS); k += 1u << l) table[k] = (uint16_t)e;
-        }
-    }
-}
 
 // The compressed bytes arrive as naturally aligned 16-byte loads, one block AHEAD of the one being consumed (the load
 // issued when a block is taken up is needed 16 payload bytes later), and move into the bit buffer a dword at a time.
@@ -193,28 +103,18 @@ __device__ __forceinline__ uint32_t take(Bits& B, int n)
     return v;
 }
 
-// one symbol: the primary table (PRIMARY > 0), else the limits of the lengths PRIMARY + 1 .. MAXL (16-byte LDS reads)
+// one symbol: the primary table (PRIMARY > 0), else the search over the limits of the lengths PRIMARY + 1 .. MAXL
 template <int PRIMARY, int MAXL, typename SortedPtr>
 __device__ __forceinline__ int decode(Bits& B, const uint16_t* table, const Canon& cn, SortedPtr sorted)
 {
     if (PRIMARY) {
         const uint32_t e = table[(uint32_t)B.bb & ((1u << PRIMARY) - 1u)];
-        if (e) { const int l = (int)(e >> 9); B.bb >>= l; B.bn -= l; return (int)(e & 0x1FFu); }
+        if (e) { const int l = (int)entry_len(e); B.bb >>= l; B.bn -= l; return (int)entry_sym(e); }
     }
-    uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (PRIMARY + 1 < 8) { const uint4 v = *reinterpret_cast<const uint4*>(&cn.limit[0]); w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w; }
-    if (MAXL >= 8) { const uint4 v = *reinterpret_cast<const uint4*>(&cn.limit[8]); w[4] = v.x; w[5] = v.y; w[6] = v.z; w[7] = v.w; }
-    const uint32_t c = __brev((uint32_t)B.bb) >> 17;
-    // the length = the number of limits <= c among limit[0 .. 15] (limit[0] = 0 is the "1 +"; the limits of the lengths the primary
-    // table covers are <= c for a code that is not in it, and a word that was not loaded is 0: counted as it should be).  Two limits
-    // per word: with c < 2^15 and limit <= 2^15, (c + 2^15) - limit has bit 15 set iff c >= limit and never borrows from the half
-    // above it -- one subtraction, one AND and one population count per pair instead of two compares and their bookkeeping.
-    const uint32_t c2 = (c | (c << 16)) + 0x80008000u;
-    int l = 0;
-#pragma unroll
-    for (int k = 0; k < (MAXL >= 8 ? 8 : 4); k++) l += __builtin_popcount((c2 - w[k]) & 0x80008000u);
+    uint32_t c;
+    const int l = code_length<PRIMARY, MAXL>((uint32_t)B.bb, cn, c);
     if (l > MAXL) return -1;
-    const int at = (int)cn.off[l] + (int)(c >> (15 - l));
+    const int at = code_index(c, l, cn);
     B.bb >>= l; B.bn -= l;
     return (int)sorted[at];
 }
@@ -345,7 +245,6 @@ void k_bgzf_inflate(const uint8_t* __restrict__ raw, const uint64_t* __restrict_
             const uint32_t le = lc < 8u || lc == 28u ? 0u : (lc >> 2) - 1u;
             uint32_t len = (lc < 8u ? 3u + lc : lc == 28u ? 258u : 3u + ((4u + (lc & 3u)) << le)) + take(B, (int)le);
             need32(B);
-            // (distance symbol 0 with a code of l bits is the entry l << 9: never 0, so "0 = longer code" stays unambiguous)
             const int ds = decode<INF_DIST_BITS, 15>(B, T.dist_tab, T.dist_cn, T.dist_sorted);
             if (ds < 0 || ds > 29) { bad = true; break; }
             const uint32_t de = ds < 4 ? 0u : ((uint32_t)ds >> 1) - 1u;
@@ -427,10 +326,10 @@ __global__ __launch_bounds__(256) void k_crc_tables(uint32_t* __restrict__ tabs)
     t0[i] = c;
     __syncthreads();
     uint32_t skip = 0x80000000u;                                               // x^(8 * (CRC_ROW - 16))
-    for (uint32_t e = CRC_ROW - 16u, k = 0; e; e >>= 1, k++) if (e & 1u) skip = gf_mul(skip, c_xpow8.v[k]);
+    for (uint32_t e = CRC_ROW - 16u, k = 0; e; e >>= 1, k++) if (e & 1u) skip = gf_mul_shift(skip, c_xpow8.v[k]);
     for (int k = 0; k < 16; k++) {
         tabs[k * 256 + i] = c;
-        tabs[(16 + k) * 256 + i] = gf_mul(c, skip);
+        tabs[(16 + k) * 256 + i] = gf_mul_shift(c, skip);
         c = (c >> 8) ^ t0[c & 0xFFu];
     }
 }
@@ -466,8 +365,8 @@ __global__ __launch_bounds__(BLOCK) void k_bgzf_crc(const uint8_t* __restrict__ 
         // the bytes behind the lane's last piece
         const uint32_t behind = count ? n - 16u * ((count - 1u) * 64u + lane + 1u) : 0u;
         uint32_t xp = 0x80000000u;                                            // x^0, reflected
-        for (uint32_t e = behind, k = 0; e; e >>= 1, k++) if (e & 1u) xp = gf_mul(xp, c_xpow8.v[k]);
-        c = gf_mul(c, xp);
+        for (uint32_t e = behind, k = 0; e; e >>= 1, k++) if (e & 1u) xp = gf_mul_shift(xp, c_xpow8.v[k]);
+        c = gf_mul_shift(c, xp);
         if (lane == 0 && (n & 15u)) {                                         // the last n % 16 bytes: nothing behind them
             uint32_t r = full ? 0u : 0xFFFFFFFFu;
             for (uint32_t k = 16u * full; k < n; k++) r = T[0][(r ^ p0[k]) & 0xFFu] ^ (r >> 8);
@@ -541,227 +440,4 @@ extern "C" uint32_t gci_bgzf_inflate_round(gci_ctx* ctx)
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_bgzf_inflate<8>, 64, 0) != hipSuccess) return 0;
     return (uint32_t)(cus > 0 && per_cu > 0 ? cus * per_cu * 8 : 0);
-}
-
-// =====================================================================================================================
-// record offsets without the serial chain
-// =====================================================================================================================
-namespace {
-
-// "A BAM record could start at p": every field a well-formed record constrains (SAM spec 4.2) -- block_size >= 32, refID and
-// next_refID in [-1, n_ref), pos and next_pos >= -1, l_read_name >= 1, l_seq >= 0, and the fixed part + name + CIGAR + SEQ +
-// QUAL fit in block_size.
-// One thread looks at 16 consecutive byte positions of the stream: their 52 bytes as four aligned 16-byte loads (`s_al` is the
-// stream's address rounded down to 16 bytes, `delta` what was cut off), every field re-aligned in registers.  refID is
-// tested first: SEQ / QUAL bytes and text almost never form a value in [-1, n_ref), so the full test runs for few positions.
-__device__ __forceinline__ uint4 cand_load(const uint8_t* __restrict__ s_al, uint64_t q, uint64_t n_phys)
-{
-    if (q + 16 <= n_phys) return *reinterpret_cast<const uint4*>(s_al + q);
-    uint32_t w[4] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
-    for (int k = 0; k < 16; k++)
-        if (q + k < n_phys) w[k >> 2] = (w[k >> 2] & ~(0xFFu << (8 * (k & 3)))) | ((uint32_t)s_al[q + k] << (8 * (k & 3)));
-    return make_uint4(w[0], w[1], w[2], w[3]);
-}
-
-__global__ __launch_bounds__(BLOCK) void k_rec_candidates(const uint8_t* __restrict__ s_al, uint32_t delta, uint64_t lo, uint64_t n, int32_t n_ref,
-                                                          const uint32_t* __restrict__ tile_off, uint32_t* __restrict__ tile_count,
-                                                          uint64_t* __restrict__ cand)
-{
-    __shared__ uint32_t wtot[BLOCK / 64];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const uint64_t n_phys = n + delta;
-    const uint64_t q0 = (uint64_t)blockIdx.x * TILE + (uint64_t)t * 16;      // physical offset of this thread's first position
-    uint32_t d[17];
-    {
-        const uint4 v0 = cand_load(s_al, q0, n_phys), v1 = cand_load(s_al, q0 + 16, n_phys), v2 = cand_load(s_al, q0 + 32, n_phys),
-                    v3 = cand_load(s_al, q0 + 48, n_phys);
-        const uint32_t tmp[16] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w, v2.x, v2.y, v2.z, v2.w, v3.x, v3.y, v3.z, v3.w};
-#pragma unroll
-        for (int k = 0; k < 16; k++) d[k] = tmp[k];
-        d[16] = 0xFFFFFFFFu;
-    }
-    uint32_t mask = 0;
-#pragma unroll
-    for (int i = 0; i < 16; i++) {
-        // dword k of the record that would start at byte i of the window
-#define FIELD(k) ((int32_t)__builtin_amdgcn_alignbyte(d[((i) >> 2) + (k) + 1], d[((i) >> 2) + (k)], (i) & 3))
-        const int32_t ref_id = FIELD(1);
-        if (ref_id < -1 || ref_id >= n_ref) continue;
-        const uint64_t q = q0 + i;
-        if (q < lo + delta || q + 36 > n_phys) continue;
-        const int32_t block_size = FIELD(0), pos = FIELD(2), l_seq = FIELD(5), next_ref = FIELD(6), next_pos = FIELD(7);
-        const uint32_t l_read_name = (uint32_t)FIELD(3) & 0xFFu, n_cigar = (uint32_t)FIELD(4) & 0xFFFFu;
-#undef FIELD
-        if (block_size < 32 || pos < -1 || l_read_name < 1 || l_seq < 0 || next_ref < -1 || next_ref >= n_ref || next_pos < -1) continue;
-        const uint64_t need = 32ull + l_read_name + 4ull * n_cigar + (((uint64_t)(uint32_t)l_seq + 1) >> 1) + (uint64_t)(uint32_t)l_seq;
-        if (need <= (uint64_t)(uint32_t)block_size) mask |= 1u << i;
-    }
-    const uint32_t cnt = (uint32_t)__builtin_popcount(mask);
-    const uint32_t inc = wave_inclusive<uint32_t>(cnt, lane);
-    if (lane == 63) wtot[wave] = inc;
-    __syncthreads();
-    if (!cand) {                                                             // counting pass
-        if (t == 0) tile_count[blockIdx.x] = wtot[0] + wtot[1] + wtot[2] + wtot[3];
-        return;
-    }
-    uint32_t w = tile_off[blockIdx.x] + inc - cnt;
-    for (int k = 0; k < wave; k++) w += wtot[k];
-    for (uint32_t m = mask; m; m &= m - 1) cand[w++] = q0 + (uint32_t)__builtin_ctz(m) - delta;
-}
-
-#define NODE_END 0xFFFFFFFEu          // the record ends exactly at the end of the stream
-#define NODE_TAIL 0xFFFFFFFDu         // the record runs past the end of the stream (a chunk's partial last record)
-#define NODE_HEAD 0xFFFFFFFCu         // the record is complete and fewer than 36 bytes follow it (a chunk's partial record head)
-#define NODE_NONE 0xFFFFFFFFu         // its successor is not a candidate: not on the chain (or the chain is broken there)
-__global__ __launch_bounds__(BLOCK) void k_rec_link(const uint8_t* __restrict__ s, uint64_t n, const uint64_t* __restrict__ cand, uint32_t nc,
-                                                    uint32_t* __restrict__ next)
-{
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= nc) return;
-    const uint64_t p = cand[i];
-    int32_t bs;
-    __builtin_memcpy(&bs, s + p, 4);                                         // (a byte-wise copy: p has any alignment)
-    const uint64_t q = p + 4 + (uint64_t)(uint32_t)bs;
-    uint32_t r = NODE_NONE;
-    if (q == n) r = NODE_END;
-    else if (q > n) r = NODE_TAIL;
-    else {
-        uint32_t lo = i + 1, hi = nc;                                        // first candidate >= q
-        while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if (cand[mid] < q) lo = mid + 1; else hi = mid; }
-        if (lo < nc && cand[lo] == q) r = lo;
-        else if (q + 36 > n) r = NODE_HEAD;                                   // fewer than 36 bytes left: a partial record head
-    }
-    next[i] = r;
-}
-
-// jump_out[i] = jump_in[jump_in[i]] (terminal values stay)
-__global__ __launch_bounds__(BLOCK) void k_rec_double(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, uint32_t nc)
-{
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= nc) return;
-    const uint32_t a = in[i];
-    out[i] = a < nc ? in[a] : a;
-}
-
-// marked nodes mark their 2^k-th successor
-__global__ __launch_bounds__(BLOCK) void k_rec_mark(const uint32_t* __restrict__ jump, uint32_t* __restrict__ mark, uint32_t nc)
-{
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= nc || !mark[i]) return;
-    const uint32_t a = jump[i];
-    if (a < nc) mark[a] = 1u;
-}
-
-__global__ __launch_bounds__(BLOCK) void k_rec_emit(const uint8_t* __restrict__ s, const uint64_t* __restrict__ cand,
-                                                    const uint32_t* __restrict__ mark, const uint32_t* __restrict__ pos,
-                                                    const uint32_t* __restrict__ next, uint32_t nc, uint64_t n, uint64_t* __restrict__ offs,
-                                                    uint64_t cap, uint64_t* __restrict__ result)
-{
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= nc || !mark[i]) return;
-    const uint32_t nx = next[i];
-    // the last record of the chain decides how the walk ended: result[1] = bytes consumed, result[2] = 0 ok / 1 broken
-    if (nx == NODE_TAIL) { result[1] = cand[i]; return; }                    // partial last record: not emitted
-    if (pos[i] < cap) offs[pos[i]] = cand[i];
-    if (nx == NODE_END) result[1] = n;
-    else if (nx == NODE_HEAD) { int32_t bs; __builtin_memcpy(&bs, s + cand[i], 4); result[1] = cand[i] + 4 + (uint64_t)(uint32_t)bs; }
-    else if (nx == NODE_NONE) { result[1] = cand[i]; result[2] = 1; }
-}
-
-__global__ __launch_bounds__(BLOCK) void k_rec_flags(const uint32_t* __restrict__ mark, const uint32_t* __restrict__ next, uint32_t nc,
-                                                     uint32_t* __restrict__ flag)
-{
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i < nc) flag[i] = (mark[i] && next[i] != NODE_TAIL) ? 1u : 0u;
-}
-
-}  // namespace
-
-// d_result (device, 3 x uint64): [0] = number of records, [1] = bytes consumed (n_bytes when the last record ends there, else
-// the offset of the partial last record), [2] = 0 ok / 1 the chain broke at offset [1] (GCI_E_MALFORMED on the host side).
-// d_offs: up to `cap` offsets; [0] may exceed cap (call again with more room).  first_record: offset of the first record
-// (the end of the BAM header), which must pass the strict test itself.
-extern "C" int gci_bam_record_offsets_device(gci_ctx* ctx, const uint8_t* d_stream, uint64_t n_bytes, uint64_t first_record, int32_t n_ref,
-                                             uint64_t* d_offs, uint64_t cap, uint64_t* d_result)
-{
-    if (!ctx || !d_result || (n_bytes && !d_stream) || first_record > n_bytes || (cap && !d_offs)) return GCI_E_INVALID;
-    hipStream_t st = ctx->stream;
-    {
-        const uint64_t init[3] = {0, first_record, 0};
-        GCI_TRY(gci_upload_small(ctx, d_result, init, sizeof init));
-    }
-    if (n_bytes - first_record < 36) return GCI_OK;                            // no complete record head: everything is tail
-    // the candidate test walks the stream in tiles of TILE bytes counted from its address rounded down to 16 bytes
-    const uint32_t delta = (uint32_t)((uintptr_t)d_stream & 15u);
-    const uint8_t* s_al = d_stream - delta;
-    const uint64_t n_tiles64 = (n_bytes + delta + TILE - 1) / TILE;
-    if (n_tiles64 > 0x7fffffffULL) return GCI_E_INVALID;
-    const uint32_t n_tiles = (uint32_t)n_tiles64;
-    GCI_TRY(gci_ensure(ctx, ctx->part_hist, (size_t)(n_tiles + 2) * 4));
-    GCI_TRY(gci_ensure(ctx, ctx->part_blk, (size_t)(n_tiles / TILE + 2) * 4));
-    uint32_t* d_tile = (uint32_t*)ctx->part_hist.p;
-    hipLaunchKernelGGL(k_rec_candidates, dim3(n_tiles), dim3(BLOCK), 0, st, s_al, delta, first_record, n_bytes, n_ref, (const uint32_t*)nullptr,
-                       d_tile, (uint64_t*)nullptr);
-    LAUNCHCHK("k_rec_candidates(count)");
-    int r = device_exclusive_scan<uint32_t, uint32_t>(ctx, d_tile, d_tile, (uint32_t*)ctx->part_blk.p, (int64_t)n_tiles, true);
-    if (r) return r;
-    uint32_t nc = 0;
-    HIPCHK(hipMemcpyAsync(&nc, d_tile + n_tiles, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    if (nc == 0) { const uint64_t res[3] = {0, first_record, 1}; return gci_upload_small(ctx, d_result, res, sizeof res); }
-    // candidates (u64) | next, jump a, jump b, mark, flag, pos (u32 each)
-    GCI_TRY(gci_ensure(ctx, ctx->part_a, (size_t)nc * 8 + 64));
-    GCI_TRY(gci_ensure(ctx, ctx->part_b, (size_t)(nc + 1) * 4 * 6 + 64));
-    uint64_t* d_cand = (uint64_t*)ctx->part_a.p;
-    uint32_t* d_next = (uint32_t*)ctx->part_b.p;
-    uint32_t* d_ja = d_next + (nc + 1);
-    uint32_t* d_jb = d_ja + (nc + 1);
-    uint32_t* d_mark = d_jb + (nc + 1);
-    uint32_t* d_flag = d_mark + (nc + 1);
-    uint32_t* d_pos = d_flag + (nc + 1);
-    hipLaunchKernelGGL(k_rec_candidates, dim3(n_tiles), dim3(BLOCK), 0, st, s_al, delta, first_record, n_bytes, n_ref, (const uint32_t*)d_tile,
-                       (uint32_t*)nullptr, d_cand);
-    LAUNCHCHK("k_rec_candidates(write)");
-    const dim3 grid((nc + BLOCK - 1) / BLOCK);
-    hipLaunchKernelGGL(k_rec_link, grid, dim3(BLOCK), 0, st, d_stream, n_bytes, (const uint64_t*)d_cand, nc, d_next);
-    LAUNCHCHK("k_rec_link");
-    // The first record must be the first candidate.  Marks spread from it by pointer doubling: the 2^k-step successor
-    // tables are built bottom up and kept on the device one after the other would need K tables; instead the marks are
-    // spread bottom up as well -- after round k every node within 2^(k+1) - 1 steps of a marked node is marked, because
-    // round k marks the 2^k-th successors of ALL nodes marked so far (distances 0 .. 2^k - 1 from node 0 become
-    // 0 .. 2^(k+1) - 1).
-    HIPCHK(hipMemsetAsync(d_mark, 0, (size_t)nc * 4, st));
-    {
-        uint64_t first_cand = 0;
-        HIPCHK(hipMemcpyAsync(&first_cand, d_cand, 8, hipMemcpyDeviceToHost, st));
-        HIPCHK(hipStreamSynchronize(st));
-        if (first_cand != first_record) { const uint64_t res[3] = {0, first_record, 1}; return gci_upload_small(ctx, d_result, res, sizeof res); }
-        const uint32_t one = 1;
-        GCI_TRY(gci_upload_small(ctx, d_mark, &one, 4));
-    }
-    HIPCHK(hipMemcpyAsync(d_ja, d_next, (size_t)nc * 4, hipMemcpyDeviceToDevice, st));
-    uint32_t* jin = d_ja;
-    uint32_t* jout = d_jb;
-    for (uint64_t reach = 1; reach < (uint64_t)nc; reach <<= 1) {
-        hipLaunchKernelGGL(k_rec_mark, grid, dim3(BLOCK), 0, st, (const uint32_t*)jin, d_mark, nc);
-        hipLaunchKernelGGL(k_rec_double, grid, dim3(BLOCK), 0, st, (const uint32_t*)jin, jout, nc);
-        uint32_t* t = jin; jin = jout; jout = t;
-    }
-    hipLaunchKernelGGL(k_rec_mark, grid, dim3(BLOCK), 0, st, (const uint32_t*)jin, d_mark, nc);
-    LAUNCHCHK("k_rec_mark");
-    hipLaunchKernelGGL(k_rec_flags, grid, dim3(BLOCK), 0, st, (const uint32_t*)d_mark, (const uint32_t*)d_next, nc, d_flag);
-    LAUNCHCHK("k_rec_flags");
-    GCI_TRY(gci_ensure(ctx, ctx->part_blk, (size_t)(nc / TILE + 2) * 4));
-    r = device_exclusive_scan<uint32_t, uint32_t>(ctx, d_flag, d_pos, (uint32_t*)ctx->part_blk.p, (int64_t)nc, true);
-    if (r) return r;
-    hipLaunchKernelGGL(k_rec_emit, grid, dim3(BLOCK), 0, st, d_stream, (const uint64_t*)d_cand, (const uint32_t*)d_mark, (const uint32_t*)d_pos,
-                       (const uint32_t*)d_next, nc, n_bytes, d_offs, cap, d_result);
-    LAUNCHCHK("k_rec_emit");
-    // the count: d_pos[nc] (u32) -> d_result[0] (u64)
-    uint32_t n_rec = 0;
-    HIPCHK(hipMemcpyAsync(&n_rec, d_pos + nc, 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipStreamSynchronize(st));
-    const uint64_t n64 = n_rec;
-    GCI_TRY(gci_upload_small(ctx, d_result, &n64, 8));
-    return GCI_OK;
 }

@@ -33,6 +33,7 @@
 // A member that does not stitch (no meeting point within WINDOW bits, end-of-block codes on wrong paths, a header the quick
 // parser rejects) is marked in its status word and left to k_bgzf_inflate (0.2 % of the members of a HiFi BAM).
 #include "gci_ctx.hpp"
+#include "gci_deflate_codes.hpp"
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -51,6 +52,8 @@
 
 namespace iw {
 
+using namespace deflate_codes;
+
 constexpr uint32_t PIECE = 1u << IW_PIECE_LOG2;                 // bits
 constexpr uint32_t PU_LOG2 = IW_PIECE_LOG2 - 6, PU = 1u << PU_LOG2;   // 8-byte units per piece
 constexpr uint32_t CHUNK_U = 64u * PU, TAIL_U = PU;             // units per chunk; units kept behind it (a symbol that begins in the chunk ends there)
@@ -67,11 +70,6 @@ constexpr uint32_t NONE = 0xFFFFFFFFu;
 constexpr uint32_t SYM_STRIDE = 65536;                          // entries of symbol stream per member (one per output byte at most)
 
 enum { ST_OK = 0, ST_HEADER = 1, ST_NO_MEETING = 2, ST_FALSE_EOB = 3, ST_UNDECODABLE = 4, ST_LENGTH = 5, ST_LANES = 6 };
-
-__constant__ uint8_t c_clen_order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
-
-// (k_inflate.hip explains limit / off / next: the canonical code without a loop over the lengths)
-struct alignas(16) Canon { uint16_t limit[16]; int16_t off[16]; uint16_t next[16]; };
 
 struct alignas(16) Lds {
     unsigned long long pay[CHUNK_U + TAIL_U];      // the chunk, transposed: unit u of piece k at [(u << 6) | k]; the tail linear behind it
@@ -123,21 +121,6 @@ struct Reader {
     }
 };
 
-// the search over the limits of all lengths (two per word: k_inflate.hip decode()); -1: no such code
-__device__ __forceinline__ int code_search(uint32_t bits, const Canon& cn, const uint16_t* sorted, int& len)
-{
-    const uint32_t c = __brev(bits) >> 17;
-    const uint4 a = *reinterpret_cast<const uint4*>(&cn.limit[0]), b = *reinterpret_cast<const uint4*>(&cn.limit[8]);
-    const uint32_t c2 = (c | (c << 16)) + 0x80008000u;
-    const int l = __builtin_popcount((c2 - a.x) & 0x80008000u) + __builtin_popcount((c2 - a.y) & 0x80008000u)
-                + __builtin_popcount((c2 - a.z) & 0x80008000u) + __builtin_popcount((c2 - a.w) & 0x80008000u)
-                + __builtin_popcount((c2 - b.x) & 0x80008000u) + __builtin_popcount((c2 - b.y) & 0x80008000u)
-                + __builtin_popcount((c2 - b.z) & 0x80008000u) + __builtin_popcount((c2 - b.w) & 0x80008000u);
-    if (l > 15) return -1;
-    len = l;
-    return (int)sorted[(int)cn.off[l] + (int)(c >> (15 - l))];
-}
-
 // what the wave keeps in registers of a block's two codes (uniform)
 struct Codes { uint32_t lit_lim, dist_lim; bool search_l, search_d; };
 
@@ -147,14 +130,14 @@ template <int BITS, uint32_t TAIL>
 __device__ __forceinline__ uint32_t code_entry(uint32_t b, const uint16_t* tab, const uint16_t* tail, uint32_t lim, bool search, const Canon& cn,
                                                const uint16_t* sorted)
 {
-    const uint32_t t = (__brev(b) >> 17) - lim;                               // (wraps to a huge value for a code in front of the tail)
+    const uint32_t t = code_value(b) - lim;                                  // (wraps to a huge value for a code in front of the tail)
     const uint32_t e_p = tab[b & ((1u << BITS) - 1u)], e_t = tail[t < TAIL ? t : TAIL - 1u];
     uint32_t e = e_p ? e_p : t < TAIL ? e_t : 0u;
     if (search) {                                                             // (uniform, and false for the blocks of a BAM)
         if (e_p == 0u && t >= TAIL && t < 0x8000u) {
             int l = 0;
             const int s = code_search(b, cn, sorted, l);
-            e = s < 0 ? 0u : (uint32_t)s | ((uint32_t)l << 9);
+            e = s < 0 ? 0u : make_entry((uint32_t)s, (uint32_t)l);
         }
     }
     return e;
@@ -169,7 +152,7 @@ __device__ __forceinline__ Sym step(const Lds& S, const Codes& C, const Reader& 
     const unsigned long long bits = R.bits();
     const uint32_t b = (uint32_t)bits;
     const uint32_t e = code_entry<LIT_BITS, LIT_TAIL>(b, S.lit_tab, S.lit_tail, C.lit_lim, C.search_l, S.lit_cn, S.lit_sorted);
-    const uint32_t l = e >> 9, s = e & 0x1FFu;
+    const uint32_t l = entry_len(e), s = entry_sym(e);
     // the length code's base and extra bits by arithmetic (RFC 1951 3.2.5); for a literal the values are not used
     const uint32_t lc = s - 257u;
     const uint32_t le = lc < 8u || lc >= 28u ? 0u : (lc >> 2) - 1u;
@@ -177,7 +160,7 @@ __device__ __forceinline__ Sym step(const Lds& S, const Codes& C, const Reader& 
     const uint32_t used1 = l + le;
     const uint32_t b2 = (uint32_t)(bits >> used1);
     const uint32_t e2 = code_entry<DIST_BITS, DIST_TAIL>(b2, S.dist_tab, S.dist_tail, C.dist_lim, C.search_d, S.dist_cn, S.dist_sorted);
-    const uint32_t dl = e2 >> 9, ds = e2 & 0x1FFu;
+    const uint32_t dl = entry_len(e2), ds = entry_sym(e2);
     const uint32_t de = ds < 4u ? 0u : ((ds >> 1) - 1u) & 15u;
     const uint32_t dist1 = (ds < 4u ? ds : ((2u + (ds & 1u)) << de)) + ((b2 >> dl) & ((1u << de) - 1u));
     const bool is_match = s > 256u;
@@ -190,37 +173,11 @@ __device__ __forceinline__ Sym step(const Lds& S, const Codes& C, const Reader& 
     return r;
 }
 
-// lens[0 .. n) -> the canonical code, by one lane (the 19 symbols of the code-length code); false: over-subscribed or incomplete
-// (zlib refuses both: the member goes to the lane decoder, whose verdict is the call's)
-__device__ bool build_code(const uint8_t* lens, int n, Canon& cn, uint16_t* sorted)
-{
-    for (int l = 0; l < 16; l++) cn.next[l] = 0;
-    for (int i = 0; i < n; i++) cn.next[lens[i]]++;
-    uint32_t code = 0, idx = 0, left = 1u << 15, prev = 0;
-    bool ok = true;
-    cn.limit[0] = 0; cn.off[0] = 0; cn.next[0] = 0;
-    for (int l = 1; l < 16; l++) {
-        const uint32_t cnt = cn.next[l];
-        code = (code + prev) << 1;
-        cn.limit[l] = (uint16_t)((code + cnt) << (15 - l));
-        cn.off[l] = (int16_t)((int)idx - (int)code);
-        cn.next[l] = (uint16_t)idx;
-        idx += cnt; prev = cnt;
-        const uint32_t need = cnt << (15 - l);
-        if (need > left) ok = false; else left -= need;
-    }
-    if (!ok || left) return false;
-    for (int s = 0; s < n; s++) {
-        const int l = lens[s];
-        if (l) sorted[cn.next[l]++] = (uint16_t)s;
-    }
-    return true;
-}
-
-// ... and by the whole wave: the counts per length and every symbol's place among those of its length by ballots (lane s + 64 c
-// holds symbol s of chunk c), the fifteen-step prefix over the lengths by lane 0.  Same Canon, same `sorted`.
+// build_code() by the whole wave: the counts per length and every symbol's place among those of its length by ballots (lane s + 64 c
+// holds symbol s of chunk c), the fifteen-step prefix over the lengths by lane 0 (build_code's, once more: this function compiles to
+// a call with spilled scalar registers, and any other wording of lane 0's block moves all of them).  Same Canon, same `sorted`.
 // complete: the set of a dynamic block, which may leave code space over only if it has no code at all or one code of length 1
-// (k_inflate.hip build_code, CODE_ONE); the fixed distance code -- 30 codes of 5 bits -- is not asked.
+// (build_code's CODE_ONE); the fixed distance code -- 30 codes of 5 bits -- is not asked (CODE_ANY).
 __device__ bool build_code_wave(const uint8_t* lens, int n, Canon& cn, uint16_t* sorted, int lane, uint32_t* s_ok, bool complete)
 {
     uint32_t my[5];
@@ -267,23 +224,6 @@ __device__ bool build_code_wave(const uint8_t* lens, int n, Canon& cn, uint16_t*
     return *s_ok != 0u;
 }
 
-// the entry of the 15-bit code value c (first bit highest, zeros behind a shorter code): the canonical search on the value itself
-__device__ __forceinline__ uint16_t entry_of_value(uint32_t c, const Canon& cn, const uint16_t* sorted)
-{
-    int l = 0;
-#pragma unroll
-    for (int j = 0; j < 16; j++) l += cn.limit[j] <= c ? 1 : 0;
-    if (l > 15) return 0;
-    return (uint16_t)((uint32_t)sorted[(int)cn.off[l] + (int)(c >> (15 - l))] | ((uint32_t)l << 9));
-}
-// entry k of a primary table of `bits` bits (k = the next bits of the stream, first bit lowest): 0 when the code is longer
-__device__ __forceinline__ uint16_t table_entry(uint32_t k, int bits, const Canon& cn, const uint16_t* sorted)
-{
-    const uint32_t c = __brev(k) >> 17;
-    if (c >= cn.limit[bits]) return 0;
-    return entry_of_value(c, cn, sorted);
-}
-
 // the primary and the tail table of one code, every lane its entries
 __device__ __forceinline__ bool fill_tables(uint16_t* tab, int bits, uint16_t* tail, uint32_t n_tail, const Canon& cn, const uint16_t* sorted, int lane)
 {
@@ -308,7 +248,7 @@ __device__ bool read_code_lengths(Lds& S, uint32_t& p, int total)
         }
         const uint32_t e = S.cl_tab[(uint32_t)bb & 127u];
         if (e == 0u) return false;
-        const int l = (int)(e >> 9), sym = (int)(e & 31u);
+        const int l = (int)entry_len(e), sym = (int)(e & 31u);
         bb >>= l; bn -= l; p += (uint32_t)l;
         if (sym < 16) { ll[n++] = (uint8_t)sym; prev = sym; continue; }
         int rep, val = 0, xb;
@@ -422,7 +362,7 @@ __global__ __launch_bounds__(64, 4) void k_inflate_symbols(const uint8_t* __rest
                         if (lane < hclen) S.lens[c_clen_order[lane]] = (uint8_t)((c3 >> (3 * lane)) & 7u);
                         p += 3u * (uint32_t)hclen;
                         __syncthreads();
-                        if (lane == 0) S.hdr[4] = build_code(S.lens, 19, S.dist_cn, S.dist_sorted) ? 1u : 0u;
+                        if (lane == 0) S.hdr[4] = build_code(S.lens, 19, S.dist_cn, S.dist_sorted, CODE_COMPLETE) ? 1u : 0u;
                         __syncthreads();
                         if (S.hdr[4] == 0u) type = 3u;
                         else {

@@ -498,7 +498,7 @@ class Engine:
         self._chk(self.lib.gci_pack_names(self.ctx, arr, self._p(blob), total, self._p(off)), "gci_pack_names")
         return blob[:total], off
 
-    # ---- N1: BGZF inflate + record walk on the device (k_inflate.hip) ---------------------------------------------------
+    # ---- N1: BGZF inflate + record walk on the device (k_inflate.hip, k_records.hip) ---------------------------------------------------
     def upload_padded(self, raw: np.ndarray) -> Buffer:
         """The bytes of a BGZF file on the device with 16 readable bytes behind them (gci_bgzf_inflate_device takes its
         input as whole aligned 16-byte blocks)."""

@@ -718,7 +718,7 @@ int gci_stage_send(gci_ctx* ctx, gci_stage* stage, const uint8_t* h_src, uint64_
 int gci_stage_send_fd(gci_ctx* ctx, gci_stage* stage, int fd, uint64_t offset, uint64_t n, uint8_t* d_dst, void* stream, int urgent);
 int gci_stage_free(gci_stage* stage);
 
-/* ---- N1 on the GPU: BGZF inflate and the BAM record walk (k_inflate.hip; replaces pysam / htslib at GCI.py:150-151) ---------
+/* ---- N1 on the GPU: BGZF inflate and the BAM record walk (k_inflate.hip, k_records.hip; replaces pysam / htslib at GCI.py:150-151) ---------
  * gci_bgzf_inflate_device: d_raw = the bytes of a BGZF file (or of a run of its members) on the device; d_member_pos[m] =
  * offset of member m in d_raw, n_members + 1 entries (the last = end of the run; gci_bgzf_blocks makes the table on the
  * host); d_out_off[m] = where member m's output goes in d_out (exclusive scan of the members' ISIZE, n_members + 1 entries).
