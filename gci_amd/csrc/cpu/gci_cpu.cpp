@@ -39,6 +39,14 @@ struct gci_ctx {
     const void* bg_text_run0 = nullptr;
     const void* bg_text_runs = nullptr;
     uint32_t bg_text_windows = 0;
+    // bam_depth.py: what the last gci_bam_cover_size keeps for gci_bam_cover_write (per record its parse and its first interval)
+    struct CoverRec { uint64_t ops_off; uint32_t n_ops; int32_t contig; int32_t pos; };
+    std::vector<CoverRec> cover_rec;
+    std::vector<uint64_t> cover_ivl0;
+    uint64_t cover_status = ~0ull;
+    bool cover_valid = false, cover_count_del = false;
+    const void* cover_stream = nullptr;
+    const void* cover_off = nullptr;
 };
 
 namespace {
@@ -203,6 +211,66 @@ int filter_record(const uint8_t* bam, uint64_t n_bytes, uint64_t off, const int3
     r.qlen = l_seq;
     r.flags = GCI_REC_PASS | (mapq >= mq_cutoff ? GCI_REC_HQ : 0);         // GCI.py:166-168
     return GCI_OK;
+}
+
+// bam_depth.py, one record: bounds, the skip decision and where its operations lie (include/gci_hip.h: gci_bam_cover_size).
+// GCI_E_MALFORMED, or GCI_OK with r.contig < 0 for a skipped record.
+int cover_parse(const uint8_t* bam, uint64_t n_bytes, uint64_t off, bool has_seq, const int32_t* ref_sel, int32_t n_ref, uint32_t excl_flags,
+                int min_mapq, gci_ctx::CoverRec& r)
+{
+    r.ops_off = 0; r.n_ops = 0; r.contig = -1; r.pos = 0;
+    if (off > n_bytes || n_bytes - off < 36) return GCI_E_MALFORMED;
+    const uint8_t* p = bam + off;
+    const int32_t block_size = (int32_t)rd32(p), ref_id = (int32_t)rd32(p + 4), pos = (int32_t)rd32(p + 8);
+    const uint32_t l_read_name = p[12];
+    const int mapq = p[13];
+    const uint32_t n_cigar = rd16(p + 16), flag = rd16(p + 18);
+    const int32_t l_seq = (int32_t)rd32(p + 20);
+    const uint64_t rec_end = off + 4 + (uint64_t)(uint32_t)block_size;
+    const uint64_t cig_off = off + 36 + l_read_name;
+    const uint64_t aux_off = cig_off + 4ull * n_cigar + (has_seq ? (((uint64_t)(uint32_t)l_seq + 1) >> 1) + (uint64_t)(uint32_t)l_seq : 0ull);
+    if (block_size < 32 || rec_end > n_bytes || l_seq < 0 || aux_off > rec_end) return GCI_E_MALFORMED;
+    if ((flag & excl_flags) || mapq < min_mapq || ref_id < 0 || ref_id >= n_ref || pos < 0 || ref_sel[ref_id] < 0) return GCI_OK;
+    r.contig = ref_sel[ref_id]; r.pos = pos; r.ops_off = cig_off; r.n_ops = n_cigar;
+    if (n_cigar > 0) {                                                      // the CG:B,I placeholder, as filter_record restores it
+        const uint32_t op0 = rd32(bam + cig_off);
+        if ((op0 & 0xFu) == 4u && (op0 >> 4) == (uint32_t)l_seq) {
+            const uint8_t* end = bam + rec_end;
+            for (const uint8_t* q = bam + aux_off; q + 3 <= end;) {
+                const int64_t sz = aux_value_size(q + 3, end, q[2]);
+                if (sz < 0 || q + 3 + sz > end) break;
+                if (q[0] == 'C' && q[1] == 'G') {                           // the first CG tag (bam_aux_get)
+                    if (q[2] == 'B' && (q[3] == 'I' || q[3] == 'i')) {
+                        const uint32_t cg_len = rd32(q + 4);
+                        if (cg_len >= n_cigar && cg_len < (1u << 29)) { r.ops_off = (uint64_t)(q + 8 - bam); r.n_ops = cg_len; }
+                    }
+                    break;
+                }
+                q += 3 + sz;
+            }
+        }
+    }
+    return GCI_OK;
+}
+
+// the maximal runs of covering operations of one record: emit(start, end) with `end` the last covered base, both clamped to `lim`;
+// false when an operation code 9 - 15 turns up
+template <typename F>
+bool cover_walk(const uint8_t* bam, const gci_ctx::CoverRec& r, bool count_del, uint64_t lim, F emit)
+{
+    bool ok = true, open = false;
+    uint64_t at = (uint64_t)(uint32_t)r.pos, start = 0;
+    auto close = [&] { if (open) { emit((int32_t)std::min(start, lim), (int32_t)std::min(at - 1, lim)); open = false; } };
+    for (uint32_t k = 0; k < r.n_ops; k++) {
+        const uint32_t v = rd32(bam + r.ops_off + 4ull * k), op = v & 0xFu, len = v >> 4;
+        if (op >= 9u) { ok = false; continue; }
+        if (!((0x18Du >> op) & 1u) || len == 0) continue;                   // consumes no reference: a run goes on across it
+        if (((0x181u >> op) & 1u) || (count_del && op == 2u)) { if (!open) { open = true; start = at; } }
+        else close();
+        at += len;
+    }
+    close();
+    return ok;
 }
 
 int need_layout(gci_ctx* ctx) { return !ctx ? GCI_E_INVALID : ctx->n_contigs <= 0 ? GCI_E_NO_LAYOUT : GCI_OK; }
@@ -564,6 +632,70 @@ int gci_max2(gci_ctx* ctx, const int32_t* a, const int32_t* b, int32_t* out)
     if (!a || !b || !out) return GCI_E_INVALID;
     parallel_blocks(ctx->threads, (uint64_t)ctx->total, (uint64_t)1 << 22, [&](uint64_t lo, uint64_t hi) {
         for (uint64_t i = lo; i < hi; i++) out[i] = std::max(a[i], b[i]);
+    });
+    return GCI_OK;
+}
+
+/* ---- bam_depth.py: the reference bases the records cover (k_cover.hip's twins; one interval per maximal run of a RECORD here) --------- */
+int gci_bam_cover_size(gci_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, const uint64_t* rec_off, uint32_t n_rec, int has_seq,
+                       const int32_t* ref_sel, int32_t n_ref, uint32_t excl_flags, int min_mapq, int count_del, uint64_t* h_n_ivl, uint64_t* status)
+{
+    if (!ctx || !h_n_ivl || !status || n_ref < 0 || (n_rec && (!bam || !rec_off || !ref_sel))) return GCI_E_INVALID;
+    const int lst = need_layout(ctx);
+    if (lst) return lst;
+    ctx->cover_valid = false;
+    *h_n_ivl = 0;
+    ctx->cover_rec.assign(n_rec, gci_ctx::CoverRec{0, 0, -1, 0});
+    ctx->cover_ivl0.assign((size_t)n_rec + 1, 0);
+    std::atomic<uint64_t> st{~0ull};
+    parallel_blocks(ctx->threads, n_rec, 4096, [&](uint64_t lo, uint64_t hi) {
+        for (uint64_t i = lo; i < hi; i++) {
+            gci_ctx::CoverRec& r = ctx->cover_rec[i];
+            if (cover_parse(bam, n_bytes, rec_off[i], has_seq != 0, ref_sel, n_ref, excl_flags, min_mapq, r) != GCI_OK) { report(st, (uint32_t)i, GCI_E_MALFORMED); continue; }
+            if (r.contig < 0) continue;
+            uint64_t n = 0;
+            if (!cover_walk(bam, r, count_del != 0, 0, [&](int32_t, int32_t) { n++; })) report(st, (uint32_t)i, GCI_E_MALFORMED);
+            ctx->cover_ivl0[i + 1] = n;
+        }
+    });
+    for (uint32_t i = 0; i < n_rec; i++) ctx->cover_ivl0[i + 1] += ctx->cover_ivl0[i];
+    ctx->cover_status = st.load();
+    ctx->cover_valid = true; ctx->cover_count_del = count_del != 0; ctx->cover_stream = bam; ctx->cover_off = rec_off;
+    *status = ctx->cover_status;
+    *h_n_ivl = ctx->cover_ivl0[n_rec];
+    return GCI_OK;
+}
+
+int gci_bam_cover_write(gci_ctx* ctx, const uint8_t* bam, uint64_t, const uint64_t* rec_off, uint32_t n_rec, int, gci_ivl* out, uint64_t cap,
+                        uint64_t* status)
+{
+    if (!ctx || !status || (n_rec && (!bam || !rec_off))) return GCI_E_INVALID;
+    const int lst = need_layout(ctx);
+    if (lst) return lst;
+    if (!ctx->cover_valid || ctx->cover_rec.size() != n_rec || bam != ctx->cover_stream || rec_off != ctx->cover_off) return GCI_E_INVALID;
+    const uint64_t total = ctx->cover_ivl0[n_rec];
+    if (total && !out) return GCI_E_INVALID;
+    if (cap < total) return GCI_E_CAPACITY;
+    parallel_blocks(ctx->threads, n_rec, 4096, [&](uint64_t lo, uint64_t hi) {
+        for (uint64_t i = lo; i < hi; i++) {
+            const gci_ctx::CoverRec& r = ctx->cover_rec[i];
+            if (r.contig < 0 || r.contig >= ctx->n_contigs) continue;
+            const int64_t L = ctx->len[(size_t)r.contig];
+            uint64_t k = ctx->cover_ivl0[i];
+            cover_walk(bam, r, ctx->cover_count_del, (uint64_t)std::min<int64_t>(L, 0x7FFFFFFEll), [&](int32_t a, int32_t b) { out[k++] = gci_ivl{r.contig, a, b, 0}; });
+        }
+    });
+    *status = ctx->cover_status;
+    return GCI_OK;
+}
+
+int gci_track_add(gci_ctx* ctx, int32_t* acc, const int32_t* add)
+{
+    const int st = need_layout(ctx);
+    if (st) return st;
+    if (!acc || !add || ((((uintptr_t)acc) | ((uintptr_t)add)) & 15u)) return GCI_E_INVALID;     // (16-byte aligned, as libgci_hip.so asks)
+    parallel_blocks(ctx->threads, (uint64_t)ctx->total, (uint64_t)1 << 22, [&](uint64_t lo, uint64_t hi) {
+        for (uint64_t i = lo; i < hi; i++) acc[i] += add[i];
     });
     return GCI_OK;
 }

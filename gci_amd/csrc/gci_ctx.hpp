@@ -123,6 +123,15 @@ struct gci_ctx {
     uint32_t bg_text_windows = 0;
     uint64_t bg_text_n_runs = 0, bg_text_total = 0;
     DevBuf hist_chunk_first;                // k_hist.hip: the first chunk (workgroup) of every window of the last gci_depth_hist
+    // k_cover.hip: what gci_bam_cover_size keeps for gci_bam_cover_write -- per record (its parse, chunk count, first chunk) and
+    // per chunk (reference length, intervals and their scans), the status word of the size pass, and what that call measured
+    DevBuf cover_rec, cover_chunk;
+    bool cover_valid = false;
+    uint32_t cover_n_rec = 0;
+    uint64_t cover_n_chunks = 0, cover_n_ivl = 0;
+    int cover_count_del = 0;
+    const void* cover_stream = nullptr;
+    const void* cover_off = nullptr;
     void* h_pinned = nullptr;               // staging for small uploads
     size_t h_pinned_cap = 0;
     // optional per-kernel HIP-event timing (gci_profile_*)

@@ -338,6 +338,28 @@ class Engine:
             self.check_status("gci_bam_filter_pages")
         return out[:n], name_off[:n]
 
+    # ---- bam_depth.py: the reference bases the records cover (include/gci_hip.h: gci_bam_cover_*, gci_track_add) -------
+    def bam_cover(self, d_stream: Buffer, d_rec_off: Buffer, has_seq: bool, d_ref_sel: Buffer, excl_flags: int = 0x704,
+                  min_mapq: int = 0, count_del: bool = False, check: bool = True, rec_idx_base: int = 0) -> Buffer:
+        """-> intervals int32 [n, 4] (contig, start, last covered base, 0) of the records of an inflated BAM stream (has_seq) or a
+        heads stream: what `samtools depth -a` counts, for depth_build with flank 0.  Needs the layout of the selected contigs."""
+        n = int(d_rec_off.shape[0])
+        n_ivl = ctypes.c_uint64(0)
+        self._chk(self.lib.gci_bam_cover_size(self.ctx, self._p(d_stream), int(d_stream.shape[0]), self._p(d_rec_off), n, int(has_seq),
+                                              self._p(d_ref_sel), int(d_ref_sel.shape[0]), int(excl_flags), int(min_mapq),
+                                              int(bool(count_del)), ctypes.byref(n_ivl), self._p(self._status)), "gci_bam_cover_size")
+        if check:
+            self._raise_status(self._status.item(), "gci_bam_cover_size", rec_idx_base)
+        out = self.T.empty((max(int(n_ivl.value), 1), 4), self.T.int32, self.device)
+        self._chk(self.lib.gci_bam_cover_write(self.ctx, self._p(d_stream), int(d_stream.shape[0]), self._p(d_rec_off), n, int(has_seq),
+                                               self._p(out), int(n_ivl.value), self._p(self._status)), "gci_bam_cover_write")
+        return out[:int(n_ivl.value)]
+
+    def track_add(self, acc: Buffer, add: Buffer) -> Buffer:
+        """acc += add over the layout."""
+        self._chk(self.lib.gci_track_add(self.ctx, self._p(acc), self._p(add)), "gci_track_add")
+        return acc
+
     def _raise_status(self, w: int, what: str, base: int = 0) -> None:
         """A status word of the library as a GciError (none for a clean one); `base`: what the word's record index counts from."""
         rec = ctypes.c_uint32(0)

@@ -291,9 +291,38 @@ BAM_CHUNK_BYTES = int(os.environ.get("GCI_BAM_CHUNK_BYTES", str(4 << 30)))     #
 K1_MODE = os.environ.get("GCI_K1", "pages")
 
 
+class StreamVisitor:
+    """What a BAM file's ingestion hands its streams to INSTEAD of the record filter, given as `filt`: every ingest mode (`gpu` whole
+    and run by run, `heads`, `full`) and GCI_BAM_CHUNK_BYTES end in _filter_stream, which calls the visitor with the inflated (or
+    heads) stream of a piece of the file and its record offsets -- no pages, no K1 -- and passes on the empty join input it returns.
+    `engine` is the context the piece lives on: in the `gpu` mode the walk engine, not the caller's (its work is ordered against the
+    caller's stream when the file is through: _gpu_runs).  rec_idx_base counts the records of the file in front of the piece; a pass
+    over a file begins with 0, and a file whose device walk gives up part-way is read again from the start by the next ingest path:
+    begin_file() / abort_file() discard what was collected for the file."""
+
+    def begin_file(self) -> None:
+        pass
+
+    def abort_file(self) -> None:
+        pass
+
+    def visit(self, engine: Engine, d_stream: Buffer, d_off: Buffer, has_seq: bool, ref_sel: Buffer, rec_idx_base: int) -> None:
+        raise NotImplementedError
+
+    def __call__(self, engine: Engine, d_stream: Buffer, d_off: Buffer, has_seq: bool, ref_sel: Buffer, rec_idx_base: int) -> JoinInput:
+        if rec_idx_base == 0:                             # the file from its first record (again): nothing of an earlier pass counts
+            self.abort_file()
+            self.begin_file()
+        self.visit(engine, d_stream, d_off, has_seq, ref_sel, rec_idx_base)
+        return _concat_parts(engine, [])
+
+
 def _filter_stream(engine: Engine, d_stream: Buffer, d_off: Buffer, has_seq: bool, ref_sel: Buffer, filt,
                    rec_idx_base: int = 0) -> JoinInput:
-    """K1 over the records of an inflated BAM stream (has_seq) or a heads stream -> join input (records + where their names are)."""
+    """K1 over the records of an inflated BAM stream (has_seq) or a heads stream -> join input (records + where their names are).
+    `filt`: the record filter's (map_qual, mq_cutoff, clip_percent, iden_percent) -- or a StreamVisitor, which gets the stream instead."""
+    if isinstance(filt, StreamVisitor):
+        return filt(engine, d_stream, d_off, has_seq, ref_sel, rec_idx_base)
     map_qual, mq_cutoff, clip_percent, iden_percent = filt
     if K1_MODE == "pages" or not has_seq:                 # (a heads stream is only ever read through its pages)
         with phases.gpu("record pages"):
@@ -1127,6 +1156,144 @@ def _depths_of_build(engine: Engine, tl: Dict[str, int], all_targets: List[str],
         with phases.wall("write_depth_gz (deflate on the device, D2H, file)") if from_build else contextlib.nullcontext():
             _write_depth_members(directory, prefix, depths, from_build=from_build)
         print("Writing depths done!!!\n\n")
+    return depths
+
+
+# ==============================================================================================
+# bam_depth.py: the unfiltered per-base depth of BAM files (`samtools depth -a`)
+# ==============================================================================================
+
+COVER_EXCL_DEFAULT = 0x704                 # UNMAP, SECONDARY, QCFAIL, DUP: samtools depth's default
+COVER_IVL_BUDGET = 1 << 27                 # intervals collected before they are built into the track: 2 GiB of them, a count below 2^31
+
+
+class CoverOpts:
+    """`samtools depth -a`'s record options: excl (flag bits that skip a record; -G adds, -g removes), min_mapq (-Q), count_del (-J)."""
+
+    def __init__(self, excl: int = COVER_EXCL_DEFAULT, min_mapq: int = 0, count_del: bool = False):
+        self.excl, self.min_mapq, self.count_del = int(excl), int(min_mapq), bool(count_del)
+
+
+class SqMismatch(ValueError):
+    """A later BAM file whose @SQ table (names, lengths, order) is not the first file's."""
+
+
+def same_sq_table(bam_files: Sequence[str]):
+    """The first file's header; SqMismatch when a later file's @SQ table (names, lengths, order) is another."""
+    first = bamfmt.read_header(bam_files[0])
+    for path in bam_files[1:]:
+        hdr = bamfmt.read_header(path)
+        if (tuple(hdr.references), tuple(hdr.lengths)) != (tuple(first.references), tuple(first.lengths)):
+            raise SqMismatch(f'The @SQ table of "{path}" differs from that of "{bam_files[0]}"')
+    return first
+
+
+class _CoverVisitor(StreamVisitor):
+    """The covered bases of one file after another: the intervals of every piece (gci_bam_cover_*) collect on the device; beyond
+    `budget` of them they are built into a scratch track that is added to the file's (gci_track_add).  All of that runs on the
+    engine, and in the stream, of the piece; file_done() -- on the caller's engine, when the ingestion has ordered the two -- turns
+    what is left into the file's track."""
+
+    def __init__(self, main: Engine, opts: CoverOpts, budget: int):
+        self.main, self.opts, self.budget = main, opts, max(int(budget), 1)
+        self.flushes = 0
+        self.begin_file()
+
+    def begin_file(self) -> None:
+        self.parts: List[Buffer] = []
+        self.n_ivl = 0
+        self.track: Optional[Buffer] = None
+
+    abort_file = begin_file
+
+    def _build(self, engine: Engine) -> Optional[Buffer]:
+        """The collected intervals as depths in a new track; None when there is nothing to build."""
+        parts, self.parts, self.n_ivl = self.parts, [], 0
+        if not parts:
+            return None
+        ivl = parts[0] if len(parts) == 1 else engine.T.cat(parts)
+        track = engine.new_track()
+        with phases.gpu("depth build"):
+            engine.depth_build(ivl, None, 0, track)
+        return track
+
+    def _flush(self, engine: Engine) -> None:
+        built = self._build(engine)
+        if built is None:
+            return
+        self.flushes += 1
+        if self.track is None:
+            self.track = built
+        else:
+            engine.track_add(self.track, built)
+
+    def visit(self, engine, d_stream, d_off, has_seq, ref_sel, rec_idx_base) -> None:
+        if engine.lengths != self.main.lengths:            # (the walk engine: a context of its own)
+            engine.set_layout(self.main.lengths)
+        try:
+            with phases.gpu("record cover"):
+                ivl = engine.bam_cover(d_stream, d_off, has_seq, ref_sel, self.opts.excl, self.opts.min_mapq, self.opts.count_del)
+        except GciError as e:
+            if e.rec < 0:
+                raise
+            # e.rec counts inside the piece (the ingestion adds what lies in front: _rebased); the text names the record of the FILE
+            raise GciError(e.status, "gci_bam_cover_size: %s (record %d of the file)"
+                           % (engine.lib.gci_strerror(e.status).decode(), e.rec + rec_idx_base), rec=e.rec) from None
+        if int(ivl.shape[0]):
+            self.parts.append(ivl)
+            self.n_ivl += int(ivl.shape[0])
+        if self.n_ivl > self.budget:
+            self._flush(engine)
+        if engine is not self.main:                        # (made in that engine's stream order, used in the caller's from file_done on)
+            for t in self.parts + ([self.track] if self.track is not None else []):
+                t.record_stream(self.main.stream)
+
+    def file_done(self) -> Buffer:
+        """The file's track (the caller's engine and stream): a file that needed no flush is built straight into a new one."""
+        engine = self.main
+        if self.track is None:
+            track = self._build(engine)
+            if track is None:                              # no interval at all
+                track = engine.new_track()
+                track.zero_()
+        else:
+            self._flush(engine)
+            track = self.track
+        self.begin_file()
+        return track
+
+
+def bam_raw_depth(engine: Engine, bam_files: Sequence[str], chrs: Sequence[str] = (), opts: Optional[CoverOpts] = None, threads: int = 1,
+                  ivl_budget: Optional[int] = None) -> DepthTracks:
+    """The per-base read-mapping depth of `bam_files` as `samtools depth -a` counts it (include/gci_hip.h: gci_bam_cover_size), added
+    over the files.  Contig names, lengths and order are the first file's header's (restricted by `chrs`); a file with another @SQ
+    table raises SqMismatch.  The files go through bam_join_input with a visitor for a filter: every ingest mode serves."""
+    opts = opts or CoverOpts()
+    first = same_sq_table(bam_files)
+    targets_length = _targets_of(first, list(chrs))
+    targets = list(targets_length.keys())
+    if not targets:
+        raise ValueError("no contig selected")
+    engine.set_layout([targets_length[t] for t in targets])
+    visitor = _CoverVisitor(engine, opts, COVER_IVL_BUDGET if ivl_budget is None else ivl_budget)
+    total = None
+    for k, path in enumerate(bam_files):
+        visitor.begin_file()
+        try:
+            with phases.wall("bam_cover[%s]" % os.path.basename(path)):
+                bam_join_input(engine, path, targets, visitor, threads)
+        except BaseException as e:
+            visitor.abort_file()
+            if isinstance(e, GciError):
+                e.path = path                             # (which file the record index counts in: the command line says so)
+            raise
+        track = visitor.file_done()
+        if total is None:
+            total = track
+        else:
+            engine.track_add(total, track)
+    depths = DepthTracks(engine, targets_length, total)
+    depths.cover_flushes = visitor.flushes
     return depths
 
 

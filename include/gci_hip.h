@@ -19,6 +19,7 @@
  *   gci_fasta_n_scan    get_Ns_ref                    GCI.py:27-35
  *   gci_depth_runs_*, gci_bedgraph_*   depth_to_bedgraph.py: a track as bedGraph lines (no counterpart in the reference)
  *   gci_depth_hist      depth_dist.py: the depth histogram, sum, min, max and count of windows (no counterpart in the reference)
+ *   gci_bam_cover_*, gci_track_add     bam_depth.py: the unfiltered per-base depth of BAM files, `samtools depth -a` (no counterpart in the reference)
  *   gci_paf_filter_device   filter(), PAF path        GCI.py:211-254  (+ helpers 49-61, 64-96)
  *
  * Conventions
@@ -246,6 +247,34 @@ uint64_t gci_name_hash(const uint8_t* h_name, uint32_t len);
  * d_out_off[i] = byte offset of name i (exclusive scan of name_len), d_out_off[n] = total. */
 int gci_pack_names(gci_ctx* ctx, const gci_join_file* h_file, uint8_t* d_out_names, uint64_t cap,
                    uint64_t* d_out_off);
+
+/* ---- bam_depth.py: the reference bases every record covers, `samtools depth -a` without its base-quality options (k_cover.hip) ----
+ * The same input as gci_bam_filter: the inflated stream and the record offsets (has_seq != 0), or a heads stream (has_seq == 0).
+ * Needs gci_layout_set (the selected contigs, in the order d_ref_sel numbers them).
+ *   skipped    a record with flag & excl_flags != 0, mapq < min_mapq, refID < 0 or >= n_ref, pos < 0 or d_ref_sel[refID] < 0
+ *   covers     M, = and X cover their reference bases; D only with count_del != 0; N never; I, S, H and P consume no reference;
+ *              operations of length 0 cover nothing.  A <l_seq>S<n>N placeholder with a CG:B,I (or B,i) tag stands for the tag's
+ *              operations (the rule of gci_bam_filter); without the tag it covers nothing
+ *   malformed  a record that runs past the end of the stream or contradicts its block_size (as gci_bam_filter finds it, skipped or
+ *              not), and operation codes 9 - 15 in a record that is not skipped: GCI_E_MALFORMED in *d_status (the smallest such
+ *              record index << 8 | -status, UINT64_MAX if none; decode with gci_decode_status)
+ * gci_bam_cover_size: *h_n_ivl = the number of intervals the write call will emit; *d_status is complete after it.  Synchronises.
+ *   The scratch of this call stays in the context for the write call.
+ * gci_bam_cover_write: the intervals of the input the size call in front of it on this context measured (same d_stream, d_rec_off
+ *   and n_rec: else GCI_E_INVALID) to d_out[0 .. *h_n_ivl), in no particular order; cap < *h_n_ivl: GCI_E_CAPACITY, nothing is
+ *   written.  `end` is the LAST covered base (inclusive), so that gci_depth_build with flank 0 -- [start : end + 1] -- adds exactly
+ *   the covered bases; positions are summed in 64 bits and clamped to the contig's length before they become int32 (what lies beyond
+ *   the contig's end is dropped by the build's slice).  One interval per maximal run of covering operations inside a chunk of
+ *   GCI_COVER_CHUNK_OPS operations: the unit of work is a chunk (one wave), never a record.
+ * gci_track_add: d_acc[i] += d_add[i] over the layout (depths of several files, or of one file built in parts).  Both are whole
+ *   tracks of gci_layout_total() elements, 16-byte aligned (any allocation is): an unaligned pointer is GCI_E_INVALID. */
+#define GCI_COVER_CHUNK_OPS 2048
+int gci_bam_cover_size(gci_ctx* ctx, const uint8_t* d_stream, uint64_t n_bytes, const uint64_t* d_rec_off, uint32_t n_rec, int has_seq,
+                       const int32_t* d_ref_sel, int32_t n_ref, uint32_t excl_flags, int min_mapq, int count_del, uint64_t* h_n_ivl,
+                       uint64_t* d_status);
+int gci_bam_cover_write(gci_ctx* ctx, const uint8_t* d_stream, uint64_t n_bytes, const uint64_t* d_rec_off, uint32_t n_rec, int has_seq,
+                        gci_ivl* d_out, uint64_t cap, uint64_t* d_status);
+int gci_track_add(gci_ctx* ctx, int32_t* d_acc, const int32_t* d_add);
 
 /* ---- R5: cross-file join --------------------------------------------------------------------
  * h_files in reference order (PAF files, then BAM files, each in command-line order).
