@@ -92,6 +92,10 @@ struct gci_ctx {
     uint32_t pg_n_rec = 0, pg_page_bytes = 0, pg_n_pages = 0;
     uint32_t pg_cus = 0;                    // compute units of the device (k_pg_write's grid; asked for once)
     uint32_t pg_per_cu = 0, pg_per_cu_page_bytes = 0;   // ... and workgroups of k_pg_write a CU holds, for pages of that size
+    uint32_t pg_lean_per_cu = 0, pg_lean_page_bytes = 0;   // ... and of k_pg_lean
+    uint32_t pg_grid_cap = 0;               // GCI_PAGES_GRID=<n>: at most n workgroups for the page writers (testing; 0: what the device holds)
+    DevBuf pg_list;                         // the pages k_pg_lean left to k_pg_write: two counters (u32 each, 16 bytes in all), then the list
+    uint32_t pg_parity = 0;                 // which of the two counters the next gci_bam_pages_write uses
     uint64_t pg_blob_off = 0;
     uint64_t pg_blob_bytes = 0;               // total size of the blob the size call measured (without its 16 guard bytes)
     std::vector<DevBuf> paf_pool;           // K2's scratch, in the order a call asks for it (k_paf.hip: PafScratch)

@@ -315,7 +315,10 @@ static inline __host__ __device__ uint32_t pg_win_cap(uint32_t page_bytes) { ret
 // the window for records from stream offset off0 on, none of them expected behind span_end (<= n_bytes): empty when that lies below
 // off0.  Whole 16-byte pieces that lie inside the stream only -- no load touches a byte outside [bam, end) -- so what a record has in
 // the stream's first or last, partial, piece is not in the window and is gathered.
-__device__ __forceinline__ PgWin pg_win_of(const uint8_t* lds, const uint8_t* bam, const uint8_t* end, uint64_t off0, uint64_t span_end, uint32_t cap)
+// whole_only: a span longer than the window gets none (the table says before any load that the page cannot be staged: a whole
+// stream with SEQ / QUAL, ONT -- its records are gathered, and the window's bytes would have been loaded for nothing)
+__device__ __forceinline__ PgWin pg_win_of(const uint8_t* lds, const uint8_t* bam, const uint8_t* end, uint64_t off0, uint64_t span_end, uint32_t cap,
+                                           bool whole_only = false)
 {
     PgWin W;
     W.lds = lds; W.lo = W.hi = bam;
@@ -326,7 +329,7 @@ __device__ __forceinline__ PgWin pg_win_of(const uint8_t* lds, const uint8_t* ba
         const uint8_t* last = bam + span_end + 15;
         const uint8_t* hi = last - ((uintptr_t)last & 15u);
         if (hi > end) hi = end - ((uintptr_t)end & 15u);
-        if (hi > lo) { W.lo = lo; W.hi = (uint64_t)(hi - lo) < cap ? hi : lo + cap; }
+        if (hi > lo && !(whole_only && (uint64_t)(hi - lo) > cap)) { W.lo = lo; W.hi = (uint64_t)(hi - lo) < cap ? hi : lo + cap; }
     }
     return W;
 }
@@ -393,7 +396,11 @@ __device__ __forceinline__ PgMine pg_mine_of(const PgArgs& A, const PgPage& p, u
 #ifndef PG_WAVES
 #define PG_WAVES 4                     // waves per SIMD the registers are cut to: 4 workgroups per CU, what the LDS allows too (3 without: 146 VGPRs)
 #endif
-__global__ __launch_bounds__(PG_BLOCK) __attribute__((amdgpu_waves_per_eu(PG_WAVES, PG_WAVES))) void k_pg_write(const PgArgs A)
+//
+// With a list (`listed`, its length read here from *n_listed) the pages are the listed ones -- those the lean writer below left --
+// instead of all of them.  Workgroup 0 also writes the 16 zero bytes behind the blob (`guard`).
+__global__ __launch_bounds__(PG_BLOCK) __attribute__((amdgpu_waves_per_eu(PG_WAVES, PG_WAVES))) void k_pg_write(const PgArgs A, const uint32_t* __restrict__ n_listed,
+                                                                                                                const uint32_t* __restrict__ listed, uint8_t* __restrict__ guard)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t win[];              // the window
     // which records of the page leave something in the blob (nearly none of a HiFi file): the pass over the blob below looks
@@ -411,15 +418,21 @@ __global__ __launch_bounds__(PG_BLOCK) __attribute__((amdgpu_waves_per_eu(PG_WAV
     const uint8_t* end = A.bam + A.n_bytes;
     const PgPage none = {0u, 0u, 0ull, 0ull};
 
-    uint32_t k = blockIdx.x;                                       // (< n_pages: the grid is no larger)
+    if (blockIdx.x == 0 && t < 16) guard[t] = 0;
+    const uint32_t n_items = listed ? *n_listed : A.n_pages;
+    uint32_t it = blockIdx.x;                                      // item `it` is page listed[it], or page `it`
+    if (it >= n_items) return;
+    uint32_t k = listed ? listed[it] : it;
+    uint32_t k_after = it + G < n_items ? (listed ? listed[it + G] : it + G) : 0u;
     PgPage p_next = pg_page_of(A, k);
-    PgPage p_after = k + G < A.n_pages ? pg_page_of(A, k + G) : none;
-    PgWin W_next = pg_win_of(win, A.bam, end, p_next.off0, p_next.span_end, win_cap);
+    PgPage p_after = it + G < n_items ? pg_page_of(A, k_after) : none;
+    PgWin W_next = pg_win_of(win, A.bam, end, p_next.off0, p_next.span_end, win_cap, true);
     uint4 v[PG_WIN_REGS];
     pg_win_load(W_next, t, v);
     PgMine m_next = pg_mine_of(A, p_next, t);
 
-    for (; k < A.n_pages; k += G) {
+    uint32_t k_next = 0u;
+    for (; it < n_items; it += G, k = k_next) {
         const PgPage pg = p_next;
         const PgMine mine = m_next;
         const PgWin W0 = W_next;
@@ -437,12 +450,15 @@ __global__ __launch_bounds__(PG_BLOCK) __attribute__((amdgpu_waves_per_eu(PG_WAV
         }
         // ---- the loads of the pages behind this one
         p_next = p_after;
-        if (k + G < A.n_pages) {
-            W_next = pg_win_of(win, A.bam, end, p_next.off0, p_next.span_end, win_cap);
+        if (it + G < n_items) {
+            W_next = pg_win_of(win, A.bam, end, p_next.off0, p_next.span_end, win_cap, true);
             pg_win_load(W_next, t, v);
             m_next = pg_mine_of(A, p_next, t);
         }
-        p_after = (uint64_t)k + 2ull * G < A.n_pages ? pg_page_of(A, k + 2 * G) : none;
+        const bool two_on = (uint64_t)it + 2ull * G < n_items;
+        k_next = k_after;
+        k_after = two_on ? (listed ? listed[it + 2 * G] : it + 2 * G) : 0u;
+        p_after = two_on ? pg_page_of(A, k_after) : none;
 
         if (cnt == 0) __syncthreads();
         for (uint32_t m0 = 0; m0 < cnt;) {
@@ -582,6 +598,218 @@ __global__ __launch_bounds__(PG_BLOCK) __attribute__((amdgpu_waves_per_eu(PG_WAV
     }
 }
 
+// ---- the lean writer: pages staged whole -----------------------------------------------------------------------------------------
+// Nearly every page of a heads stream is LEAN: its span, taken from the page table, is whole 16-byte pieces of the stream that
+// fit the window; it has 1 .. PG_META_MAX records at ascending offsets; each measures as kind 0 and lies in the window.  k_pg_lean
+// writes those and nothing else: no gather, no blob pass, no second fill -- its only global loads are the page tables, the
+// offsets, the sums and the window.  A page it finds not lean it leaves alone and appends to a list (one atomic per such page);
+// k_pg_write then runs over the list.  (K1's scheme: a lean path for nearly every record, the path that knows every case for the
+// rest.)
+//
+// How it waits.  A page is NP * PG_BLOCK pieces of 16 bytes -- header, directory, records and zero tail alike -- and every thread
+// stores exactly NP of them, unconditionally, after ALL loads of the iteration (the next page's window, its offsets and sums, the
+// table entries of the page behind it) have been issued.  The memory counter retires in order, so the wait at the loop's top for
+// those loads is "all but the last NP": the stores of the page just composed stay in flight, and nothing between the loads and
+// the back edge waits for them.  That needs a store that is issued whether or not the page is written: the stores go through a
+// buffer descriptor over the page whose size is 0 for a page that is not lean -- the hardware drops them.
+struct PglWin { const uint8_t* lo; uint32_t pieces; };             // the window: `pieces` 16-byte pieces from lo on; 0: not staged
+__device__ __forceinline__ PglWin pgl_win_of(const PgArgs& A, const PgPage& p, uint32_t cap)
+{
+    PglWin W;
+    W.lo = A.bam; W.pieces = 0;
+    if (p.cnt == 0 || p.cnt > PG_META_MAX || p.off0 >= p.span_end) return W;          // (span_end <= n_bytes: pg_page_of)
+    const uint8_t* p0 = A.bam + p.off0;
+    const uint8_t* lo = p0 - ((uintptr_t)p0 & 15u);                // (the ADDRESS rounded down: the stream pointer need not be aligned)
+    const uint8_t* last = A.bam + p.span_end + 15;
+    const uint8_t* hi = last - ((uintptr_t)last & 15u);
+    if (lo < A.bam || hi > A.bam + A.n_bytes || (uint64_t)(hi - lo) > cap) return W;   // the stream's partial first and last piece: not here
+    W.lo = lo; W.pieces = (uint32_t)(hi - lo) / 16u;
+    return W;
+}
+
+// What the loads of an iteration bring, as loaded: any arithmetic on it would be a wait where it stands, so it is done at the loop's top.
+// (z: a zero the compiler cannot see through, in a vector register.  With it the same-for-all-lanes loads below are vector loads
+//  whose results stay where they land; without it the compiler moves each into a scalar register right behind the load -- a wait.)
+struct PglTab { uint32_t first, first1; uint64_t off0, off1; };    // the table entries of pages k and k + 1
+__device__ __forceinline__ uint32_t pgl_rfl(uint32_t x) { return __builtin_amdgcn_readfirstlane(x); }
+__device__ __forceinline__ uint64_t pgl_rfl(uint64_t x) { return pgl_rfl((uint32_t)x) | ((uint64_t)pgl_rfl((uint32_t)(x >> 32)) << 32); }
+__device__ __forceinline__ PglTab pgl_tab_of(const PgArgs& A, uint32_t k, uint32_t z)
+{
+    PglTab r;
+    r.first = A.page_first[k + z]; r.first1 = A.page_first[k + 1 + z]; r.off0 = A.page_off[k + z]; r.off1 = A.page_off[k + 1 + z];
+    return r;
+}
+__device__ __forceinline__ PgPage pgl_page_of(const PgArgs& A, const PglTab& r)   // = pg_page_of()
+{
+    PgPage p;
+    p.first = pgl_rfl(r.first); p.cnt = pgl_rfl(r.first1) - p.first; p.off0 = pgl_rfl(r.off0); p.span_end = pgl_rfl(r.off1);
+    if (p.span_end > A.n_bytes) p.span_end = A.n_bytes;
+    return p;
+}
+// the two levels of a cost offset (pg_S() adds them), the low word of each: all that is asked of them here is the difference of two
+// within a page (a loaded word nobody reads is a register the compiler reuses at once -- behind a wait for the load)
+struct PglSum { uint32_t loc, blk; };
+__device__ __forceinline__ PglSum pgl_sum_of(const PgSums& s, uint32_t i)
+{
+    PglSum r;
+    r.loc = s.S_loc[i]; r.blk = reinterpret_cast<const uint32_t*>(s.blk)[2u * (i / TILE)];
+    return r;
+}
+__device__ __forceinline__ uint32_t pgl_diff(const PglSum& a, const PglSum& b) { return (a.loc + a.blk) - (b.loc + b.blk); }
+__device__ __forceinline__ PglSum pgl_rfl(const PglSum& a) { PglSum r; r.loc = pgl_rfl(a.loc); r.blk = pgl_rfl(a.blk); return r; }
+struct PglMine { uint64_t off; PglSum S, S0, S_end; };             // = PgMine
+__device__ __forceinline__ PglMine pgl_mine_of(const PgArgs& A, const PgPage& p, uint32_t t, uint32_t z)
+{
+    PglMine m;
+    m.off = 0; m.S.loc = 0; m.S.blk = 0;
+    if (t < p.cnt && t < PG_META_MAX) { m.off = A.rec_off[p.first + t]; m.S = pgl_sum_of(A.sums, p.first + t); }
+    m.S0 = pgl_sum_of(A.sums, p.first + z);                        // (index n_rec is an entry like any other)
+    m.S_end = pgl_sum_of(A.sums, p.first + p.cnt + z);
+    return m;
+}
+
+typedef uint32_t pgl_u32x4 __attribute__((ext_vector_type(4)));
+// The window is read once and the page written once, 5.6 GB per file that no cache holds: both non-temporal (1102 -> 1034 us per file,
+// the loads 52 and the stores 19 of it on their own: profiles/pages_lean_variants.txt)
+__device__ __forceinline__ uint4 pgl_load16(const uint4* p)
+{
+    const pgl_u32x4 x = __builtin_nontemporal_load(reinterpret_cast<const pgl_u32x4*>(p));
+    return make_uint4(x[0], x[1], x[2], x[3]);
+}
+#define PGL_STORE_NT 2                 // the cache policy word of the buffer store: "nt"
+
+template <int NP>                      // pieces of a page per thread: page_bytes = NP * 16 * PG_BLOCK  (7, 8: the LDS holds three workgroups per CU)
+__global__ __launch_bounds__(PG_BLOCK) __attribute__((amdgpu_waves_per_eu(NP > 6 ? 3 : PG_WAVES, NP > 6 ? 3 : PG_WAVES))) void k_pg_lean(const PgArgs A, uint32_t* __restrict__ n_listed,
+                                                                                                               uint32_t* __restrict__ listed, uint32_t* __restrict__ n_listed_next)
+{
+    constexpr uint32_t P = NP * 16u * PG_BLOCK;
+    constexpr uint32_t HEAD = P + PG_WIN_SLACK, HEAD_BYTES = 16u + 2u * PG_META_MAX, CORE = HEAD + HEAD_BYTES;
+    // one array, so that a piece is "16 bytes at an offset": the window and its slack | header and directory | the records' first 48 bytes
+    __shared__ __attribute__((aligned(16))) uint8_t lds[CORE + 48u * PG_META_MAX];
+    __shared__ uint32_t s_desc[P / 16];                                             // piece of the page -> src | len << 16
+    __shared__ __attribute__((aligned(16))) uint32_t s_mask[17][4];                 // the first `len` bytes of sixteen
+    __shared__ uint32_t s_rel[PG_META_MAX];                                         // a record's offset in the window (beyond it: ~0)
+    __shared__ uint32_t s_bad;
+    const uint32_t t = threadIdx.x, G = gridDim.x;
+    if (blockIdx.x == 0 && t == 0) *n_listed_next = 0u;            // nobody reads that counter during this call
+    if (t < 17u) {
+#pragma unroll
+        for (int d = 0; d < 4; d++) s_mask[t][d] = t >= 4u * d + 4u ? ~0u : t > 4u * d ? (1u << (8u * (t - 4u * d))) - 1u : 0u;
+    }
+
+    uint32_t k = blockIdx.x;                                       // (< n_pages: the grid is no larger)
+    const PglTab no_tab = {0u, 0u, 0ull, 0ull};
+    uint32_t z;
+    asm("v_mov_b32 %0, 0" : "=v"(z));
+    PgPage p_next = pg_page_of(A, k);
+    PglTab tab_after = k + G < A.n_pages ? pgl_tab_of(A, k + G, z) : no_tab;
+    PglWin W_next = pgl_win_of(A, p_next, P);
+    uint4 v[NP];
+#pragma unroll
+    for (int u = 0; u < NP; u++) {
+        const uint32_t i = u * PG_BLOCK + t;
+        v[u] = i < W_next.pieces ? pgl_load16(reinterpret_cast<const uint4*>(W_next.lo) + i) : make_uint4(0, 0, 0, 0);
+    }
+    PglMine m_next = pgl_mine_of(A, p_next, t, z);
+    // (the loop is entered as it is re-entered: with nothing but a page's stores in flight -- here none -- so that the compiler's count
+    //  of what the top may leave outstanding is the steady state's)
+    __builtin_amdgcn_s_waitcnt(0x0F70);                            // vmcnt(0)
+
+    for (; k < A.n_pages; k += G) {
+        const PgPage pg = p_next;
+        PglMine mine = m_next;
+        mine.S0 = pgl_rfl(mine.S0); mine.S_end = pgl_rfl(mine.S_end);
+        const PglWin W = W_next;
+        const uint32_t cnt = pg.cnt;
+        const uint32_t rec0 = 16u + a16(2u * cnt);
+        uint32_t used = cnt ? rec0 + pgl_diff(mine.S_end, mine.S0) - 2u * cnt : 16u;
+        if (used > P) used = P;
+        // ---- the window into LDS; where each record lies in it; the header
+#pragma unroll
+        for (int u = 0; u < NP; u++) {
+            const uint32_t i = u * PG_BLOCK + t;
+            if (i < W.pieces) reinterpret_cast<uint4*>(lds)[i] = v[u];
+        }
+        const uint64_t rel64 = (uint64_t)(A.bam + mine.off - W.lo);                 // (wraps to something huge in front of the window)
+        const uint32_t rel = rel64 < 16ull * W.pieces ? (uint32_t)rel64 : ~0u;
+        if (t < PG_META_MAX) s_rel[t] = rel;
+        if (t < HEAD_BYTES / 16u) reinterpret_cast<uint4*>(lds + HEAD)[t] = t ? make_uint4(0, 0, 0, 0) : make_uint4(cnt, pg.first, used, PG_MAGIC);
+        if (t == 0) s_bad = W.pieces ? 0u : 1u;
+        __syncthreads();
+        // ---- every load of the iteration: the window of the next page, its offsets and sums, the table entries of the page behind it.
+        // Nothing below uses what they bring before the loop's top.
+        p_next = pgl_page_of(A, tab_after);
+        if (k + G < A.n_pages) {
+            W_next = pgl_win_of(A, p_next, P);
+#pragma unroll
+            for (int u = 0; u < NP; u++) {
+                const uint32_t i = u * PG_BLOCK + t;
+                v[u] = i < W_next.pieces ? pgl_load16(reinterpret_cast<const uint4*>(W_next.lo) + i) : make_uint4(0, 0, 0, 0);
+            }
+            m_next = pgl_mine_of(A, p_next, t, z);
+        }
+        tab_after = (uint64_t)k + 2ull * G < A.n_pages ? pgl_tab_of(A, k + 2 * G, z) : no_tab;
+        // ---- phase A: a thread per record measures it out of the window and leaves what the pieces need
+        if (W.pieces && t < cnt) {
+            const uint32_t win_bytes = 16u * W.pieces;
+            bool good = rel != ~0u && rel + 36u <= win_bytes && (t == 0 || s_rel[t - 1] < rel);
+            if (good) {
+                uint32_t core[12];
+#pragma unroll
+                for (int d = 0; d < 12; d++) core[d] = pg_lds32(lds + rel + 4 * d);          // (behind the record: the slack, or older bytes)
+                const PgRec r = pg_classify(core, A.n_bytes, mine.off, false);
+                const uint32_t at = rec0 + pgl_diff(mine.S, mine.S0) - 2u * t;
+                const uint32_t src_len = 36u + r.lrn + 4u * r.n_cig + r.aux_len;             // the record in the stream: one run of bytes
+                good = r.kind == 0 && rel + src_len <= win_bytes && (at & 15u) == 0 && at >= rec0 && at + r.size <= used;
+                if (good) {
+                    *reinterpret_cast<uint16_t*>(lds + HEAD + 16 + 2 * t) = (uint16_t)(at >> 4);
+                    core[0] = r.size;
+                    core[3] &= 0xFFFFu;                                                      // kind 0
+                    core[6] = r.aux_len; core[7] = 0u; core[8] = 0u;
+#pragma unroll
+                    for (int d = 0; d < 3; d++)                                              // the first twelve bytes of the name
+                        core[9 + d] = r.lrn >= 4u * d + 4u ? core[9 + d] : r.lrn > 4u * d ? core[9 + d] & ((1u << (8u * (r.lrn - 4u * d))) - 1u) : 0u;
+#pragma unroll
+                    for (int d = 0; d < 12; d += 4) *reinterpret_cast<uint4*>(lds + CORE + 48u * t + 4u * d) = make_uint4(core[d], core[d + 1], core[d + 2], core[d + 3]);
+                    // its pieces: three out of the 48 bytes above, then the rest of the name, the CIGAR, the aux block
+                    uint32_t* d = s_desc + (at >> 4);
+                    const uint32_t name_end = 36u + r.lrn, cig = 4u * r.n_cig, c = a16(name_end);
+                    d[0] = (CORE + 48u * t) | (16u << 16); d[1] = (CORE + 48u * t + 16u) | (16u << 16); d[2] = (CORE + 48u * t + 32u) | (16u << 16);
+                    d += 3;
+                    for (uint32_t b = 48u; b < c; b += 16u) *d++ = (rel + b) | ((name_end - b < 16u ? name_end - b : 16u) << 16);
+                    for (uint32_t b = 0; b < cig; b += 16u) *d++ = (rel + name_end + b) | ((cig - b < 16u ? cig - b : 16u) << 16);
+                    for (uint32_t b = 0; b < r.aux_len; b += 16u) *d++ = (rel + name_end + cig + b) | ((r.aux_len - b < 16u ? r.aux_len - b : 16u) << 16);
+                }
+            }
+            if (!good) s_bad = 1u;
+        }
+        // ... and the pieces that belong to no record: header and directory, zeros behind the last record
+#pragma unroll
+        for (int u = 0; u < NP; u++) {
+            const uint32_t piece = u * PG_BLOCK + t;
+            if (piece < rec0 / 16u) s_desc[piece] = (HEAD + 16u * piece) | (16u << 16);
+            else if (piece >= used / 16u) s_desc[piece] = 0u;
+        }
+        __syncthreads();
+        // ---- phase B: the page, NP pieces per thread.  A piece is 16 bytes of `lds` from `src` on, of which the first `len` count.
+        const bool lean = __builtin_amdgcn_readfirstlane(s_bad) == 0u;
+        const __amdgpu_buffer_rsrc_t page = __builtin_amdgcn_make_buffer_rsrc(A.out + (uint64_t)k * P, 0, lean ? P : 0u, 0x00020000);
+#pragma unroll
+        for (int u = 0; u < NP; u++) {
+            const uint32_t piece = u * PG_BLOCK + t;
+            const uint32_t desc = lean ? s_desc[piece] : 0u;                                // (not lean: the table may hold anything)
+            const uint32_t src = desc & 0xFFFFu;
+            const uint4 m = *reinterpret_cast<const uint4*>(s_mask[desc >> 16 < 16u ? desc >> 16 : 16u]);
+            pgl_u32x4 o;
+            o[0] = pg_lds32(lds + src) & m.x; o[1] = pg_lds32(lds + src + 4) & m.y;
+            o[2] = pg_lds32(lds + src + 8) & m.z; o[3] = pg_lds32(lds + src + 12) & m.w;
+            __builtin_amdgcn_raw_buffer_store_b128(o, page, 16u * piece, 0, PGL_STORE_NT);
+        }
+        if (!lean && t == 0) listed[atomicAdd(n_listed, 1u)] = k;
+        __syncthreads();                                           // (the window and the tables are written again)
+    }
+}
+
 // The scratch of the size pass, all of it in pg_scan -- gci_bam_pages_write reads it in a later call, and the context's shared scan
 // scratch does not last that long: three totals (what the host reads back) | B_loc (n_rec + 1, u64) | the two rows of workgroup
 // totals (2 nb, u64) | S_loc (n_rec + 1, u32).
@@ -640,6 +868,21 @@ extern "C" int gci_bam_pages_size(gci_ctx* ctx, const uint8_t* d_stream, uint64_
     return GCI_OK;
 }
 
+typedef void (*pg_lean_fn)(const PgArgs, uint32_t*, uint32_t*, uint32_t*);
+static inline pg_lean_fn pg_lean_of(uint32_t page_bytes)           // (8192 .. GCI_PAGE_MAX_BYTES in steps of 4096: gci_bam_pages_size)
+{
+    static_assert(GCI_PAGE_MAX_BYTES == 8 * 16 * PG_BLOCK, "k_pg_lean is instantiated for 2 .. 8 pieces per thread");
+    switch (page_bytes / (16u * PG_BLOCK)) {
+    case 2: return k_pg_lean<2>;
+    case 3: return k_pg_lean<3>;
+    case 4: return k_pg_lean<4>;
+    case 5: return k_pg_lean<5>;
+    case 6: return k_pg_lean<6>;
+    case 7: return k_pg_lean<7>;
+    default: return k_pg_lean<8>;
+    }
+}
+
 extern "C" int gci_bam_pages_write(gci_ctx* ctx, const uint8_t* d_stream, uint64_t n_bytes, const uint64_t* d_rec_off, uint32_t n_rec,
                                    int has_seq, uint8_t* d_out, uint64_t cap)
 {
@@ -667,13 +910,39 @@ extern "C" int gci_bam_pages_write(gci_ctx* ctx, const uint8_t* d_stream, uint64
         ctx->pg_per_cu = per_cu > 0 ? (uint32_t)per_cu : 1u;
         ctx->pg_per_cu_page_bytes = ctx->pg_page_bytes;
     }
-    const uint32_t resident = ctx->pg_cus * ctx->pg_per_cu;
-    {
-        ProfScope _ps(ctx, GCI_PROF_PAGES_WRITE);
-        hipLaunchKernelGGL(k_pg_write, dim3(PG_PERSIST && resident < ctx->pg_n_pages ? resident : ctx->pg_n_pages), dim3(PG_BLOCK), lds, ctx->stream, A);
+    // (GCI_PAGES_GRID caps both grids: a test's few pages then go through the steady state of the loops)
+    const auto grid_of = [&](uint32_t per_cu) {
+        uint32_t g = ctx->pg_cus * per_cu;
+        if (!PG_PERSIST || g > ctx->pg_n_pages) g = ctx->pg_n_pages;
+        return ctx->pg_grid_cap && g > ctx->pg_grid_cap ? ctx->pg_grid_cap : g;
+    };
+    // the 16 zero bytes directly behind the blob (k_cigar_chunks fetches whole 16-byte pieces): k_pg_write's first workgroup writes them
+    uint8_t* const guard = d_out + need - 16;
+    ProfScope _ps(ctx, GCI_PROF_PAGES_WRITE);
+    if (has_seq) {                                                          // SEQ / QUAL between a record's runs: no page is lean
+        hipLaunchKernelGGL(k_pg_write, dim3(grid_of(ctx->pg_per_cu)), dim3(PG_BLOCK), lds, ctx->stream, A, (const uint32_t*)nullptr, (const uint32_t*)nullptr, guard);
         LAUNCHCHK("k_pg_write");
+        return GCI_OK;
     }
-    // the 16 zero bytes directly behind the blob (k_cigar_chunks fetches whole 16-byte pieces)
-    HIPCHK(hipMemsetAsync(d_out + need - 16, 0, 16, ctx->stream));
+    // the lean writer over all pages, k_pg_write over those it lists: two counters | the list.  The counters are used alternately --
+    // the lean writer of one call zeroes the one of the next, so no memset is launched per call (as K1's counters, k_filter.hip)
+    const size_t cap_before = ctx->pg_list.cap;
+    GCI_TRY(gci_ensure(ctx, ctx->pg_list, 16 + 4 * (size_t)ctx->pg_n_pages));
+    if (ctx->pg_list.cap != cap_before) { HIPCHK(hipMemsetAsync(ctx->pg_list.p, 0, 16, ctx->stream)); ctx->pg_parity = 0; }
+    uint32_t* const counters = (uint32_t*)ctx->pg_list.p;
+    uint32_t* const listed = counters + 4;
+    const uint32_t par = ctx->pg_parity;
+    const pg_lean_fn lean = pg_lean_of(ctx->pg_page_bytes);
+    if (ctx->pg_lean_page_bytes != ctx->pg_page_bytes) {
+        int per_cu = 0;
+        HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, lean, PG_BLOCK, 0));
+        ctx->pg_lean_per_cu = per_cu > 0 ? (uint32_t)per_cu : 1u;
+        ctx->pg_lean_page_bytes = ctx->pg_page_bytes;
+    }
+    ctx->pg_parity ^= 1u;
+    hipLaunchKernelGGL(lean, dim3(grid_of(ctx->pg_lean_per_cu)), dim3(PG_BLOCK), 0, ctx->stream, A, counters + par, listed, counters + (par ^ 1u));
+    LAUNCHCHK("k_pg_lean");
+    hipLaunchKernelGGL(k_pg_write, dim3(grid_of(ctx->pg_per_cu)), dim3(PG_BLOCK), lds, ctx->stream, A, (const uint32_t*)(counters + par), (const uint32_t*)listed, guard);
+    LAUNCHCHK("k_pg_write");
     return GCI_OK;
 }
