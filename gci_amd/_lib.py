@@ -24,6 +24,8 @@ HIST_MAX_BINS = 65536         # GCI_HIST_MAX_BINS: the largest n_bins of gci_dep
 HIST_CHUNK_TILES = 64         # GCI_HIST_CHUNK_TILES: tiles of one window a workgroup of k_depth_hist accumulates before it flushes
 HIST_LDS_BINS = 4096          # GCI_HIST_LDS_BINS (k_hist.hip): the bins a workgroup keeps in LDS; those above go to global memory per run
 COVER_CHUNK_OPS = 2048        # GCI_COVER_CHUNK_OPS: CIGAR operations a wave of the cover kernels takes
+FATE_NAMES = ("none", "secondary", "supplementary", "mapq", "clip", "identity", "kept", "error")    # GCI_FATE_*: gci_bam_fate's classes
+FATE_CLASSES = len(FATE_NAMES)
 PROF_COUNT = 19
 PROF_DEPTH_SCAN = 5          # k_tile_build: the pass that writes the depth track (+ text)
 PROF_TILE_PASS1 = 13
@@ -104,6 +106,10 @@ EXPORTS = [
                                    POINTER(c_uint64), c_void_p]),
     ("gci_bam_cover_write", c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_int, c_void_p, c_uint64, c_void_p]),
     ("gci_track_add", c_int, [c_void_p, c_void_p, c_void_p]),
+    ("gci_bam_fate", c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_int, c_void_p, c_int32, c_int, c_double, c_double, c_void_p,
+                             c_void_p, c_void_p]),
+    ("gci_bam_cover_size_sel", c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_int, c_void_p, c_int32, c_uint32, c_int, c_int,
+                                       c_void_p, c_uint32, POINTER(c_uint64), c_void_p]),
     ("gci_decode_status", c_int, [c_uint64, POINTER(c_uint32)]),
     ("gci_name_hash", c_uint64, [c_void_p, c_uint32]),
     ("gci_pack_names", c_int, [c_void_p, POINTER(JoinFile), c_void_p, c_uint64, c_void_p]),

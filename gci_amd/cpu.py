@@ -41,7 +41,8 @@ gci_memcpy_d2h gci_memset gci_layout_set gci_layout_total gci_layout_offsets gci
 gci_depth_build gci_gap_mask gci_max2 gci_issue_scan gci_issue_scan_windows gci_depth_classes gci_depth_text_size gci_depth_text_write
 gci_depth_sum gci_range_sums gci_depth_deflate_from_build gci_depth_deflate_size gci_depth_deflate_write gci_depth_text_index
 gci_depth_text_parse gci_sdepth_index gci_sdepth_parse gci_depth_gz_scan gci_depth_gz_runs gci_depth_gz_expand gci_depth_runs_count
-gci_depth_runs_write gci_bedgraph_size gci_bedgraph_write gci_depth_hist gci_bam_cover_size gci_bam_cover_write gci_track_add""".split()
+gci_depth_runs_write gci_bedgraph_size gci_bedgraph_write gci_depth_hist gci_bam_cover_size gci_bam_cover_write gci_track_add
+gci_bam_fate gci_bam_cover_size_sel""".split()
 _PROTO = {name: (name, res, args) for name, res, args in _lib.EXPORTS}
 EXPORTS = [_PROTO[name] for name in _SEAMS] + [("gci_cpu_option", c_int, [c_void_p, c_char_p, c_int])]
 
@@ -152,17 +153,23 @@ class CpuEngine:
 
     # ---- bam_depth.py (k_cover.hip's twins)
     def bam_cover(self, stream: np.ndarray, offs: np.ndarray, ref_sel: np.ndarray, has_seq: bool = True, excl_flags: int = 0x704,
-                  min_mapq: int = 0, count_del: bool = False, check: bool = True, cap: Optional[int] = None) -> np.ndarray:
+                  min_mapq: int = 0, count_del: bool = False, check: bool = True, cap: Optional[int] = None,
+                  classes: Optional[np.ndarray] = None, mask: int = 0) -> np.ndarray:
         """device.Engine.bam_cover's twin: the covered reference bases of every record as IVL_DTYPE (`end` = the last covered base).
-        cap: the room offered to the write call (default: what the size call asked for)."""
+        cap: the room offered to the write call (default: what the size call asked for).  classes (bam_fate's bytes) and mask: only the
+        records whose class is a bit of the mask (gci_bam_cover_size_sel)."""
         stream = np.ascontiguousarray(stream, dtype=np.uint8)
         offs = np.ascontiguousarray(offs, dtype=np.uint64)
         ref_sel = np.ascontiguousarray(ref_sel, dtype=np.int32)
         n = ctypes.c_uint64(0)
         self.last_status = np.zeros(1, dtype=np.uint64)
-        self._chk(self.lib.gci_bam_cover_size(self.ctx, _p(stream), stream.shape[0], _p(offs), offs.shape[0], int(has_seq), _p(ref_sel),
-                                              ref_sel.shape[0], int(excl_flags), int(min_mapq), int(count_del), ctypes.byref(n),
-                                              _p(self.last_status)), "gci_bam_cover_size")
+        head = (self.ctx, _p(stream), stream.shape[0], _p(offs), offs.shape[0], int(has_seq), _p(ref_sel), ref_sel.shape[0], int(excl_flags),
+                int(min_mapq), int(count_del))
+        if classes is None:
+            self._chk(self.lib.gci_bam_cover_size(*head, ctypes.byref(n), _p(self.last_status)), "gci_bam_cover_size")
+        else:
+            classes = np.ascontiguousarray(classes, dtype=np.uint8)
+            self._chk(self.lib.gci_bam_cover_size_sel(*head, _p(classes), int(mask), ctypes.byref(n), _p(self.last_status)), "gci_bam_cover_size_sel")
         if check:
             self._status(self.last_status, "gci_bam_cover_size")
         room = int(n.value) if cap is None else int(cap)
@@ -170,6 +177,22 @@ class CpuEngine:
         self._chk(self.lib.gci_bam_cover_write(self.ctx, _p(stream), stream.shape[0], _p(offs), offs.shape[0], int(has_seq), _p(out), room,
                                                _p(self.last_status)), "gci_bam_cover_write")
         return out[:int(n.value)]
+
+    def bam_fate(self, stream: np.ndarray, offs: np.ndarray, ref_sel: np.ndarray, map_qual: int, clip_percent: float, iden_percent: float,
+                 has_seq: bool = True, check: bool = True):
+        """device.Engine.bam_fate's twin -> (class byte per record, records per class)."""
+        stream = np.ascontiguousarray(stream, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        ref_sel = np.ascontiguousarray(ref_sel, dtype=np.int32)
+        cls = np.zeros(max(offs.shape[0], 1), dtype=np.uint8)
+        counts = np.zeros(_lib.FATE_CLASSES, dtype=np.uint64)
+        self.last_status = np.zeros(1, dtype=np.uint64)
+        self._chk(self.lib.gci_bam_fate(self.ctx, _p(stream), stream.shape[0], _p(offs), offs.shape[0], int(has_seq), _p(ref_sel), ref_sel.shape[0],
+                                        int(map_qual), float(clip_percent), float(iden_percent), _p(cls), _p(counts), _p(self.last_status)),
+                  "gci_bam_fate")
+        if check:
+            self._status(self.last_status, "gci_bam_fate")
+        return cls[:offs.shape[0]], counts
 
     def track_add(self, acc: np.ndarray, add: np.ndarray) -> np.ndarray:
         self._chk(self.lib.gci_track_add(self.ctx, _p(acc), _p(add)), "gci_track_add")

@@ -253,6 +253,70 @@ int cover_parse(const uint8_t* bam, uint64_t n_bytes, uint64_t off, bool has_seq
     return GCI_OK;
 }
 
+// filter_depth.py, one record: its class (include/gci_hip.h: gci_bam_fate) and what the status word says of it (GCI_OK for a record of the
+// classes none .. kept).  The tests and their order are filter_record's.
+int fate_record(const uint8_t* bam, uint64_t n_bytes, uint64_t off, bool has_seq, const int32_t* ref_sel, int32_t n_ref, int map_qual,
+                double clip_percent, double iden_percent, uint8_t& cls)
+{
+    cls = GCI_FATE_ERROR;
+    if (off > n_bytes || n_bytes - off < 36) return GCI_E_MALFORMED;
+    const uint8_t* p = bam + off;
+    const int32_t block_size = (int32_t)rd32(p), ref_id = (int32_t)rd32(p + 4), pos = (int32_t)rd32(p + 8);
+    const uint32_t l_read_name = p[12];
+    const int mapq = p[13];
+    const uint32_t n_cigar = rd16(p + 16), flag = rd16(p + 18);
+    const int32_t l_seq = (int32_t)rd32(p + 20);
+    const uint64_t rec_end = off + 4 + (uint64_t)(uint32_t)block_size;
+    const uint64_t cig_off = off + 36 + l_read_name;
+    const uint64_t aux_off = cig_off + 4ull * n_cigar + (has_seq ? (((uint64_t)(uint32_t)l_seq + 1) >> 1) + (uint64_t)(uint32_t)l_seq : 0ull);
+    if (block_size < 32 || rec_end > n_bytes || l_seq < 0 || aux_off > rec_end) return GCI_E_MALFORMED;
+    if ((flag & 0x4u) || ref_id < 0 || ref_id >= n_ref || pos < 0 || ref_sel[ref_id] < 0) { cls = GCI_FATE_NONE; return GCI_OK; }
+    if (flag & 0x100u) { cls = GCI_FATE_SECONDARY; return GCI_OK; }          // GCI.py:156, test by test
+    if (flag & 0x800u) { cls = GCI_FATE_SUPPLEMENTARY; return GCI_OK; }
+    if (mapq < map_qual) { cls = GCI_FATE_MAPQ; return GCI_OK; }
+    const uint8_t* end = bam + rec_end;
+    const uint8_t* nm_p = nullptr;                                          // the first NM and the first CG tag (bam_aux_get)
+    const uint8_t* cg_p = nullptr;
+    for (const uint8_t* q = bam + aux_off; q + 3 <= end;) {
+        const int64_t sz = aux_value_size(q + 3, end, q[2]);
+        if (sz < 0 || q + 3 + sz > end) break;
+        if (q[0] == 'N' && q[1] == 'M' && !nm_p) nm_p = q + 2;
+        if (q[0] == 'C' && q[1] == 'G' && !cg_p) cg_p = q + 2;
+        q += 3 + sz;
+    }
+    int64_t NM = 0;
+    const bool nm_bad = nm_p ? !nm_value(nm_p, NM) : false;
+    const uint8_t* ops = bam + cig_off;
+    uint32_t n_ops = n_cigar;
+    if (n_cigar > 0) {
+        const uint32_t op0 = rd32(ops);
+        if ((op0 & 0xF) == 4 && (op0 >> 4) == (uint32_t)l_seq && cg_p && cg_p[0] == 'B' && (cg_p[1] == 'I' || cg_p[1] == 'i')) {
+            const uint32_t cg_len = rd32(cg_p + 2);
+            if (cg_len >= n_cigar && cg_len < (1u << 29)) { ops = cg_p + 6; n_ops = cg_len; }
+        }
+    }
+    int64_t M = 0, I = 0, D = 0, S = 0;
+    for (uint32_t k = 0; k < n_ops; k++) {
+        const uint32_t v = rd32(ops + 4ull * k);
+        const int64_t len = v >> 4;
+        switch (v & 0xF) {
+        case 0: case 7: case 8: M += len; break;
+        case 1: I += len; break;
+        case 2: D += len; break;
+        case 4: S += len; break;
+        default: break;
+        }
+    }
+    if (!nm_p) return GCI_E_NO_NM;
+    if (nm_bad) return GCI_E_BAD_NM_TYPE;
+    const int64_t den1 = M + I + S, den2 = M + I + D;
+    if (den1 == 0) return GCI_E_ZERO_DIV;
+    if (!((double)S / (double)den1 <= clip_percent)) { cls = GCI_FATE_CLIP; return GCI_OK; }
+    if (den2 == 0) return GCI_E_ZERO_DIV;
+    cls = (double)(den2 - NM) / (double)den2 >= iden_percent ? GCI_FATE_KEPT : GCI_FATE_IDENTITY;
+    return GCI_OK;
+}
+
 // the maximal runs of covering operations of one record: emit(start, end) with `end` the last covered base, both clamped to `lim`;
 // false when an operation code 9 - 15 turns up
 template <typename F>
@@ -637,8 +701,9 @@ int gci_max2(gci_ctx* ctx, const int32_t* a, const int32_t* b, int32_t* out)
 }
 
 /* ---- bam_depth.py: the reference bases the records cover (k_cover.hip's twins; one interval per maximal run of a RECORD here) --------- */
-int gci_bam_cover_size(gci_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, const uint64_t* rec_off, uint32_t n_rec, int has_seq,
-                       const int32_t* ref_sel, int32_t n_ref, uint32_t excl_flags, int min_mapq, int count_del, uint64_t* h_n_ivl, uint64_t* status)
+int gci_bam_cover_size_sel(gci_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, const uint64_t* rec_off, uint32_t n_rec, int has_seq,
+                           const int32_t* ref_sel, int32_t n_ref, uint32_t excl_flags, int min_mapq, int count_del, const uint8_t* cls,
+                           uint32_t class_mask, uint64_t* h_n_ivl, uint64_t* status)
 {
     if (!ctx || !h_n_ivl || !status || n_ref < 0 || (n_rec && (!bam || !rec_off || !ref_sel))) return GCI_E_INVALID;
     const int lst = need_layout(ctx);
@@ -652,6 +717,7 @@ int gci_bam_cover_size(gci_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, const
         for (uint64_t i = lo; i < hi; i++) {
             gci_ctx::CoverRec& r = ctx->cover_rec[i];
             if (cover_parse(bam, n_bytes, rec_off[i], has_seq != 0, ref_sel, n_ref, excl_flags, min_mapq, r) != GCI_OK) { report(st, (uint32_t)i, GCI_E_MALFORMED); continue; }
+            if (r.contig >= 0 && cls && !(cls[i] < 32u && ((class_mask >> cls[i]) & 1u))) r = gci_ctx::CoverRec{0, 0, -1, 0};   // not a class of the mask
             if (r.contig < 0) continue;
             uint64_t n = 0;
             if (!cover_walk(bam, r, count_del != 0, 0, [&](int32_t, int32_t) { n++; })) report(st, (uint32_t)i, GCI_E_MALFORMED);
@@ -663,6 +729,35 @@ int gci_bam_cover_size(gci_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, const
     ctx->cover_valid = true; ctx->cover_count_del = count_del != 0; ctx->cover_stream = bam; ctx->cover_off = rec_off;
     *status = ctx->cover_status;
     *h_n_ivl = ctx->cover_ivl0[n_rec];
+    return GCI_OK;
+}
+
+int gci_bam_cover_size(gci_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, const uint64_t* rec_off, uint32_t n_rec, int has_seq,
+                       const int32_t* ref_sel, int32_t n_ref, uint32_t excl_flags, int min_mapq, int count_del, uint64_t* h_n_ivl, uint64_t* status)
+{
+    return gci_bam_cover_size_sel(ctx, bam, n_bytes, rec_off, n_rec, has_seq, ref_sel, n_ref, excl_flags, min_mapq, count_del, nullptr, 0, h_n_ivl,
+                                  status);
+}
+
+/* ---- filter_depth.py: the class of every record (k_fate.hip's twin: a record at a time) ------------------------------------------------ */
+int gci_bam_fate(gci_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, const uint64_t* rec_off, uint32_t n_rec, int has_seq, const int32_t* ref_sel,
+                 int32_t n_ref, int map_qual, double clip_percent, double iden_percent, uint8_t* cls, uint64_t* h_counts, uint64_t* status)
+{
+    if (!ctx || !h_counts || !status || n_ref < 0 || (n_rec && (!bam || !rec_off || !ref_sel || !cls))) return GCI_E_INVALID;
+    std::atomic<uint64_t> st{~0ull};
+    std::atomic<uint64_t> counts[GCI_FATE_CLASSES];
+    for (auto& c : counts) c.store(0);
+    parallel_blocks(ctx->threads, n_rec, 4096, [&](uint64_t lo, uint64_t hi) {
+        uint64_t mine[GCI_FATE_CLASSES] = {0};
+        for (uint64_t i = lo; i < hi; i++) {
+            const int code = fate_record(bam, n_bytes, rec_off[i], has_seq != 0, ref_sel, n_ref, map_qual, clip_percent, iden_percent, cls[i]);
+            if (code != GCI_OK) report(st, (uint32_t)i, code);
+            mine[cls[i]]++;
+        }
+        for (int c = 0; c < GCI_FATE_CLASSES; c++) counts[c].fetch_add(mine[c]);
+    });
+    for (int c = 0; c < GCI_FATE_CLASSES; c++) h_counts[c] = counts[c].load();
+    *status = st.load();
     return GCI_OK;
 }
 

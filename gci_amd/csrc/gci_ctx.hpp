@@ -136,6 +136,7 @@ struct gci_ctx {
     int cover_count_del = 0;
     const void* cover_stream = nullptr;
     const void* cover_off = nullptr;
+    DevBuf fate_rec, fate_chunk;            // k_fate.hip: per record (parse, NM, chunk counts and their scan) and per chunk (base sums)
     void* h_pinned = nullptr;               // staging for small uploads
     size_t h_pinned_cap = 0;
     // optional per-kernel HIP-event timing (gci_profile_*)

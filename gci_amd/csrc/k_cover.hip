@@ -1,6 +1,8 @@
 // k_cover.hip -- the reference bases the records of a BAM stream cover: `samtools depth -a` without its base-quality options, as
 // intervals for the depth build (gci_bam_cover_size / _write), and the element-wise sum of two tracks (gci_track_add).
 //
+// gci_bam_cover_size_sel is the size call over the records of chosen classes only (gci_bam_fate's class bytes: k_fate.hip).
+//
 // Input as for gci_bam_filter: the inflated stream (or a heads stream) and the record offsets.  The unit of work is a CHUNK of at
 // most GCI_COVER_CHUNK_OPS CIGAR operations, never a record: an ONT record holds 10^3 - 10^5 operations.  Three steps:
 //   k_cover_parse   one lane per record: bounds, the skip decision (flag, MAPQ, refID, pos, contig), where the operations lie (the
@@ -12,20 +14,8 @@
 // M, = or X (D too with count_del) and longer than zero; D (without count_del) and N of non-zero length end a run; I, S, H, P,
 // zero-length operations and the codes 9 - 15 leave a run as it is.
 //
-// CIGAR words lie at any byte phase of the stream: a lane loads the naturally aligned dword its operation begins in, takes the next
-// one from its neighbour lane and re-aligns the two in registers (v_alignbyte), as k_cigar_chunks and pg_src_dword do.
-#include "gci_ctx.hpp"
-
-#define CV_OPS GCI_COVER_CHUNK_OPS
-static_assert(CV_OPS % 64 == 0, "a chunk is whole rounds of one operation per lane");
-
-struct CoverRec {
-    uint64_t ops_off;              // byte offset of the first operation word in the stream
-    uint32_t n_ops;
-    int32_t contig;                // index among the selected contigs (the record is not skipped when it has chunks)
-    int32_t pos;
-    uint32_t pad;
-};
+// The chunk helpers (where a chunk lies, its operation words at any byte phase) are gci_cover_chunks.hpp, shared with k_fate.hip.
+#include "gci_cover_chunks.hpp"
 
 struct CoverRecScratch {           // carved out of ctx->cover_rec
     unsigned long long* status;
@@ -79,42 +69,12 @@ static inline CoverChunkScratch cv_chunk_scratch(gci_ctx* ctx, uint64_t n)
     return s;
 }
 
-__device__ __forceinline__ void cv_report(unsigned long long* status, uint32_t rec, int code)
-{
-    atomicMin(status, ((unsigned long long)rec << 8) | (unsigned long long)(uint8_t)(-code));
-}
-
-__device__ __forceinline__ uint32_t cv_rd16(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
-__device__ __forceinline__ uint32_t cv_rd32(const uint8_t* p) { return cv_rd16(p) | (cv_rd16(p + 2) << 16); }
-
-// size of an aux value of type t at p; -1: malformed / past the end of the record (as the record filter walks them)
-__device__ __forceinline__ int64_t cv_aux_size(const uint8_t* p, const uint8_t* end, uint8_t t)
-{
-    switch (t) {
-    case 'A': case 'c': case 'C': return 1;
-    case 's': case 'S': return 2;
-    case 'i': case 'I': case 'f': return 4;
-    case 'Z': case 'H': {
-        const uint8_t* q = p;
-        while (q < end && *q) q++;
-        return q < end ? (q - p) + 1 : -1;
-    }
-    case 'B': {
-        if (p + 5 > end) return -1;
-        const uint8_t sub = p[0];
-        const int64_t n = cv_rd32(p + 1);
-        const int64_t es = (sub == 'c' || sub == 'C') ? 1 : (sub == 's' || sub == 'S') ? 2 : (sub == 'i' || sub == 'I' || sub == 'f') ? 4 : -1;
-        return es < 0 ? -1 : 5 + n * es;
-    }
-    default: return -1;
-    }
-}
-
 // ---- step 1: one lane per record ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(BLOCK) void k_cover_parse(const uint8_t* __restrict__ bam, uint64_t n_bytes, const uint64_t* __restrict__ rec_off,
                                                        uint32_t n_rec, int has_seq, const int32_t* __restrict__ ref_sel, int32_t n_ref,
-                                                       uint32_t excl_flags, int min_mapq, CoverRec* __restrict__ recs,
-                                                       uint32_t* __restrict__ nch, unsigned long long* __restrict__ status)
+                                                       uint32_t excl_flags, int min_mapq, const uint8_t* __restrict__ cls, uint32_t class_mask,
+                                                       CoverRec* __restrict__ recs, uint32_t* __restrict__ nch,
+                                                       unsigned long long* __restrict__ status)
 {
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n_rec) return;
@@ -136,7 +96,8 @@ __global__ __launch_bounds__(BLOCK) void k_cover_parse(const uint8_t* __restrict
         const uint64_t aux_off = cig_off + 4ull * n_cigar + (has_seq ? (((uint64_t)(uint32_t)l_seq + 1) >> 1) + (uint64_t)(uint32_t)l_seq : 0ull);
         if (block_size < 32 || rec_end > n_bytes || l_seq < 0 || aux_off > rec_end) {
             cv_report(status, i, GCI_E_MALFORMED);
-        } else if (!(flag & excl_flags) && mapq >= min_mapq && ref_id >= 0 && ref_id < n_ref && pos >= 0 && ref_sel[ref_id] >= 0) {
+        } else if (!(flag & excl_flags) && mapq >= min_mapq && ref_id >= 0 && ref_id < n_ref && pos >= 0 && ref_sel[ref_id] >= 0 &&
+                   (!cls || (cls[i] < 32u && ((class_mask >> cls[i]) & 1u)))) {       // (gci_bam_cover_size_sel: only the classes of the mask)
             r.contig = ref_sel[ref_id];
             r.pos = pos;
             r.ops_off = cig_off;
@@ -169,55 +130,6 @@ __global__ __launch_bounds__(BLOCK) void k_cover_parse(const uint8_t* __restrict
 }
 
 // ---- the walk of one chunk, shared by the two passes ------------------------------------------------------------------------------
-
-// the record of chunk c: the largest i with chunk0[i] <= c (records without chunks share their value with the record behind them)
-__device__ __forceinline__ uint32_t cv_rec_of_chunk(const unsigned long long* __restrict__ chunk0, uint32_t n_rec, unsigned long long c)
-{
-    uint32_t lo = 0, hi = n_rec;                       // chunk0[lo] <= c < chunk0[hi]
-    while (hi - lo > 1) {
-        const uint32_t mid = lo + ((hi - lo) >> 1);
-        if (chunk0[mid] <= c) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// the dword at byte offset o of the stream (bam + o is 4-byte aligned); bytes at or beyond n_bytes read as zero and are not touched
-__device__ __forceinline__ uint32_t cv_dword(const uint8_t* __restrict__ bam, uint64_t n_bytes, uint64_t o)
-{
-    if (o + 4 <= n_bytes) return *reinterpret_cast<const uint32_t*>(bam + o);
-    uint32_t w = 0;
-    for (int k = 0; k < 4; k++) if (o + k < n_bytes) w |= (uint32_t)bam[o + k] << (8 * k);
-    return w;
-}
-
-struct CvChunk {
-    uint64_t first;                // byte offset of the aligned dword the chunk's first operation begins in
-    uint32_t b;                    // ... and the byte phase of the operation words inside their dwords
-    uint32_t n;                    // operations of the chunk
-};
-
-__device__ __forceinline__ CvChunk cv_chunk_of(const uint8_t* __restrict__ bam, const CoverRec& r, uint32_t ci)
-{
-    CvChunk c;
-    const uint64_t at = r.ops_off + 4ull * (uint64_t)ci * CV_OPS;
-    c.b = (uint32_t)(((uintptr_t)bam + at) & 3u);
-    c.first = at - c.b;                                // (at >= 36)
-    const uint64_t left = (uint64_t)r.n_ops - (uint64_t)ci * CV_OPS;
-    c.n = (uint32_t)(left < CV_OPS ? left : CV_OPS);
-    return c;
-}
-
-// operation word k = 64 * round + lane of the chunk (0 for a lane beyond the chunk's operations); every lane of the wave calls it
-__device__ __forceinline__ uint32_t cv_op_word(const uint8_t* __restrict__ bam, uint64_t n_bytes, const CvChunk& c, uint32_t k, int lane)
-{
-    const bool valid = k < c.n;
-    const uint64_t o = c.first + 4ull * k;
-    const uint32_t w0 = valid ? cv_dword(bam, n_bytes, o) : 0u;
-    if (c.b == 0) return w0;                           // (uniform)
-    uint32_t w1 = (uint32_t)__shfl((int)w0, (lane + 1) & 63, 64);
-    if (valid && (lane == 63 || k + 1 >= c.n)) w1 = cv_dword(bam, n_bytes, o + 4);     // nobody holds the dword that completes this word
-    return __builtin_amdgcn_alignbyte(w1, w0, c.b);
-}
 
 struct CvClass { bool cov, brk, bad; uint32_t ref_len; };
 
@@ -341,9 +253,9 @@ __global__ __launch_bounds__(BLOCK) void k_cover_write(const uint8_t* __restrict
 }
 
 // ---- exports ----------------------------------------------------------------------------------------------------------------------
-extern "C" int gci_bam_cover_size(gci_ctx* ctx, const uint8_t* d_stream, uint64_t n_bytes, const uint64_t* d_rec_off, uint32_t n_rec, int has_seq,
-                                  const int32_t* d_ref_sel, int32_t n_ref, uint32_t excl_flags, int min_mapq, int count_del, uint64_t* h_n_ivl,
-                                  uint64_t* d_status)
+extern "C" int gci_bam_cover_size_sel(gci_ctx* ctx, const uint8_t* d_stream, uint64_t n_bytes, const uint64_t* d_rec_off, uint32_t n_rec, int has_seq,
+                                      const int32_t* d_ref_sel, int32_t n_ref, uint32_t excl_flags, int min_mapq, int count_del,
+                                      const uint8_t* d_class, uint32_t class_mask, uint64_t* h_n_ivl, uint64_t* d_status)
 {
     if (!ctx || !h_n_ivl || !d_status || n_ref < 0 || (n_rec && (!d_stream || !d_rec_off || !d_ref_sel))) return GCI_E_INVALID;
     if (!ctx->n_contigs) return GCI_E_NO_LAYOUT;
@@ -355,7 +267,7 @@ extern "C" int gci_bam_cover_size(gci_ctx* ctx, const uint8_t* d_stream, uint64_
     unsigned long long n_chunks = 0, n_ivl = 0;
     if (n_rec) {
         hipLaunchKernelGGL(k_cover_parse, dim3((n_rec + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, ctx->stream, d_stream, n_bytes, d_rec_off, n_rec, has_seq,
-                           d_ref_sel, n_ref, excl_flags, min_mapq, R.recs, R.nch, R.status);
+                           d_ref_sel, n_ref, excl_flags, min_mapq, d_class, class_mask, R.recs, R.nch, R.status);
         LAUNCHCHK("k_cover_parse");
         GCI_TRY((device_exclusive_scan<uint32_t, unsigned long long>(ctx, R.nch, R.chunk0, R.blk, (int64_t)n_rec, true)));
         HIPCHK(hipMemcpyAsync(&n_chunks, R.chunk0 + n_rec, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -379,6 +291,14 @@ extern "C" int gci_bam_cover_size(gci_ctx* ctx, const uint8_t* d_stream, uint64_
     ctx->cover_stream = d_stream; ctx->cover_off = d_rec_off;
     *h_n_ivl = n_ivl;
     return GCI_OK;
+}
+
+extern "C" int gci_bam_cover_size(gci_ctx* ctx, const uint8_t* d_stream, uint64_t n_bytes, const uint64_t* d_rec_off, uint32_t n_rec, int has_seq,
+                                  const int32_t* d_ref_sel, int32_t n_ref, uint32_t excl_flags, int min_mapq, int count_del, uint64_t* h_n_ivl,
+                                  uint64_t* d_status)
+{
+    return gci_bam_cover_size_sel(ctx, d_stream, n_bytes, d_rec_off, n_rec, has_seq, d_ref_sel, n_ref, excl_flags, min_mapq, count_del, nullptr, 0,
+                                  h_n_ivl, d_status);
 }
 
 extern "C" int gci_bam_cover_write(gci_ctx* ctx, const uint8_t* d_stream, uint64_t n_bytes, const uint64_t* d_rec_off, uint32_t n_rec, int has_seq,

@@ -18,6 +18,7 @@
 //     staged head.  Same decisions, same status codes.
 // SEQ and QUAL are skipped by pointer arithmetic and never touched.
 #include "gci_ctx.hpp"
+#include "gci_ratio.hpp"
 #include <stdlib.h>
 
 #ifndef G
@@ -97,24 +98,6 @@ __device__ __forceinline__ bool has_zero_byte(uint32_t x) { return ((x - 0x01010
 // The decision of GCI.py:163-168; fills r and returns a gci_status (GCI_OK also when filtered).  With M = bases under M, =
 // and X together, the op totals enter it only as S, den1 = M + I + S, den2 = M + I + D and rlen = M + D + N
 // (mm = NM - (I + D), GCI.py:164, appears as M - mm = den2 - NM).
-// (double)a / (double)b  <=  c  (le) or  >=  c  (!le), b != 0: the reference's IEEE f64 division and comparison (GCI.py:165),
-// bit for bit.  An f64 division is ~40 instructions a wave executes for all its lanes, and almost no record is anywhere near a
-// threshold: a single-precision quotient (relative error < 1e-6) decides whenever it is further than 1e-4 from the threshold --
-// rounding is monotonic, so the f64 quotient falls on the same side -- and only the records in between take the division.
-__device__ __forceinline__ bool ratio_cmp(int64_t a, int64_t b, double c, bool le)
-{
-    if (((a < 0 ? -a : a) | b) >> 30 == 0) {                     // both convert to f32 through the 32-bit path
-        const float x = (float)(int32_t)a * __builtin_amdgcn_rcpf((float)(int32_t)b);
-        const float cf = (float)c, m = 1e-4f * fmaxf(1.0f, fabsf(x));
-        if (c == c && fabs(c) < 1e30) {                          // (a NaN or absurd threshold: the exact comparison below)
-            if (x < cf - m) return le;
-            if (x > cf + m) return !le;
-        }
-    }
-    const double q = (double)a / (double)b;
-    return le ? q <= c : q >= c;
-}
-
 __device__ __forceinline__ int decide4(gci_rec& r, int64_t S, int64_t den1, int64_t den2, int64_t rlen, bool have_nm,
                                        bool nm_bad_type, int64_t NM, int32_t pos, int32_t contig, int32_t l_seq,
                                        uint32_t n_cigar_field, int mapq, int mq_cutoff, double clip_percent,

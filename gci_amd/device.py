@@ -340,20 +340,40 @@ class Engine:
 
     # ---- bam_depth.py: the reference bases the records cover (include/gci_hip.h: gci_bam_cover_*, gci_track_add) -------
     def bam_cover(self, d_stream: Buffer, d_rec_off: Buffer, has_seq: bool, d_ref_sel: Buffer, excl_flags: int = 0x704,
-                  min_mapq: int = 0, count_del: bool = False, check: bool = True, rec_idx_base: int = 0) -> Buffer:
+                  min_mapq: int = 0, count_del: bool = False, check: bool = True, rec_idx_base: int = 0,
+                  classes: Optional[Buffer] = None, mask: int = 0) -> Buffer:
         """-> intervals int32 [n, 4] (contig, start, last covered base, 0) of the records of an inflated BAM stream (has_seq) or a
-        heads stream: what `samtools depth -a` counts, for depth_build with flank 0.  Needs the layout of the selected contigs."""
+        heads stream: what `samtools depth -a` counts, for depth_build with flank 0.  Needs the layout of the selected contigs.
+        classes (bam_fate's bytes) and mask: only the records whose class is a bit of the mask (gci_bam_cover_size_sel)."""
         n = int(d_rec_off.shape[0])
         n_ivl = ctypes.c_uint64(0)
-        self._chk(self.lib.gci_bam_cover_size(self.ctx, self._p(d_stream), int(d_stream.shape[0]), self._p(d_rec_off), n, int(has_seq),
-                                              self._p(d_ref_sel), int(d_ref_sel.shape[0]), int(excl_flags), int(min_mapq),
-                                              int(bool(count_del)), ctypes.byref(n_ivl), self._p(self._status)), "gci_bam_cover_size")
+        head = (self.ctx, self._p(d_stream), int(d_stream.shape[0]), self._p(d_rec_off), n, int(has_seq), self._p(d_ref_sel),
+                int(d_ref_sel.shape[0]), int(excl_flags), int(min_mapq), int(bool(count_del)))
+        if classes is None:
+            self._chk(self.lib.gci_bam_cover_size(*head, ctypes.byref(n_ivl), self._p(self._status)), "gci_bam_cover_size")
+        else:
+            self._chk(self.lib.gci_bam_cover_size_sel(*head, self._p(classes), int(mask), ctypes.byref(n_ivl), self._p(self._status)),
+                      "gci_bam_cover_size_sel")
         if check:
             self._raise_status(self._status.item(), "gci_bam_cover_size", rec_idx_base)
         out = self.T.empty((max(int(n_ivl.value), 1), 4), self.T.int32, self.device)
         self._chk(self.lib.gci_bam_cover_write(self.ctx, self._p(d_stream), int(d_stream.shape[0]), self._p(d_rec_off), n, int(has_seq),
                                                self._p(out), int(n_ivl.value), self._p(self._status)), "gci_bam_cover_write")
         return out[:int(n_ivl.value)]
+
+    def bam_fate(self, d_stream: Buffer, d_rec_off: Buffer, has_seq: bool, d_ref_sel: Buffer, map_qual: int, clip_percent: float,
+                 iden_percent: float, check: bool = True, rec_idx_base: int = 0):
+        """-> (class byte per record uint8 [n] on the device, records per class as a list of FATE_CLASSES ints): which test of read_sam
+        drops every record of an inflated BAM stream (has_seq) or a heads stream (include/gci_hip.h: gci_bam_fate)."""
+        n = int(d_rec_off.shape[0])
+        cls = self.T.empty(max(n, 1), self.T.uint8, self.device)
+        counts = (ctypes.c_uint64 * _lib.FATE_CLASSES)()
+        self._chk(self.lib.gci_bam_fate(self.ctx, self._p(d_stream), int(d_stream.shape[0]), self._p(d_rec_off), n, int(has_seq),
+                                        self._p(d_ref_sel), int(d_ref_sel.shape[0]), int(map_qual), float(clip_percent), float(iden_percent),
+                                        self._p(cls), counts, self._p(self._status)), "gci_bam_fate")
+        if check:
+            self._raise_status(self._status.item(), "gci_bam_fate", rec_idx_base)
+        return cls[:n], [int(c) for c in counts]
 
     def track_add(self, acc: Buffer, add: Buffer) -> Buffer:
         """acc += add over the layout."""

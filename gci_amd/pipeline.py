@@ -1188,23 +1188,23 @@ def same_sq_table(bam_files: Sequence[str]):
     return first
 
 
-class _CoverVisitor(StreamVisitor):
-    """The covered bases of one file after another: the intervals of every piece (gci_bam_cover_*) collect on the device; beyond
-    `budget` of them they are built into a scratch track that is added to the file's (gci_track_add).  All of that runs on the
-    engine, and in the stream, of the piece; file_done() -- on the caller's engine, when the ingestion has ordered the two -- turns
-    what is left into the file's track."""
+class _IntervalCollector:
+    """Intervals of one file on their way into a track: the parts of every piece collect on the device; flush() builds them into a
+    scratch track that is added to the file's (gci_track_add); finish() turns what is left into the file's track."""
 
-    def __init__(self, main: Engine, opts: CoverOpts, budget: int):
-        self.main, self.opts, self.budget = main, opts, max(int(budget), 1)
+    def __init__(self):
         self.flushes = 0
-        self.begin_file()
+        self.reset()
 
-    def begin_file(self) -> None:
+    def reset(self) -> None:
         self.parts: List[Buffer] = []
         self.n_ivl = 0
         self.track: Optional[Buffer] = None
 
-    abort_file = begin_file
+    def add(self, ivl: Buffer) -> None:
+        if int(ivl.shape[0]):
+            self.parts.append(ivl)
+            self.n_ivl += int(ivl.shape[0])
 
     def _build(self, engine: Engine) -> Optional[Buffer]:
         """The collected intervals as depths in a new track; None when there is nothing to build."""
@@ -1217,7 +1217,7 @@ class _CoverVisitor(StreamVisitor):
             engine.depth_build(ivl, None, 0, track)
         return track
 
-    def _flush(self, engine: Engine) -> None:
+    def flush(self, engine: Engine) -> None:
         built = self._build(engine)
         if built is None:
             return
@@ -1226,6 +1226,48 @@ class _CoverVisitor(StreamVisitor):
             self.track = built
         else:
             engine.track_add(self.track, built)
+
+    def hand_over(self, stream) -> None:
+        """What was made in another engine's stream order is used in `stream` from finish() on."""
+        for t in self.parts + ([self.track] if self.track is not None else []):
+            t.record_stream(stream)
+
+    def finish(self, engine: Engine) -> Buffer:
+        """The file's track: a file that needed no flush is built straight into a new one."""
+        if self.track is None:
+            track = self._build(engine)
+            if track is None:                              # no interval at all
+                track = engine.new_track()
+                track.zero_()
+        else:
+            self.flush(engine)
+            track = self.track
+        self.reset()
+        return track
+
+
+def _file_record_error(engine: Engine, e: GciError, what: str, rec_idx_base: int) -> GciError:
+    """e.rec counts inside the piece (the ingestion adds what lies in front: _rebased); the text names the record of the FILE."""
+    return GciError(e.status, "%s: %s (record %d of the file)" % (what, engine.lib.gci_strerror(e.status).decode(), e.rec + rec_idx_base), rec=e.rec)
+
+
+class _CoverVisitor(StreamVisitor):
+    """The covered bases of one file after another: the intervals of every piece (gci_bam_cover_*) collect on the device; beyond
+    `budget` of them they are built into a scratch track that is added to the file's (_IntervalCollector).  All of that runs on the
+    engine, and in the stream, of the piece; file_done() -- on the caller's engine, when the ingestion has ordered the two -- turns
+    what is left into the file's track."""
+
+    def __init__(self, main: Engine, opts: CoverOpts, budget: int):
+        self.main, self.opts, self.budget = main, opts, max(int(budget), 1)
+        self.collector = _IntervalCollector()
+
+    flushes = property(lambda self: self.collector.flushes)
+    track = property(lambda self: self.collector.track)
+
+    def begin_file(self) -> None:
+        self.collector.reset()
+
+    abort_file = begin_file
 
     def visit(self, engine, d_stream, d_off, has_seq, ref_sel, rec_idx_base) -> None:
         if engine.lengths != self.main.lengths:            # (the walk engine: a context of its own)
@@ -1236,31 +1278,16 @@ class _CoverVisitor(StreamVisitor):
         except GciError as e:
             if e.rec < 0:
                 raise
-            # e.rec counts inside the piece (the ingestion adds what lies in front: _rebased); the text names the record of the FILE
-            raise GciError(e.status, "gci_bam_cover_size: %s (record %d of the file)"
-                           % (engine.lib.gci_strerror(e.status).decode(), e.rec + rec_idx_base), rec=e.rec) from None
-        if int(ivl.shape[0]):
-            self.parts.append(ivl)
-            self.n_ivl += int(ivl.shape[0])
-        if self.n_ivl > self.budget:
-            self._flush(engine)
+            raise _file_record_error(engine, e, "gci_bam_cover_size", rec_idx_base) from None
+        self.collector.add(ivl)
+        if self.collector.n_ivl > self.budget:
+            self.collector.flush(engine)
         if engine is not self.main:                        # (made in that engine's stream order, used in the caller's from file_done on)
-            for t in self.parts + ([self.track] if self.track is not None else []):
-                t.record_stream(self.main.stream)
+            self.collector.hand_over(self.main.stream)
 
     def file_done(self) -> Buffer:
-        """The file's track (the caller's engine and stream): a file that needed no flush is built straight into a new one."""
-        engine = self.main
-        if self.track is None:
-            track = self._build(engine)
-            if track is None:                              # no interval at all
-                track = engine.new_track()
-                track.zero_()
-        else:
-            self._flush(engine)
-            track = self.track
-        self.begin_file()
-        return track
+        """The file's track (the caller's engine and stream)."""
+        return self.collector.finish(self.main)
 
 
 def bam_raw_depth(engine: Engine, bam_files: Sequence[str], chrs: Sequence[str] = (), opts: Optional[CoverOpts] = None, threads: int = 1,
@@ -1295,6 +1322,148 @@ def bam_raw_depth(engine: Engine, bam_files: Sequence[str], chrs: Sequence[str] 
     depths = DepthTracks(engine, targets_length, total)
     depths.cover_flushes = visitor.flushes
     return depths
+
+
+# ==============================================================================================
+# filter_depth.py: the per-base depth of what the record filter drops, test by test
+# ==============================================================================================
+
+FATE_NAMES = _lib.FATE_NAMES
+FATE_WANTED = ("secondary", "supplementary", "mapq", "clip", "identity", "kept")      # the classes a run can ask for, in the filter's order
+
+
+class FateOpts:
+    """The record filter's options that decide a record's class (-mq, -cp, -ip) and how coverage is counted (-J)."""
+
+    def __init__(self, map_qual: int = 30, clip_percent: float = 0.1, iden_percent: float = 0.9, count_del: bool = False):
+        self.map_qual, self.clip_percent, self.iden_percent, self.count_del = int(map_qual), float(clip_percent), float(iden_percent), bool(count_del)
+
+
+class TracksDoNotFit(MemoryError):
+    """The depth tracks a run of bam_filter_depth needs are more than the device has free."""
+
+    def __init__(self, n_tracks: int, track_bytes: int, free_bytes: int):
+        self.n_tracks, self.track_bytes, self.free_bytes = n_tracks, track_bytes, free_bytes
+        super().__init__("%d depth tracks of %d bytes each do not fit into the %d bytes the device has free" % (n_tracks, track_bytes, free_bytes))
+
+
+def device_memory_free(engine: Engine) -> int:
+    """What the process can still take on the engine's device: what the driver has free, and what the arena holds but has not handed out."""
+    dev = engine.device.index or 0
+    free, total = ctypes.c_uint64(0), ctypes.c_uint64(0)
+    r, u, n = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint32(0)
+    engine._chk(engine.lib.gci_dev_mem_info(dev, ctypes.byref(free), ctypes.byref(total)), "gci_dev_mem_info")
+    engine.lib.gci_dev_arena_info(dev, ctypes.byref(r), ctypes.byref(u), ctypes.byref(n))
+    return int(free.value) + max(int(r.value) - int(u.value), 0)
+
+
+class FilterDepth:
+    """What bam_filter_depth returns: tracks[class name] = the DepthTracks of every wanted class, counts[k][class id] = the records of
+    file k per class (FATE_NAMES), flushes = how often intervals were built into a track before their file was through."""
+
+    def __init__(self, tracks: Dict[str, DepthTracks], counts: List[List[int]], flushes: int):
+        self.tracks, self.counts, self.flushes = tracks, counts, flushes
+
+
+class _FateVisitor(StreamVisitor):
+    """Next to _CoverVisitor: per piece ONE gci_bam_fate call (every CIGAR read once for the verdicts), then for every wanted class
+    gci_bam_cover_size_sel / _write with that class's mask into that class's collector -- a record that is not selected makes no
+    chunk, so the walks of all classes together read every CIGAR once more.  The interval budget is shared: beyond it every collector
+    that holds intervals builds them into its track."""
+
+    def __init__(self, main: Engine, opts: FateOpts, classes: Sequence[int], budget: int):
+        self.main, self.opts, self.classes, self.budget = main, opts, list(classes), max(int(budget), 1)
+        self.collectors = {c: _IntervalCollector() for c in self.classes}
+        self.counts = [0] * _lib.FATE_CLASSES
+
+    flushes = property(lambda self: sum(c.flushes for c in self.collectors.values()))
+
+    def begin_file(self) -> None:
+        for c in self.collectors.values():
+            c.reset()
+        self.counts = [0] * _lib.FATE_CLASSES
+
+    abort_file = begin_file
+
+    def visit(self, engine, d_stream, d_off, has_seq, ref_sel, rec_idx_base) -> None:
+        if engine.lengths != self.main.lengths:            # (the walk engine: a context of its own)
+            engine.set_layout(self.main.lengths)
+        o = self.opts
+        what = "gci_bam_fate"
+        try:
+            with phases.gpu("record fate"):
+                cls, counts = engine.bam_fate(d_stream, d_off, has_seq, ref_sel, o.map_qual, o.clip_percent, o.iden_percent)
+            what = "gci_bam_cover_size_sel"
+            for c in self.classes:
+                if counts[c]:                              # (`none` is never asked for: 0x4 stays among the excluded flags)
+                    with phases.gpu("record cover"):
+                        self.collectors[c].add(engine.bam_cover(d_stream, d_off, has_seq, ref_sel, 0x4, 0, o.count_del, classes=cls, mask=1 << c))
+        except GciError as e:
+            if e.rec < 0:
+                raise
+            raise _file_record_error(engine, e, what, rec_idx_base) from None
+        self.counts = [a + b for a, b in zip(self.counts, counts)]
+        if sum(c.n_ivl for c in self.collectors.values()) > self.budget:
+            for c in self.collectors.values():
+                c.flush(engine)
+        if engine is not self.main:                        # (made in that engine's stream order, used in the caller's from file_done on)
+            for c in self.collectors.values():
+                c.hand_over(self.main.stream)
+
+    def file_done(self) -> Dict[int, Buffer]:
+        """The file's track of every wanted class (the caller's engine and stream)."""
+        return {c: col.finish(self.main) for c, col in self.collectors.items()}
+
+
+def bam_filter_depth(engine: Engine, bam_files: Sequence[str], chrs: Sequence[str], opts: Optional[FateOpts], threads: int,
+                     classes: Sequence[str], ivl_budget: Optional[int] = None) -> FilterDepth:
+    """Per wanted class of the record filter (FATE_WANTED: the first test of read_sam a record fails, or `kept`) the per-base depth of
+    that class's records over `bam_files`, counted as bam_raw_depth counts it (CIGAR-aware, no flank; opts.count_del for deletions), so
+    that the six tracks add up, base for base, to bam_raw_depth with excl = 0x4.  Several files add per class; the contigs are the
+    first file's (restricted by `chrs`), a file with another @SQ table raises SqMismatch.  A record the reference would have raised on
+    (no NM tag, a zero denominator) or a malformed one raises GciError with .path and the record's index in the file.
+    Raises TracksDoNotFit before anything is read when the tracks of the run are more than the device has free."""
+    opts = opts or FateOpts()
+    ids = []
+    for name in classes:
+        if name not in FATE_WANTED:
+            raise ValueError('"%s" is not one of %s' % (name, ", ".join(FATE_WANTED)))
+        if FATE_NAMES.index(name) not in ids:
+            ids.append(FATE_NAMES.index(name))
+    if not ids:
+        raise ValueError("no class selected")
+    first = same_sq_table(bam_files)
+    targets_length = _targets_of(first, list(chrs))
+    targets = list(targets_length.keys())
+    if not targets:
+        raise ValueError("no contig selected")
+    engine.set_layout([targets_length[t] for t in targets])
+    # a track per class, one more while intervals are built in parts -- and with several files a second one per class, the file's next
+    # to the sum of the files before it
+    n_tracks = len(ids) * (2 if len(bam_files) > 1 else 1) + 1
+    track_bytes, free = 4 * int(engine.total), device_memory_free(engine)
+    if n_tracks * track_bytes > free:
+        raise TracksDoNotFit(n_tracks, track_bytes, free)
+    visitor = _FateVisitor(engine, opts, ids, COVER_IVL_BUDGET if ivl_budget is None else ivl_budget)
+    totals: Dict[int, Buffer] = {}
+    counts = []
+    for path in bam_files:
+        visitor.begin_file()
+        try:
+            with phases.wall("bam_fate[%s]" % os.path.basename(path)):
+                bam_join_input(engine, path, targets, visitor, threads)
+        except BaseException as e:
+            visitor.abort_file()
+            if isinstance(e, GciError):
+                e.path = path                             # (which file the record index counts in: the command line says so)
+            raise
+        counts.append(list(visitor.counts))
+        for c, track in visitor.file_done().items():
+            if c in totals:
+                engine.track_add(totals[c], track)
+            else:
+                totals[c] = track
+    return FilterDepth({FATE_NAMES[c]: DepthTracks(engine, targets_length, totals[c]) for c in ids}, counts, visitor.flushes)
 
 
 # ==============================================================================================

@@ -20,6 +20,7 @@
  *   gci_depth_runs_*, gci_bedgraph_*   depth_to_bedgraph.py: a track as bedGraph lines (no counterpart in the reference)
  *   gci_depth_hist      depth_dist.py: the depth histogram, sum, min, max and count of windows (no counterpart in the reference)
  *   gci_bam_cover_*, gci_track_add     bam_depth.py: the unfiltered per-base depth of BAM files, `samtools depth -a` (no counterpart in the reference)
+ *   gci_bam_fate, gci_bam_cover_size_sel   filter_depth.py: which test of read_sam drops a record (GCI.py:152-168), and the depth of every such class
  *   gci_paf_filter_device   filter(), PAF path        GCI.py:211-254  (+ helpers 49-61, 64-96)
  *
  * Conventions
@@ -277,6 +278,43 @@ int gci_bam_cover_size(gci_ctx* ctx, const uint8_t* d_stream, uint64_t n_bytes, 
 int gci_bam_cover_write(gci_ctx* ctx, const uint8_t* d_stream, uint64_t n_bytes, const uint64_t* d_rec_off, uint32_t n_rec, int has_seq,
                         gci_ivl* d_out, uint64_t cap, uint64_t* d_status);
 int gci_track_add(gci_ctx* ctx, int32_t* d_acc, const int32_t* d_add);
+
+/* ---- filter_depth.py: what becomes of every record in the record filter, and the depth of each class (k_fate.hip, k_cover.hip) ----
+ * gci_bam_fate: the same input as gci_bam_filter (has_seq as for gci_bam_cover_size).  d_class[i] = the class of record i, named
+ * after the FIRST test of read_sam (GCI.py:152-168) the record fails, in the reference's order:
+ *   GCI_FATE_NONE           flag & 0x4, refID < 0 or >= n_ref, pos < 0 or d_ref_sel[refID] < 0: the skip rule of gci_bam_cover_size with
+ *                           excl_flags = 0x4 -- a record the reference's fetch never yields
+ *   GCI_FATE_SECONDARY      flag & 0x100
+ *   GCI_FATE_SUPPLEMENTARY  flag & 0x800 (and not 0x100)
+ *   GCI_FATE_MAPQ           mapq < map_qual
+ *   GCI_FATE_CLIP           not S / (M + I + S) <= clip_percent           (M: the bases under M, = and X together)
+ *   GCI_FATE_IDENTITY       not (M - mm) / (M + I + D) >= iden_percent    (mm = NM - (I + D))
+ *   GCI_FATE_KEPT           reaches GCI.py:166: exactly the records gci_bam_filter marks GCI_REC_PASS
+ *   GCI_FATE_ERROR          a record *d_status reports: one that runs past the end of the stream or contradicts its block_size, or one
+ *                           the reference would have raised on
+ * The last three use the IEEE f64 quotients, the first-NM rule and the CG:B,I restore of gci_bam_filter, and *d_status is the word
+ * gci_bam_filter (rec_idx_base 0) gives for the same input and thresholds whenever no reported record has pos < 0: no NM
+ * (GCI_E_NO_NM), NM of a non-integer type, M + I + S == 0, the clip test, M + I + D == 0, the identity test, in this order.  A record of
+ * the first four classes is settled by its core fields: no tag is looked for, nothing is divided, its CIGAR is not read.
+ * h_counts[c]: the records of class c (GCI_FATE_CLASSES entries, host).  Needs no layout.  Synchronises.
+ * gci_bam_cover_size_sel: gci_bam_cover_size over the records whose class is in the mask -- a record is also skipped when bit
+ *   d_class[i] of class_mask is clear (d_class == NULL: no record is; that is gci_bam_cover_size).  gci_bam_cover_write follows it
+ *   unchanged.  A record that is not selected makes no chunk: walking class after class reads every CIGAR once in total. */
+#define GCI_FATE_NONE 0
+#define GCI_FATE_SECONDARY 1
+#define GCI_FATE_SUPPLEMENTARY 2
+#define GCI_FATE_MAPQ 3
+#define GCI_FATE_CLIP 4
+#define GCI_FATE_IDENTITY 5
+#define GCI_FATE_KEPT 6
+#define GCI_FATE_ERROR 7
+#define GCI_FATE_CLASSES 8
+int gci_bam_fate(gci_ctx* ctx, const uint8_t* d_stream, uint64_t n_bytes, const uint64_t* d_rec_off, uint32_t n_rec, int has_seq,
+                 const int32_t* d_ref_sel, int32_t n_ref, int map_qual, double clip_percent, double iden_percent, uint8_t* d_class,
+                 uint64_t* h_counts, uint64_t* d_status);
+int gci_bam_cover_size_sel(gci_ctx* ctx, const uint8_t* d_stream, uint64_t n_bytes, const uint64_t* d_rec_off, uint32_t n_rec, int has_seq,
+                           const int32_t* d_ref_sel, int32_t n_ref, uint32_t excl_flags, int min_mapq, int count_del, const uint8_t* d_class,
+                           uint32_t class_mask, uint64_t* h_n_ivl, uint64_t* d_status);
 
 /* ---- R5: cross-file join --------------------------------------------------------------------
  * h_files in reference order (PAF files, then BAM files, each in command-line order).
