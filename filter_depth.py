@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""`python filter_depth.py [-d DIR] [-o PREFIX] [--chrs a,b] [-mq INT] [-ip FLOAT] [-cp FLOAT] [-J] [--classes a,b] [-t INT] [-f] a.bam
-[b.bam ...]`: the per-base depth of what the record filter of GCI.py drops, test by test, as `{DIR}/{PREFIX}.{class}.depth.gz` and the
+"""`python filter_depth.py [-d DIR] [-o PREFIX] [--chrs a,b] [-mq INT] [-ip FLOAT] [-cp FLOAT] [-J] [--classes a,b] [-t INT] [-f]
+[--join [-op FLOAT] [--mq-cutoff INT] [--cover N]] a.bam [b.bam | b.paf ...]`: the per-base depth of what the record filter of GCI.py
+drops, test by test -- and with `--join` of what its join across files drops --, as `{DIR}/{PREFIX}.{class}.depth.gz` and the
 record counts as `{DIR}/{PREFIX}.filter.txt`, from the BAM bytes, by the gfx950 HIP path in gci_amd/ -- see gci_amd/filterdepth_cli.py.
 
 Like GCI.py, a run imports no tensor library: its HBM buffers, streams and events are the library's own (gci_amd/hbm.py), and the

@@ -26,6 +26,10 @@ HIST_LDS_BINS = 4096          # GCI_HIST_LDS_BINS (k_hist.hip): the bins a workg
 COVER_CHUNK_OPS = 2048        # GCI_COVER_CHUNK_OPS: CIGAR operations a wave of the cover kernels takes
 FATE_NAMES = ("none", "secondary", "supplementary", "mapq", "clip", "identity", "kept", "error")    # GCI_FATE_*: gci_bam_fate's classes
 FATE_CLASSES = len(FATE_NAMES)
+JOIN_FATE_NAMES = ("shadowed", "unpaired", "contig", "overlap", "joined")    # GCI_FATE_SHADOWED ..: gci_name_join_fate's bytes of a passing record
+JOIN_FATE_FIRST = 8
+JOIN_FATE_CLASSES = 16        # GCI_JOIN_FATE_CLASSES: entries of a row of gci_name_join_fate's counts
+ALL_FATE_NAMES = FATE_NAMES + JOIN_FATE_NAMES                                # a class id is its index here
 PROF_COUNT = 19
 PROF_DEPTH_SCAN = 5          # k_tile_build: the pass that writes the depth track (+ text)
 PROF_TILE_PASS1 = 13
@@ -118,6 +122,8 @@ EXPORTS = [
     ("gci_join_mode", c_int, [c_void_p, c_int]),
     ("gci_name_join_count", c_int, [c_void_p, POINTER(JoinFile), c_int, c_double, c_void_p, c_void_p, c_uint32, c_void_p,
                               c_void_p, c_int]),
+    ("gci_name_join_fate", c_int, [c_void_p, POINTER(JoinFile), c_int, c_double, POINTER(c_void_p), c_void_p, c_void_p]),
+    ("gci_fate_refine", c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),
     ("gci_depth_deflate_from_build", c_int, [c_void_p, c_void_p]),
     ("gci_depth_deflate_size", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("gci_depth_deflate_write", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p,

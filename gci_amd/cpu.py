@@ -42,7 +42,7 @@ gci_depth_build gci_gap_mask gci_max2 gci_issue_scan gci_issue_scan_windows gci_
 gci_depth_sum gci_range_sums gci_depth_deflate_from_build gci_depth_deflate_size gci_depth_deflate_write gci_depth_text_index
 gci_depth_text_parse gci_sdepth_index gci_sdepth_parse gci_depth_gz_scan gci_depth_gz_runs gci_depth_gz_expand gci_depth_runs_count
 gci_depth_runs_write gci_bedgraph_size gci_bedgraph_write gci_depth_hist gci_bam_cover_size gci_bam_cover_write gci_track_add
-gci_bam_fate gci_bam_cover_size_sel""".split()
+gci_bam_fate gci_bam_cover_size_sel gci_name_join_fate gci_fate_refine""".split()
 _PROTO = {name: (name, res, args) for name, res, args in _lib.EXPORTS}
 EXPORTS = [_PROTO[name] for name in _SEAMS] + [("gci_cpu_option", c_int, [c_void_p, c_char_p, c_int])]
 
@@ -219,6 +219,33 @@ class CpuEngine:
         self._chk(self.lib.gci_name_join(self.ctx, arr, len(files), ovlp, _p(cm), _p(out), out.shape[0], _p(n), _p(st)), "gci_name_join")
         self._status(st, "gci_name_join")
         return out[:int(n[0])]
+
+    def name_join_fate(self, files: Sequence[Tuple[np.ndarray, np.ndarray, np.ndarray, int]], ovlp: float, guard: int = 0):
+        """device.Engine.name_join_fate's twin; files as for name_join -> (per file the byte of every record, followed by `guard`
+        bytes of 0xA5 the call must leave alone; uint64 [n, JOIN_FATE_CLASSES] records per file and byte; the status word)."""
+        arr = (_JoinFile * len(files))()
+        keep, fate = [], []
+        for k, (recs, base, off, delta) in enumerate(files):
+            recs = np.ascontiguousarray(recs, dtype=REC_DTYPE)
+            base = np.ascontiguousarray(base, dtype=np.uint8)
+            off = np.ascontiguousarray(off, dtype=np.uint64)
+            keep += [recs, base, off]
+            arr[k] = _JoinFile(recs.ctypes.data, recs.shape[0], int(delta), base.ctypes.data, off.ctypes.data)
+            fate.append(np.full(recs.shape[0] + guard, 0xA5, dtype=np.uint8))
+        ptrs = (c_void_p * len(files))(*[f.ctypes.data for f in fate])
+        counts = np.full((len(files) + 1, _lib.JOIN_FATE_CLASSES), 7, dtype=np.uint64)       # (one row more than the call may write)
+        st = np.zeros(1, dtype=np.uint64)
+        self._chk(self.lib.gci_name_join_fate(self.ctx, arr, len(files), float(ovlp), ptrs, _p(counts), _p(st)), "gci_name_join_fate")
+        if (counts[-1] != 7).any():
+            raise CpuError(-1, "gci_name_join_fate wrote behind its counts")
+        return fate, counts[:-1], int(st[0])
+
+    def fate_refine(self, classes: np.ndarray, join_fate: np.ndarray) -> int:
+        """gci_fate_refine over `classes` in place -> the status word."""
+        st = np.zeros(1, dtype=np.uint64)
+        n = min(classes.shape[0], join_fate.shape[0])
+        self._chk(self.lib.gci_fate_refine(self.ctx, _p(classes), _p(join_fate), n, _p(st)), "gci_fate_refine")
+        return int(st[0])
 
     # ---- R6, R8, R9
     def depth_build(self, ivl: np.ndarray, flank: int, track: Optional[np.ndarray] = None) -> np.ndarray:

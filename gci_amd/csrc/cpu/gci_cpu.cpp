@@ -21,6 +21,7 @@
 #include <atomic>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 struct gci_ctx {
@@ -630,6 +631,91 @@ int gci_name_join(gci_ctx* ctx, const gci_join_file* files, int n_files, double 
     });
     *n_out = n.load();
     *status = st.load();
+    return GCI_OK;
+}
+
+/* ---- filter_depth.py --join: what the join does with every record (k_join.hip's gci_name_join_fate, k_fate.hip's gci_fate_refine) as
+ * plain loops: one map from a name to its winners, the statement of include/gci_hip.h name by name, then the records once more ------- */
+int gci_name_join_fate(gci_ctx* ctx, const gci_join_file* files, int n_files, double ovlp_percent, uint8_t* const* fate, uint64_t* counts,
+                       uint64_t* status)
+{
+    if (!ctx || !files || n_files < 1 || n_files > GCI_MAX_JOIN_FILES || !fate || !counts || !status) return GCI_E_INVALID;
+    for (int f = 0; f < n_files; f++)
+        if (files[f].n_recs && (!files[f].d_recs || !files[f].d_name_base || !files[f].d_name_off || !fate[f])) return GCI_E_INVALID;
+    struct Name { uint64_t last[GCI_MAX_JOIN_FILES]; bool hq; uint8_t verdict; };
+    std::unordered_map<std::string, Name> names;
+    auto key_of = [&](const gci_join_file& F, uint32_t i) {                              // the name's bytes, and its hash as the device compares it
+        const gci_rec& r = F.d_recs[i];
+        std::string k((const char*)(F.d_name_base + F.d_name_off[i] + F.name_delta), r.name_len);
+        k.append((const char*)&r.name_hash, 8);
+        return k;
+    };
+    auto order_of = [](const gci_rec& r, uint32_t i) { return (((uint64_t)(uint32_t)r.contig << 32) | i) + 1; };   // contig by contig, file order inside
+    for (int f = 0; f < n_files; f++) {
+        for (uint32_t i = 0; i < files[f].n_recs; i++) {
+            const gci_rec& r = files[f].d_recs[i];
+            if (!(r.flags & GCI_REC_PASS)) continue;
+            auto it = names.find(key_of(files[f], i));
+            if (it == names.end()) it = names.emplace(key_of(files[f], i), Name{{0}, false, 0}).first;
+            it->second.last[f] = std::max(it->second.last[f], order_of(r, i));
+            if (r.flags & GCI_REC_HQ) it->second.hq = true;
+        }
+    }
+    uint64_t st = ~0ull;
+    for (auto& kv : names) {
+        Name& n = kv.second;
+        if (n_files == 1) { n.verdict = GCI_FATE_JOINED; continue; }
+        bool comm = true;
+        for (int f = 0; f < n_files; f++) comm = comm && n.last[f] != 0;
+        bool have = n.last[0] != 0 && (n.hq || comm);
+        uint8_t why = GCI_FATE_UNPAIRED;
+        int32_t contig = 0, s = 0, e = 0;
+        if (have) { const gci_rec& r = files[0].d_recs[(uint32_t)(n.last[0] - 1)]; contig = r.contig; s = r.start; e = r.end; }
+        for (int f = 1; f < n_files; f++) {
+            if (!n.last[f]) continue;
+            const gci_rec& r = files[f].d_recs[(uint32_t)(n.last[f] - 1)];
+            if (have) {
+                if (r.contig != contig) { have = false; why = GCI_FATE_CONTIG; continue; }
+                const int32_t ms = std::max(r.start, s), me = std::min(r.end, e);
+                if (r.qlen == 0) {                                                       // ZeroDivisionError, GCI.py:292: the fold ends here
+                    st = std::min(st, ((uint64_t)r.rec_idx << 8) | (uint64_t)(uint8_t)(-GCI_E_ZERO_DIV));
+                    have = false; why = GCI_FATE_OVERLAP;
+                    break;
+                }
+                if ((double)((int64_t)me - (int64_t)ms) / (double)r.qlen < ovlp_percent) { have = false; why = GCI_FATE_OVERLAP; }
+                else { s = ms; e = me; }
+            } else if (n.hq) { have = true; contig = r.contig; s = r.start; e = r.end; }
+        }
+        n.verdict = have ? (uint8_t)GCI_FATE_JOINED : why;
+    }
+    for (int f = 0; f < n_files; f++) {
+        uint64_t* row = counts + (size_t)f * GCI_JOIN_FATE_CLASSES;
+        for (int c = 0; c < GCI_JOIN_FATE_CLASSES; c++) row[c] = 0;
+        for (uint32_t i = 0; i < files[f].n_recs; i++) {
+            const gci_rec& r = files[f].d_recs[i];
+            uint8_t c = 0;
+            if (r.flags & GCI_REC_PASS) {
+                const Name& n = names.find(key_of(files[f], i))->second;
+                c = n.last[f] == order_of(r, i) ? n.verdict : (uint8_t)GCI_FATE_SHADOWED;
+            }
+            fate[f][i] = c;
+            row[c]++;
+        }
+    }
+    *status = st;
+    return GCI_OK;
+}
+
+int gci_fate_refine(gci_ctx* ctx, uint8_t* cls, const uint8_t* join_fate, uint32_t n_rec, uint64_t* status)
+{
+    if (!ctx || !status || (n_rec && (!cls || !join_fate))) return GCI_E_INVALID;
+    uint64_t st = ~0ull;
+    for (uint32_t i = 0; i < n_rec; i++) {
+        const bool joined = join_fate[i] >= GCI_FATE_SHADOWED && join_fate[i] <= GCI_FATE_JOINED;
+        if (cls[i] == GCI_FATE_KEPT && joined) cls[i] = join_fate[i];
+        else if (cls[i] == GCI_FATE_KEPT || join_fate[i] != 0) st = std::min(st, ((uint64_t)i << 8) | (uint64_t)(uint8_t)(-GCI_E_INVALID));
+    }
+    *status = st;
     return GCI_OK;
 }
 

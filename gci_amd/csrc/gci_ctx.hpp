@@ -70,6 +70,7 @@ struct gci_ctx {
     bool build_runs_armed = false;          // ... gci_depth_deflate_from_build() has said that track is untouched: the next size / write pair may use them
     // join scratch
     DevBuf join_table, join_last, join_hq;
+    DevBuf join_fate;                       // gci_name_join_fate: the counts of every (file, class), then a verdict byte per slot
     DevBuf join_bucket;                     // partitioned join: per bucket its survivor count, first slot and output offset
     DevBuf part_a, part_b, part_hist, part_blk;   // partitioned join: entry ping-pong, histograms + segment table, scan totals
     DevBuf route_tab;                       // gci_route_*: per (part, chunk) counts and their scan

@@ -12,7 +12,8 @@
 //   k_fate_sum      one wave per chunk: the bases under S, M / = / X, I and D, summed over the wave; no atomics
 //   k_fate_decide   one lane per record: adds the record's chunk sums, runs the two ratio tests in the order of decide4 (k_filter.hip),
 //                   writes the class byte; the records per class go through an LDS histogram per workgroup, flushed once
-// with an exclusive scan of the chunk counts between the first two.
+// with an exclusive scan of the chunk counts between the first two.  gci_fate_refine (filter_depth.py --join) then moves every `kept`
+// byte to the class the cross-file join gave the record (k_join.hip: gci_name_join_fate), one lane per record.
 #include "gci_cover_chunks.hpp"
 #include "gci_ratio.hpp"
 
@@ -202,6 +203,31 @@ __global__ __launch_bounds__(BLOCK) void k_fate_decide(uint32_t n_rec, const uns
     }
     __syncthreads();
     if (threadIdx.x < GCI_FATE_CLASSES && hist[threadIdx.x]) atomicAdd(counts + threadIdx.x, (unsigned long long)hist[threadIdx.x]);
+}
+
+// ---- gci_fate_refine: a `kept` record takes the class the cross-file join gave it (gci_name_join_fate) -------------------------------
+__global__ __launch_bounds__(BLOCK) void k_fate_refine(uint8_t* __restrict__ cls, const uint8_t* __restrict__ join_fate, uint32_t n_rec,
+                                                       unsigned long long* __restrict__ status)
+{
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n_rec) return;
+    const uint32_t c = cls[i], j = join_fate[i];
+    if (c == GCI_FATE_KEPT) {
+        if (j >= GCI_FATE_SHADOWED && j <= GCI_FATE_JOINED) cls[i] = (uint8_t)j;
+        else cv_report(status, i, GCI_E_INVALID);                                // the join saw no passing record here: the two passes disagree
+    } else if (j != 0) cv_report(status, i, GCI_E_INVALID);                      // ... or a passing one where the classes see none
+}
+
+extern "C" int gci_fate_refine(gci_ctx* ctx, uint8_t* d_class, const uint8_t* d_join_fate, uint32_t n_rec, uint64_t* d_status)
+{
+    if (!ctx || !d_status || (n_rec && (!d_class || !d_join_fate))) return GCI_E_INVALID;
+    HIPCHK(hipMemsetAsync(d_status, 0xFF, 8, ctx->stream));
+    if (n_rec) {
+        hipLaunchKernelGGL(k_fate_refine, dim3((n_rec + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, ctx->stream, d_class, d_join_fate, n_rec,
+                           (unsigned long long*)d_status);
+        LAUNCHCHK("k_fate_refine");
+    }
+    return GCI_OK;
 }
 
 // ---- export -------------------------------------------------------------------------------------------------------------------------

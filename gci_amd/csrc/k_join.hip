@@ -77,11 +77,14 @@ __global__ __launch_bounds__(BLOCK) void k_join_insert(JoinFiles F, int file, un
     if (F.n > 1 && (r.flags & GCI_REC_HQ)) atomicOr(hq + slot, 1u);    // (a single file keeps every passing name: GCI.py:270)
 }
 
-// Fold of one name over the files (GCI.py:279-299); returns true when an interval survives.
+// Fold of one name over the files (GCI.py:279-299); returns true when an interval survives.  why (optional, gci_name_join_fate):
+// the name's verdict before the contig map -- GCI_FATE_JOINED, or what took the name out LAST: another contig, too little
+// overlap (a zero qlen ends the fold there and counts as that), or GCI_FATE_UNPAIRED when no test did (never admitted).
 __device__ __forceinline__ bool fold_slot(const JoinFiles& F, uint64_t slot, const unsigned long long* last,
                                           bool high, double ovlp_percent, const int32_t* __restrict__ contig_map,
-                                          unsigned long long* __restrict__ status, gci_ivl& o)
+                                          unsigned long long* __restrict__ status, gci_ivl& o, uint8_t* why = nullptr)
 {
+    uint8_t w = GCI_FATE_UNPAIRED;
     bool comm = true;
     for (int f = 0; f < F.n; f++) comm = comm && last[slot * F.n + f] != 0;
     // file1 = entries of files[0] whose name is in high_qual | comm   (GCI.py:279-280)
@@ -104,15 +107,17 @@ __device__ __forceinline__ bool fold_slot(const JoinFiles& F, uint64_t slot, con
                 const int64_t ovlp = (int64_t)me - (int64_t)ms;
                 if (r.qlen == 0) {                                           // ZeroDivisionError at GCI.py:292
                     atomicMin(status, ((unsigned long long)r.rec_idx << 8) | (unsigned)(-GCI_E_ZERO_DIV));
+                    if (why) *why = GCI_FATE_OVERLAP;
                     return false;
                 }
-                if ((double)ovlp / (double)r.qlen < ovlp_percent) have = false;
+                if ((double)ovlp / (double)r.qlen < ovlp_percent) { have = false; w = GCI_FATE_OVERLAP; }
                 else { s = ms; e = me; }
-            } else have = false;
+            } else { have = false; w = GCI_FATE_CONTIG; }
         } else if (high) {
             have = true; contig = r.contig; s = r.start; e = r.end;
         }
     }
+    if (why) *why = have ? GCI_FATE_JOINED : w;
     if (!have) return false;
     if (contig_map) { contig = contig_map[contig]; if (contig < 0) return false; }
     o.contig = contig; o.start = s; o.end = e; o.pad = 0;
@@ -188,6 +193,70 @@ __global__ __launch_bounds__(BLOCK) void k_join_fold(JoinFiles F, unsigned long 
             }
         }
     }
+}
+
+// ---- gci_name_join_fate: what the join does with every record, and why ----------------------------------------------
+// After k_join_insert over every file the tables hold, per name, the winners and the high-quality bit.  k_join_verdict
+// folds every used slot with fold_slot (the join rule stays written once) into one byte per slot and clears nothing;
+// k_join_fate_rec walks the records again, finds each one's slot with the probe and the full-name comparison of the
+// insert, and stores GCI_FATE_SHADOWED for a record that is not its file's winner, else the slot's verdict; k_join_clear
+// then leaves the three tables as name_join_impl expects to find them.
+__global__ __launch_bounds__(BLOCK) void k_join_verdict(JoinFiles F, const unsigned long long* __restrict__ table, uint64_t n_slots,
+                                                        const unsigned long long* __restrict__ last, const uint32_t* __restrict__ hq,
+                                                        double ovlp_percent, unsigned long long* __restrict__ status,
+                                                        uint8_t* __restrict__ verdict)
+{
+    const uint64_t slot = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (slot >= n_slots || table[slot] == SLOT_EMPTY) return;
+    gci_ivl o;
+    uint8_t why = GCI_FATE_UNPAIRED;
+    fold_slot(F, slot, last, hq[slot] != 0, ovlp_percent, nullptr, status, o, &why);
+    verdict[slot] = why;
+}
+
+__global__ __launch_bounds__(BLOCK) void k_join_fate_rec(JoinFiles F, int file, const unsigned long long* __restrict__ table, uint64_t mask,
+                                                         const unsigned long long* __restrict__ last, const uint8_t* __restrict__ verdict,
+                                                         uint8_t* __restrict__ fate, unsigned long long* __restrict__ counts)
+{
+    __shared__ uint32_t hist[GCI_JOIN_FATE_CLASSES];
+    if (threadIdx.x < GCI_JOIN_FATE_CLASSES) hist[threadIdx.x] = 0;
+    __syncthreads();
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i < F.f[file].n_recs) {
+        const gci_rec r = F.f[file].d_recs[i];
+        uint32_t c = 0;
+        if (r.flags & GCI_REC_PASS) {
+            const unsigned long long ord = (((unsigned long long)(uint32_t)r.contig << 32) | i) + 1ull;    // k_join_insert's order key
+            uint64_t slot = r.name_hash & mask;
+            unsigned long long cur;
+            // every passing record was inserted, so its name's slot comes before an empty one (the table is at most half full);
+            // an empty slot all the same ends the probe: GCI_FATE_ERROR, which no caller takes for a verdict
+            for (;;) {
+                cur = table[slot];
+                if (cur == SLOT_EMPTY) break;
+                if (same_name(F, file, i, r, F.n == 1 ? (unsigned long long)(uint32_t)(cur - 1ull) : cur)) break;
+                slot = (slot + 1) & mask;
+            }
+            if (cur == SLOT_EMPTY) c = GCI_FATE_ERROR;
+            else if (F.n == 1) c = cur == ord ? GCI_FATE_JOINED : GCI_FATE_SHADOWED;     // (the slot word is the winner's order key)
+            else c = last[slot * F.n + file] == ord ? verdict[slot] : GCI_FATE_SHADOWED;
+        }
+        fate[i] = (uint8_t)c;
+        atomicAdd(&hist[c & (GCI_JOIN_FATE_CLASSES - 1)], 1u);
+    }
+    __syncthreads();
+    if (threadIdx.x < GCI_JOIN_FATE_CLASSES && hist[threadIdx.x]) atomicAdd(counts + threadIdx.x, (unsigned long long)hist[threadIdx.x]);
+}
+
+__global__ __launch_bounds__(BLOCK) void k_join_clear(int n_files, unsigned long long* __restrict__ table, uint64_t n_slots,
+                                                      unsigned long long* __restrict__ last, uint32_t* __restrict__ hq)
+{
+    const uint64_t slot = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (slot >= n_slots || table[slot] == SLOT_EMPTY) return;
+    table[slot] = SLOT_EMPTY;
+    if (n_files == 1) return;                       // (one file: the slot word is all the insert wrote)
+    hq[slot] = 0u;
+    for (int f = 0; f < n_files; f++) last[slot * n_files + f] = 0ull;
 }
 
 
@@ -1002,6 +1071,26 @@ static int name_join_partitioned(gci_ctx* ctx, const JoinFiles& F, uint64_t tota
     return GCI_OK;
 }
 
+// The classic table for `total` records of n_files files, clean, and marked dirty until the caller has emptied it again.
+static int join_tables_begin(gci_ctx* ctx, uint64_t total, int n_files, uint64_t* out_slots)
+{
+    uint64_t slots = 1024;
+    while (slots < 2 * total) slots <<= 1;
+    // The three tables are kept clean between calls (k_join_fold and k_join_clear empty every slot they find used), whatever
+    // the slot count and the number of files of the next call: a memset only when a buffer is new or a
+    // join was cut short.
+    const size_t cap_t = ctx->join_table.cap, cap_l = ctx->join_last.cap, cap_h = ctx->join_hq.cap;
+    GCI_TRY(gci_ensure(ctx, ctx->join_table, slots * 8));
+    GCI_TRY(gci_ensure(ctx, ctx->join_last, slots * 8 * n_files));
+    GCI_TRY(gci_ensure(ctx, ctx->join_hq, slots * 4));
+    if (ctx->join_table.cap != cap_t || ctx->join_dirty) HIPCHK(hipMemsetAsync(ctx->join_table.p, 0xFF, ctx->join_table.cap, ctx->stream));
+    if (ctx->join_last.cap != cap_l || ctx->join_dirty) HIPCHK(hipMemsetAsync(ctx->join_last.p, 0, ctx->join_last.cap, ctx->stream));
+    if (ctx->join_hq.cap != cap_h || ctx->join_dirty) HIPCHK(hipMemsetAsync(ctx->join_hq.p, 0, ctx->join_hq.cap, ctx->stream));
+    ctx->join_dirty = true;
+    *out_slots = slots;
+    return GCI_OK;
+}
+
 static int name_join_impl(gci_ctx* ctx, const gci_join_file* h_files, int n_files, double ovlp_percent,
                           const int32_t* d_contig_map, gci_ivl* d_out, uint32_t cap, uint32_t* d_n_out,
                           uint64_t* d_status, const CountArgs& cnt)
@@ -1022,19 +1111,8 @@ static int name_join_impl(gci_ctx* ctx, const gci_join_file* h_files, int n_file
             if (st != GCI_OK || done) return st;
         }
     }
-    uint64_t slots = 1024;
-    while (slots < 2 * total) slots <<= 1;
-    // The three tables are kept clean between calls (k_join_fold empties every slot it reads), whatever the slot count
-    // and the number of files of the next call: a memset only when a buffer is new or a
-    // join was cut short.
-    const size_t cap_t = ctx->join_table.cap, cap_l = ctx->join_last.cap, cap_h = ctx->join_hq.cap;
-    GCI_TRY(gci_ensure(ctx, ctx->join_table, slots * 8));
-    GCI_TRY(gci_ensure(ctx, ctx->join_last, slots * 8 * n_files));
-    GCI_TRY(gci_ensure(ctx, ctx->join_hq, slots * 4));
-    if (ctx->join_table.cap != cap_t || ctx->join_dirty) HIPCHK(hipMemsetAsync(ctx->join_table.p, 0xFF, ctx->join_table.cap, ctx->stream));
-    if (ctx->join_last.cap != cap_l || ctx->join_dirty) HIPCHK(hipMemsetAsync(ctx->join_last.p, 0, ctx->join_last.cap, ctx->stream));
-    if (ctx->join_hq.cap != cap_h || ctx->join_dirty) HIPCHK(hipMemsetAsync(ctx->join_hq.p, 0, ctx->join_hq.cap, ctx->stream));
-    ctx->join_dirty = true;
+    uint64_t slots = 0;
+    GCI_TRY(join_tables_begin(ctx, total, n_files, &slots));
     bool reset_done = false;
     for (int f = 0; f < n_files; f++) {
         if (!F.f[f].n_recs) continue;
@@ -1111,6 +1189,64 @@ extern "C" int gci_name_join_count(gci_ctx* ctx, const gci_join_file* h_files, i
     const int st = name_join_impl(ctx, h_files, n_files, ovlp_percent, d_contig_map, d_out, cap, d_n_out, d_status, cnt);
     if (st == GCI_OK) { ctx->cd_state = 1; ctx->counted_flank = flank; }
     return st;
+}
+
+// What the join does with every record (include/gci_hip.h).  Always the classic table: the verdict needs every record's way
+// back to its name's slot, which the partitioned join does not keep.
+extern "C" int gci_name_join_fate(gci_ctx* ctx, const gci_join_file* h_files, int n_files, double ovlp_percent,
+                                  uint8_t* const* h_d_fate, uint64_t* h_counts, uint64_t* d_status)
+{
+    if (!ctx || !h_files || n_files < 1 || n_files > GCI_MAX_JOIN_FILES || !h_d_fate || !h_counts || !d_status) return GCI_E_INVALID;
+    JoinFiles F;
+    memset(&F, 0, sizeof F);
+    F.n = n_files;
+    uint64_t total = 0;
+    for (int f = 0; f < n_files; f++) {
+        const gci_join_file& jf = h_files[f];
+        if (jf.n_recs && (!jf.d_recs || !jf.d_name_base || !jf.d_name_off || !h_d_fate[f])) return GCI_E_INVALID;
+        F.f[f] = jf;
+        total += jf.n_recs;
+    }
+    const size_t n_counts = (size_t)n_files * GCI_JOIN_FATE_CLASSES;
+    for (size_t k = 0; k < n_counts; k++) h_counts[k] = 0;
+    uint64_t slots = 0;
+    GCI_TRY(join_tables_begin(ctx, total, n_files, &slots));
+    GCI_TRY(gci_ensure(ctx, ctx->join_fate, 8 * (size_t)GCI_MAX_JOIN_FILES * GCI_JOIN_FATE_CLASSES + slots));
+    unsigned long long* counts = (unsigned long long*)ctx->join_fate.p;
+    uint8_t* verdict = (uint8_t*)ctx->join_fate.p + 8 * (size_t)GCI_MAX_JOIN_FILES * GCI_JOIN_FATE_CLASSES;
+    unsigned long long* table = (unsigned long long*)ctx->join_table.p;
+    unsigned long long* last = (unsigned long long*)ctx->join_last.p;
+    uint32_t* hq = (uint32_t*)ctx->join_hq.p;
+    HIPCHK(hipMemsetAsync(counts, 0, 8 * n_counts, ctx->stream));
+    HIPCHK(hipMemsetAsync(d_status, 0xFF, 8, ctx->stream));
+    for (int f = 0; f < n_files; f++) {
+        if (!F.f[f].n_recs) continue;
+        ProfScope _ps(ctx, GCI_PROF_JOIN_INSERT);
+        hipLaunchKernelGGL(k_join_insert, dim3((F.f[f].n_recs + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, ctx->stream, F, f, table, slots - 1, last, hq,
+                           (uint32_t*)nullptr, (unsigned long long*)nullptr);
+        LAUNCHCHK("k_join_insert");
+    }
+    const dim3 slot_grid((uint32_t)((slots + BLOCK - 1) / BLOCK));
+    if (n_files > 1 && total) {
+        ProfScope _ps(ctx, GCI_PROF_JOIN_FOLD);
+        hipLaunchKernelGGL(k_join_verdict, slot_grid, dim3(BLOCK), 0, ctx->stream, F, table, slots, last, hq, ovlp_percent,
+                           (unsigned long long*)d_status, verdict);
+        LAUNCHCHK("k_join_verdict");
+    }
+    for (int f = 0; f < n_files; f++) {
+        if (!F.f[f].n_recs) continue;
+        hipLaunchKernelGGL(k_join_fate_rec, dim3((F.f[f].n_recs + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, ctx->stream, F, f, table, slots - 1, last,
+                           verdict, h_d_fate[f], counts + (size_t)f * GCI_JOIN_FATE_CLASSES);
+        LAUNCHCHK("k_join_fate_rec");
+    }
+    if (total) {
+        hipLaunchKernelGGL(k_join_clear, slot_grid, dim3(BLOCK), 0, ctx->stream, n_files, table, slots, last, hq);
+        LAUNCHCHK("k_join_clear");
+    }
+    ctx->join_dirty = false;
+    HIPCHK(hipMemcpyAsync(h_counts, counts, 8 * n_counts, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return GCI_OK;
 }
 
 // ---- names blob for the multi-GPU exchange ------------------------------------------------------

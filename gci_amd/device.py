@@ -450,6 +450,31 @@ class Engine:
                 return out, count
             out = self.T.empty((n, 4), self.T.int32, self.device)
 
+    def name_join_fate(self, files: Sequence[JoinInput], ovlp_percent: float, check: bool = True):
+        """-> (per file the join's byte of every record uint8 [n] on the device, per file the records per byte as a list of
+        JOIN_FATE_CLASSES ints): what the cross-file join does with every record and why (include/gci_hip.h: gci_name_join_fate).
+        check: a zero qlen the join divides by raises GciError with .file (index in `files`) and .rec (the record's rec_idx)."""
+        n = len(files)
+        fate = [self.T.empty(max(int(f.recs.shape[0]), 1), self.T.uint8, self.device) for f in files]
+        ptrs = (ctypes.c_void_p * n)(*[t.data_ptr() for t in fate])
+        counts = (ctypes.c_uint64 * (n * _lib.JOIN_FATE_CLASSES))()
+        self._chk(self.lib.gci_name_join_fate(self.ctx, self._join_files(files), n, float(ovlp_percent), ptrs, counts, self._p(self._status)),
+                  "gci_name_join_fate")
+        if check:
+            self.check_status("gci_name_join_fate")
+        k = _lib.JOIN_FATE_CLASSES
+        return [t[:int(f.recs.shape[0])] for t, f in zip(fate, files)], [[int(c) for c in counts[f * k:(f + 1) * k]] for f in range(n)]
+
+    def fate_refine(self, classes: Buffer, join_fate: Buffer, check: bool = True, rec_idx_base: int = 0) -> Buffer:
+        """classes[i] == kept becomes join_fate[i] (gci_fate_refine); a record the two passes disagree about raises GciError."""
+        n = int(classes.shape[0])
+        if int(join_fate.shape[0]) != n:
+            raise GciError(_lib.GCI_E_INVALID, "gci_fate_refine: %d class bytes, %d join bytes" % (n, int(join_fate.shape[0])))
+        self._chk(self.lib.gci_fate_refine(self.ctx, self._p(classes), self._p(join_fate), n, self._p(self._status)), "gci_fate_refine")
+        if check:
+            self._raise_status(self._status.item(), "gci_fate_refine", rec_idx_base)
+        return classes
+
     # ---- R7 / N2: gzip members of the depth text, written on the device ----------------------------------------
     MEMBER_BASES = 64 * 4096
 

@@ -1359,22 +1359,48 @@ def device_memory_free(engine: Engine) -> int:
 
 class FilterDepth:
     """What bam_filter_depth returns: tracks[class name] = the DepthTracks of every wanted class, counts[k][class id] = the records of
-    file k per class (FATE_NAMES), flushes = how often intervals were built into a track before their file was through."""
+    file k per class (FATE_NAMES), flushes = how often intervals were built into a track before their file was through.  With `join`:
+    counts holds the covered file alone, its row running on through the join's classes (ALL_FATE_NAMES), join_files names every file
+    of the join in its order (PAF files, then BAM files), join_counts[k] is gci_name_join_fate's row of file k and cover_file the
+    covered file's index among them."""
 
     def __init__(self, tracks: Dict[str, DepthTracks], counts: List[List[int]], flushes: int):
         self.tracks, self.counts, self.flushes = tracks, counts, flushes
+        self.join_files: List[str] = []
+        self.join_counts: List[List[int]] = []
+        self.cover_file = -1
+
+
+JOIN_FATE_NAMES = _lib.JOIN_FATE_NAMES
+ALL_FATE_NAMES = _lib.ALL_FATE_NAMES
+_JOIN_FATE_IDS = tuple(range(_lib.JOIN_FATE_FIRST, _lib.JOIN_FATE_FIRST + len(JOIN_FATE_NAMES)))
+_JOIN_FATE_MASK = sum(1 << c for c in _JOIN_FATE_IDS)
+_KEPT = FATE_NAMES.index("kept")
+
+
+class JoinFateOpts:
+    """bam_filter_depth's `join`: the files are one read set aligned several times (GCI.py's --hifi list), joined by read name as
+    filter() joins them -- paf_files in front of the BAM files, mq_cutoff and ovlp_percent as GCI.py's -- and `cover` is the index,
+    among the BAM files, of the one whose records give the depth."""
+
+    def __init__(self, paf_files: Sequence[str] = (), mq_cutoff: int = 50, ovlp_percent: float = 0.9, cover: int = 0):
+        self.paf_files, self.mq_cutoff, self.ovlp_percent, self.cover = list(paf_files), int(mq_cutoff), float(ovlp_percent), int(cover)
 
 
 class _FateVisitor(StreamVisitor):
     """Next to _CoverVisitor: per piece ONE gci_bam_fate call (every CIGAR read once for the verdicts), then for every wanted class
     gci_bam_cover_size_sel / _write with that class's mask into that class's collector -- a record that is not selected makes no
     chunk, so the walks of all classes together read every CIGAR once more.  The interval budget is shared: beyond it every collector
-    that holds intervals builds them into its track."""
+    that holds intervals builds them into its track.  join_fate: the file's bytes of gci_name_join_fate, made on the caller's engine;
+    every `kept` record of a piece then takes its join class (gci_fate_refine over the piece's slice) before the classes are walked,
+    and `kept`, where it is asked for, is the five of them together."""
 
-    def __init__(self, main: Engine, opts: FateOpts, classes: Sequence[int], budget: int):
+    def __init__(self, main: Engine, opts: FateOpts, classes: Sequence[int], budget: int, join_fate: Optional[Buffer] = None):
         self.main, self.opts, self.classes, self.budget = main, opts, list(classes), max(int(budget), 1)
         self.collectors = {c: _IntervalCollector() for c in self.classes}
+        self.join_fate = join_fate
         self.counts = [0] * _lib.FATE_CLASSES
+        self.n_seen = 0
 
     flushes = property(lambda self: sum(c.flushes for c in self.collectors.values()))
 
@@ -1382,8 +1408,18 @@ class _FateVisitor(StreamVisitor):
         for c in self.collectors.values():
             c.reset()
         self.counts = [0] * _lib.FATE_CLASSES
+        self.n_seen = 0
 
     abort_file = begin_file
+
+    def _refine(self, engine, cls, n: int, rec_idx_base: int):
+        """The piece's slice of the join's bytes into its class bytes."""
+        total = int(self.join_fate.shape[0])
+        if rec_idx_base + n > total:
+            raise GciError(_lib.GCI_E_INVALID, "the second pass meets record %d of a file the join saw %d records of" % (rec_idx_base + n - 1, total))
+        if engine is not self.main:                        # (made in the caller's stream order -- the export synchronised --, used in this one's)
+            self.join_fate.record_stream(engine.stream)
+        engine.fate_refine(cls, self.join_fate[rec_idx_base:rec_idx_base + n])
 
     def visit(self, engine, d_stream, d_off, has_seq, ref_sel, rec_idx_base) -> None:
         if engine.lengths != self.main.lengths:            # (the walk engine: a context of its own)
@@ -1393,15 +1429,21 @@ class _FateVisitor(StreamVisitor):
         try:
             with phases.gpu("record fate"):
                 cls, counts = engine.bam_fate(d_stream, d_off, has_seq, ref_sel, o.map_qual, o.clip_percent, o.iden_percent)
+                if self.join_fate is not None:
+                    what = "gci_fate_refine"
+                    self._refine(engine, cls, int(d_off.shape[0]), rec_idx_base)
             what = "gci_bam_cover_size_sel"
             for c in self.classes:
-                if counts[c]:                              # (`none` is never asked for: 0x4 stays among the excluded flags)
+                joined = self.join_fate is not None and (c == _KEPT or c in _JOIN_FATE_IDS)
+                if counts[_KEPT if joined else c]:         # (`none` is never asked for: 0x4 stays among the excluded flags)
+                    mask = _JOIN_FATE_MASK if (joined and c == _KEPT) else 1 << c
                     with phases.gpu("record cover"):
-                        self.collectors[c].add(engine.bam_cover(d_stream, d_off, has_seq, ref_sel, 0x4, 0, o.count_del, classes=cls, mask=1 << c))
+                        self.collectors[c].add(engine.bam_cover(d_stream, d_off, has_seq, ref_sel, 0x4, 0, o.count_del, classes=cls, mask=mask))
         except GciError as e:
             if e.rec < 0:
                 raise
             raise _file_record_error(engine, e, what, rec_idx_base) from None
+        self.n_seen += int(d_off.shape[0])
         self.counts = [a + b for a, b in zip(self.counts, counts)]
         if sum(c.n_ivl for c in self.collectors.values()) > self.budget:
             for c in self.collectors.values():
@@ -1415,23 +1457,72 @@ class _FateVisitor(StreamVisitor):
         return {c: col.finish(self.main) for c, col in self.collectors.items()}
 
 
+def _zero_qlen_file(inputs: Sequence[JoinInput], rec: int) -> int:
+    """Which file of the join holds the passing record `rec` (its rec_idx) with a zero query length: the first one behind file 0."""
+    for f in range(1, len(inputs)):
+        r = np.ascontiguousarray(inputs[f].recs.cpu().numpy()).view(REC_DTYPE).reshape(-1)
+        if (((r["flags"] & REC_PASS) != 0) & (r["rec_idx"] == rec) & (r["qlen"] == 0)).any():
+            return f
+    return -1
+
+
+def _join_fates(engine: Engine, bam_files: Sequence[str], targets: List[str], opts: FateOpts, join: JoinFateOpts, threads: int):
+    """The first pass of bam_filter_depth(join=...): every PAF through the PAF filter, every BAM through the record filter, one
+    gci_name_join_fate over them in the reference's order -> (the covered file's bytes, the records the join saw of it, every file's
+    row of counts).  The records and names of all files are released on the way out."""
+    filt = (opts.map_qual, join.mq_cutoff, opts.clip_percent, opts.iden_percent)
+    inputs: List[JoinInput] = []
+    if join.paf_files:
+        with phases.wall("paf_filter"):
+            inputs += engine.paf_filter(join.paf_files, targets, opts.map_qual, join.mq_cutoff, opts.iden_percent)
+        if os.environ.get("GCI_PAF_POOL_KEEP_GB") is None:
+            engine.lib.gci_paf_pool_release(engine.ctx)
+    for path in bam_files:
+        try:
+            with phases.wall("bam_join_input[%s]" % os.path.basename(path)):
+                inputs.append(bam_join_input(engine, path, targets, filt, threads))
+        except GciError as e:
+            e.path = path
+            raise
+    names = list(join.paf_files) + list(bam_files)
+    try:
+        with phases.wall("name_join_fate"), phases.gpu("name join fate"):
+            fates, counts = engine.name_join_fate(inputs, join.ovlp_percent)
+    except GciError as e:
+        if e.status == _lib.GCI_E_ZERO_DIV and e.rec >= 0:
+            f = _zero_qlen_file(inputs, e.rec)
+            e.path, e.in_join = (names[f] if f >= 0 else "?"), True
+        raise
+    k = len(join.paf_files) + join.cover
+    return fates[k], int(inputs[k].recs.shape[0]), counts
+
+
 def bam_filter_depth(engine: Engine, bam_files: Sequence[str], chrs: Sequence[str], opts: Optional[FateOpts], threads: int,
-                     classes: Sequence[str], ivl_budget: Optional[int] = None) -> FilterDepth:
+                     classes: Sequence[str], ivl_budget: Optional[int] = None, join: Optional[JoinFateOpts] = None) -> FilterDepth:
     """Per wanted class of the record filter (FATE_WANTED: the first test of read_sam a record fails, or `kept`) the per-base depth of
     that class's records over `bam_files`, counted as bam_raw_depth counts it (CIGAR-aware, no flank; opts.count_del for deletions), so
     that the six tracks add up, base for base, to bam_raw_depth with excl = 0x4.  Several files add per class; the contigs are the
     first file's (restricted by `chrs`), a file with another @SQ table raises SqMismatch.  A record the reference would have raised on
     (no NM tag, a zero denominator) or a malformed one raises GciError with .path and the record's index in the file.
-    Raises TracksDoNotFit before anything is read when the tracks of the run are more than the device has free."""
+    Raises TracksDoNotFit before anything is read when the tracks of the run are more than the device has free.
+
+    join (JoinFateOpts): the files are ONE read set aligned several times and are joined, not added.  A first pass filters every file
+    and asks gci_name_join_fate what the cross-file join does with every record; the second pass walks the BAM file join.cover alone,
+    as above, with every `kept` record moved to its join class -- shadowed, unpaired, contig, overlap, joined (JOIN_FATE_NAMES), which
+    `classes` may then name; `kept` stays their sum.  The covered file is read twice.  A zero query length the join divides by raises
+    GciError with .path, .rec and .in_join."""
     opts = opts or FateOpts()
+    wanted = FATE_WANTED + (JOIN_FATE_NAMES if join is not None else ())
     ids = []
     for name in classes:
-        if name not in FATE_WANTED:
-            raise ValueError('"%s" is not one of %s' % (name, ", ".join(FATE_WANTED)))
-        if FATE_NAMES.index(name) not in ids:
-            ids.append(FATE_NAMES.index(name))
+        if name not in wanted:
+            raise ValueError('"%s" is not one of %s' % (name, ", ".join(wanted)))
+        if ALL_FATE_NAMES.index(name) not in ids:
+            ids.append(ALL_FATE_NAMES.index(name))
     if not ids:
         raise ValueError("no class selected")
+    if join is not None and not 0 <= join.cover < len(bam_files):
+        raise ValueError("cover = %d: there are %d BAM files" % (join.cover, len(bam_files)))
     first = same_sq_table(bam_files)
     targets_length = _targets_of(first, list(chrs))
     targets = list(targets_length.keys())
@@ -1440,14 +1531,15 @@ def bam_filter_depth(engine: Engine, bam_files: Sequence[str], chrs: Sequence[st
     engine.set_layout([targets_length[t] for t in targets])
     # a track per class, one more while intervals are built in parts -- and with several files a second one per class, the file's next
     # to the sum of the files before it
-    n_tracks = len(ids) * (2 if len(bam_files) > 1 else 1) + 1
+    n_tracks = len(ids) * (2 if (len(bam_files) > 1 and join is None) else 1) + 1      # (with join one file alone is covered)
     track_bytes, free = 4 * int(engine.total), device_memory_free(engine)
     if n_tracks * track_bytes > free:
         raise TracksDoNotFit(n_tracks, track_bytes, free)
-    visitor = _FateVisitor(engine, opts, ids, COVER_IVL_BUDGET if ivl_budget is None else ivl_budget)
+    join_fate, join_n_rec, join_counts = _join_fates(engine, bam_files, targets, opts, join, threads) if join is not None else (None, 0, [])
+    visitor = _FateVisitor(engine, opts, ids, COVER_IVL_BUDGET if ivl_budget is None else ivl_budget, join_fate)
     totals: Dict[int, Buffer] = {}
     counts = []
-    for path in bam_files:
+    for path in (bam_files if join is None else [bam_files[join.cover]]):
         visitor.begin_file()
         try:
             with phases.wall("bam_fate[%s]" % os.path.basename(path)):
@@ -1463,7 +1555,17 @@ def bam_filter_depth(engine: Engine, bam_files: Sequence[str], chrs: Sequence[st
                 engine.track_add(totals[c], track)
             else:
                 totals[c] = track
-    return FilterDepth({FATE_NAMES[c]: DepthTracks(engine, targets_length, totals[c]) for c in ids}, counts, visitor.flushes)
+    result = FilterDepth({ALL_FATE_NAMES[c]: DepthTracks(engine, targets_length, totals[c]) for c in ids}, counts, visitor.flushes)
+    if join is not None:
+        # both passes saw the same records of the covered file, and agree on which of them pass (gci_fate_refine checked each one)
+        k = len(join.paf_files) + join.cover
+        row = join_counts[k][_lib.JOIN_FATE_FIRST:_lib.JOIN_FATE_FIRST + len(JOIN_FATE_NAMES)]
+        if visitor.n_seen != join_n_rec or sum(row) != counts[0][_KEPT]:
+            raise GciError(_lib.GCI_E_INVALID, 'the two passes over "%s" disagree: %d records and %d kept in the join, %d and %d in the walk'
+                           % (bam_files[join.cover], join_n_rec, sum(row), visitor.n_seen, counts[0][_KEPT]))
+        counts[0] = counts[0] + row
+        result.join_files, result.join_counts, result.cover_file = list(join.paf_files) + list(bam_files), join_counts, k
+    return result
 
 
 # ==============================================================================================

@@ -21,6 +21,7 @@
  *   gci_depth_hist      depth_dist.py: the depth histogram, sum, min, max and count of windows (no counterpart in the reference)
  *   gci_bam_cover_*, gci_track_add     bam_depth.py: the unfiltered per-base depth of BAM files, `samtools depth -a` (no counterpart in the reference)
  *   gci_bam_fate, gci_bam_cover_size_sel   filter_depth.py: which test of read_sam drops a record (GCI.py:152-168), and the depth of every such class
+ *   gci_name_join_fate, gci_fate_refine    filter_depth.py --join: what the cross-file join (GCI.py:272-301) does with every record, and why
  *   gci_paf_filter_device   filter(), PAF path        GCI.py:211-254  (+ helpers 49-61, 64-96)
  *
  * Conventions
@@ -340,6 +341,44 @@ int gci_join_mode(gci_ctx* ctx, int mode);
 int gci_name_join_count(gci_ctx* ctx, const gci_join_file* h_files, int n_files, double ovlp_percent,
                         const int32_t* d_contig_map, gci_ivl* d_out, uint32_t cap, uint32_t* d_n_out,
                         uint64_t* d_status, int flank);
+
+/* ---- filter_depth.py --join: what the cross-file join does with every record, and why (k_join.hip, k_fate.hip) ----
+ * gci_name_join_fate: the inputs of gci_name_join (h_files in the reference's order) -> one byte per record, h_d_fate[f][i] for
+ * the record at POSITION i of file f's d_recs (h_d_fate: n_files device pointers on the host, h_d_fate[f] of n_recs bytes).
+ * For a read name q: present[f] = q has a GCI_REC_PASS record in file f; the file's WINNER for q is the PASS record that is
+ * last in (contig index, position) -- what the reference's dict keeps (GCI.py:166, 269); hq = any PASS record of q in any file
+ * carries GCI_REC_HQ; comm = q is present in every file.  One file: the verdict of every name is `joined`.  Several files
+ * (GCI.py:277-299): have = present[0] and (hq or comm), why = unpaired; then for the files 1 .. n - 1 in order that hold q:
+ *   have:             the winner lies on another contig than the interval so far  -> have = false, why = contig
+ *                     else ovlp / qlen < ovlp_percent (ovlp = length of the intersection, qlen = THIS file's winner's;
+ *                       IEEE f64 quotient)                                          -> have = false, why = overlap
+ *                     else the interval narrows to the intersection
+ *   not have, and hq: have = true, the interval is this winner's (a name a test took out comes back)
+ * and the verdict is `joined` if have holds at the end, else why.  qlen == 0 where the quotient is asked for: GCI_E_ZERO_DIV
+ * with the winner's rec_idx in *d_status (the smallest such word, as gci_name_join reports it), the name's fold ends there and
+ * its verdict is `overlap`.  `unpaired` thus names reads below mq_cutoff everywhere that some file has no passing record of.
+ *   GCI_FATE_SHADOWED   a PASS record that is not its file's winner for its name (the dict overwrite)
+ *   GCI_FATE_UNPAIRED / _CONTIG / _OVERLAP / _JOINED   a winner: the verdict of its name
+ *   0                   a record without GCI_REC_PASS
+ * The names whose verdict is `joined` are exactly the intervals gci_name_join emits (without a contig map); `joined` is the set
+ * of reads GCI.py counts, not its depth.  h_counts[f * GCI_JOIN_FATE_CLASSES + c]: the records of file f with byte c (host).
+ * ALWAYS the open-addressing table in HBM, whatever gci_join_mode says: the partitioned join keeps no way back from a name to
+ * its records.  That table takes about 5 G records/s at genome scale (k_join.hip); this export has been measured only on 0.66 M
+ * records in two files, at 1.6 times gci_name_join on the same table.  The
+ * join tables are left as gci_name_join expects them.  Needs no layout.  Synchronises.
+ * gci_fate_refine: d_class[i] == GCI_FATE_KEPT becomes d_join_fate[i] (gci_bam_fate's classes of a piece of a file, and the
+ * slice of that file's join bytes that begins at the piece's first record).  A `kept` record whose join byte is not one of the
+ * five above, or a join byte other than 0 on a record that is not `kept` -- the two passes disagree about which records pass
+ * -- is GCI_E_INVALID with the record's index in *d_status, and that class byte stays.  Does not synchronise. */
+#define GCI_FATE_SHADOWED 8
+#define GCI_FATE_UNPAIRED 9
+#define GCI_FATE_CONTIG 10
+#define GCI_FATE_OVERLAP 11
+#define GCI_FATE_JOINED 12
+#define GCI_JOIN_FATE_CLASSES 16       /* entries of a row of gci_name_join_fate's counts */
+int gci_name_join_fate(gci_ctx* ctx, const gci_join_file* h_files, int n_files, double ovlp_percent, uint8_t* const* h_d_fate,
+                       uint64_t* h_counts, uint64_t* d_status);
+int gci_fate_refine(gci_ctx* ctx, uint8_t* d_class, const uint8_t* d_join_fate, uint32_t n_rec, uint64_t* d_status);
 
 /* Cross-rank name check for contig-sharded runs (exact).  gci_hash_bucket sorts the 64-bit name hashes of the
  * passing records into n_parts buckets by (hash >> 33) % n_parts; a bucket is part_cap + 1 uint64 words:

@@ -14,7 +14,13 @@ stream:
   * measure_cover.py's yardsticks in the same process: gci_bam_cover_size + _write (excl = 0x704) and record pages +
     gci_bam_filter_pages.
 
--> OUT/fate_runs.json."""
+-> OUT/fate_runs.json.
+
+    python tools/measure_fate.py join OUT [RUNS] [SCALE]
+
+filter_depth.py --join's export: the HiFi read set and synth.perturb of it as two files of one read set (heads streams, record pages,
+gci_bam_filter_pages), then, as above, gci_name_join_fate against gci_name_join on the classic table over the same inputs, and
+gci_fate_refine over the first file's classes.  -> OUT/joinfate_runs.json."""
 from __future__ import annotations
 
 import ctypes
@@ -119,7 +125,58 @@ def run(out: str, runs: int = 5, scale: float = 1.0) -> None:
     print(json.dumps(res))
 
 
+def join(out: str, runs: int = 5, scale: float = 1.0) -> None:
+    from gci_amd import _lib, pipeline, synth
+    from gci_amd.device import JoinInput
+    os.makedirs(out, exist_ok=True)
+    engine = pipeline.default_engine()
+    contigs, rs = _read_set("hifi", scale)
+    d_sel = engine.to_device(np.arange(len(contigs), dtype=np.int32))
+    files, first = [], None
+    for k, one in enumerate((rs, synth.perturb(rs, 12))):
+        stream, offs = synth.to_bam_stream(one, heads=True)
+        d_stream, d_off = engine.to_device(stream), engine.to_device(offs)
+        pages = engine.bam_pages(d_stream, d_off, False)
+        recs, noff = engine.bam_filter_pages(pages, d_sel, 30, 50, FILT[1], FILT[2])
+        files.append(JoinInput(recs, pages.buf, noff, 0))
+        if k == 0:
+            first = (d_stream, d_off)
+    cls, _ = engine.bam_fate(first[0], first[1], False, d_sel, *FILT)
+    engine.set_join_mode("classic")
+    kept = {}
+
+    def fate():
+        kept["fate"], kept["counts"] = engine.name_join_fate(files, 0.9)
+
+    def plain():
+        kept["n"] = int(engine.name_join(files, 0.9)[1].item())
+
+    fate()
+    work = engine.T.empty(int(cls.shape[0]), engine.T.uint8, engine.device)
+
+    def refine():
+        work.copy_(cls)
+        engine.fate_refine(work, kept["fate"][0])
+
+    calls = {"gci_name_join_fate": fate, "gci_name_join(classic)": plain, "copy+gci_fate_refine": refine}
+    for c in calls.values():
+        c()
+    engine.T.synchronize()
+    ms = {k: [] for k in calls}
+    for _ in range(runs):
+        for k, c in calls.items():
+            ms[k].append(round(_timed(engine, c), 4))
+    names = _lib.ALL_FATE_NAMES
+    res = {"scale": scale, "repeats": runs, "records": [int(f.recs.shape[0]) for f in files], "intervals_of_gci_name_join": kept["n"],
+           "records_per_join_class": [{names[c]: row[c] for c in range(8, 13)} for row in kept["counts"]], "ms": ms,
+           "ms_min_median": {k: [min(v), round(statistics.median(v), 4)] for k, v in ms.items()}}
+    res["fate_over_join"] = round(res["ms_min_median"]["gci_name_join_fate"][1] / res["ms_min_median"]["gci_name_join(classic)"][1], 3)
+    with open(os.path.join(out, "joinfate_runs.json"), "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
 if __name__ == "__main__":
-    if len(sys.argv) < 3 or sys.argv[1] != "run":
+    if len(sys.argv) < 3 or sys.argv[1] not in ("run", "join"):
         raise SystemExit(__doc__)
-    run(sys.argv[2], int(sys.argv[3]) if len(sys.argv) > 3 else 5, float(sys.argv[4]) if len(sys.argv) > 4 else 1.0)
+    (run if sys.argv[1] == "run" else join)(sys.argv[2], int(sys.argv[3]) if len(sys.argv) > 3 else 5, float(sys.argv[4]) if len(sys.argv) > 4 else 1.0)
