@@ -30,6 +30,7 @@ JOIN_FATE_NAMES = ("shadowed", "unpaired", "contig", "overlap", "joined")    # G
 JOIN_FATE_FIRST = 8
 JOIN_FATE_CLASSES = 16        # GCI_JOIN_FATE_CLASSES: entries of a row of gci_name_join_fate's counts
 ALL_FATE_NAMES = FATE_NAMES + JOIN_FATE_NAMES                                # a class id is its index here
+READS_CLASS_MASK = 0x1F7E     # the classes gci_bam_reads_size lists: every one but none and error
 PROF_COUNT = 19
 PROF_DEPTH_SCAN = 5          # k_tile_build: the pass that writes the depth track (+ text)
 PROF_TILE_PASS1 = 13
@@ -124,6 +125,9 @@ EXPORTS = [
                               c_void_p, c_int]),
     ("gci_name_join_fate", c_int, [c_void_p, POINTER(JoinFile), c_int, c_double, POINTER(c_void_p), c_void_p, c_void_p]),
     ("gci_fate_refine", c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),
+    ("gci_bam_reads_size", c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_int, c_void_p, c_int32, c_void_p, c_uint32, c_void_p,
+                                   c_void_p, c_void_p, c_uint32, POINTER(c_uint64), POINTER(c_uint64), c_void_p]),
+    ("gci_bam_reads_write", c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64]),
     ("gci_depth_deflate_from_build", c_int, [c_void_p, c_void_p]),
     ("gci_depth_deflate_size", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("gci_depth_deflate_write", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -42,7 +42,7 @@ gci_depth_build gci_gap_mask gci_max2 gci_issue_scan gci_issue_scan_windows gci_
 gci_depth_sum gci_range_sums gci_depth_deflate_from_build gci_depth_deflate_size gci_depth_deflate_write gci_depth_text_index
 gci_depth_text_parse gci_sdepth_index gci_sdepth_parse gci_depth_gz_scan gci_depth_gz_runs gci_depth_gz_expand gci_depth_runs_count
 gci_depth_runs_write gci_bedgraph_size gci_bedgraph_write gci_depth_hist gci_bam_cover_size gci_bam_cover_write gci_track_add
-gci_bam_fate gci_bam_cover_size_sel gci_name_join_fate gci_fate_refine""".split()
+gci_bam_fate gci_bam_cover_size_sel gci_name_join_fate gci_fate_refine gci_bam_reads_size gci_bam_reads_write""".split()
 _PROTO = {name: (name, res, args) for name, res, args in _lib.EXPORTS}
 EXPORTS = [_PROTO[name] for name in _SEAMS] + [("gci_cpu_option", c_int, [c_void_p, c_char_p, c_int])]
 
@@ -193,6 +193,36 @@ class CpuEngine:
         if check:
             self._status(self.last_status, "gci_bam_fate")
         return cls[:offs.shape[0]], counts
+
+    def bam_reads(self, stream: np.ndarray, offs: np.ndarray, ref_sel: np.ndarray, classes: np.ndarray, mask: int, names: Sequence[bytes],
+                  win: Optional[np.ndarray] = None, win0: Optional[np.ndarray] = None, file_no: int = 1, has_seq: bool = True,
+                  check: bool = True, cap: Optional[int] = None, guard: int = 0) -> Tuple[bytes, int]:
+        """device.Engine.bam_reads's twin -> (the rows of the records whose class is a bit of the mask and that overlap a window, the
+        number of rows).  names: the selected contigs' names; win int64 [n, 2] and win0 uint32 [n_sel + 1] as pipeline.merge_windows
+        makes them (None: no window test).  cap: the room offered to the write call; guard: bytes of 0xA5 behind it that must stay."""
+        stream = np.ascontiguousarray(stream, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        ref_sel = np.ascontiguousarray(ref_sel, dtype=np.int32)
+        classes = np.ascontiguousarray(classes, dtype=np.uint8)
+        if win0 is not None:
+            win, win0 = np.ascontiguousarray(win, dtype=np.int64).reshape(-1, 2), np.ascontiguousarray(win0, dtype=np.uint32)
+        blob = np.frombuffer(b"".join(names) + b"\0", dtype=np.uint8)
+        name_len = np.asarray([len(x) for x in names], dtype=np.uint32)
+        name_off = np.concatenate(([0], np.cumsum(name_len[:-1], dtype=np.uint64))).astype(np.uint64)
+        rows, size = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self.last_status = np.zeros(1, dtype=np.uint64)
+        self._chk(self.lib.gci_bam_reads_size(self.ctx, _p(stream), stream.shape[0], _p(offs), offs.shape[0], int(has_seq), _p(ref_sel), ref_sel.shape[0],
+                                              _p(classes), int(mask), _p(win) if win0 is not None else None, _p(win0), _p(name_len), int(file_no),
+                                              ctypes.byref(rows), ctypes.byref(size), _p(self.last_status)), "gci_bam_reads_size")
+        if check:
+            self._status(self.last_status, "gci_bam_reads_size")
+        room = int(size.value) if cap is None else int(cap)
+        out = np.full(room + guard + 1, 0xA5, dtype=np.uint8)
+        self._chk(self.lib.gci_bam_reads_write(self.ctx, _p(stream), stream.shape[0], _p(offs), offs.shape[0], _p(blob), _p(name_off), _p(name_len),
+                                               _p(out), room), "gci_bam_reads_write")
+        if (out[int(size.value):] != 0xA5).any():
+            raise CpuError(-1, "gci_bam_reads_write wrote behind its rows")
+        return out[:int(size.value)].tobytes(), int(rows.value)
 
     def track_add(self, acc: np.ndarray, add: np.ndarray) -> np.ndarray:
         self._chk(self.lib.gci_track_add(self.ctx, _p(acc), _p(add)), "gci_track_add")

@@ -48,6 +48,16 @@ struct gci_ctx {
     bool cover_valid = false, cover_count_del = false;
     const void* cover_stream = nullptr;
     const void* cover_off = nullptr;
+    // filter_reads.py: what the last gci_bam_reads_size keeps for gci_bam_reads_write (per selected record what its row holds besides
+    // the contig's name, and where the row begins)
+    struct ReadsRow { uint64_t M, I, D, S, end, name_at, byte0; int64_t nm; int32_t contig, pos; uint16_t flag; uint8_t mapq, name_len, cls; };
+    std::vector<ReadsRow> reads_rows;
+    std::vector<uint32_t> reads_name_len;
+    uint64_t reads_total = 0, reads_n_bytes = 0;
+    uint32_t reads_n_rec = 0, reads_file_no = 0;
+    bool reads_valid = false;
+    const void* reads_stream = nullptr;
+    const void* reads_off = nullptr;
 };
 
 namespace {
@@ -316,6 +326,106 @@ int fate_record(const uint8_t* bam, uint64_t n_bytes, uint64_t off, bool has_seq
     if (den2 == 0) return GCI_E_ZERO_DIV;
     cls = (double)(den2 - NM) / (double)den2 >= iden_percent ? GCI_FATE_KEPT : GCI_FATE_IDENTITY;
     return GCI_OK;
+}
+
+// filter_reads.py, one record whose class is asked for (include/gci_hip.h: gci_bam_reads_size): `row` says whether it makes a row, w what
+// the row holds; the return value is what the status word says of the record (GCI_OK: nothing)
+constexpr int64_t READS_NM_NONE = INT64_MAX;
+
+int reads_record(const uint8_t* bam, uint64_t n_bytes, uint64_t off, bool has_seq, const int32_t* ref_sel, int32_t n_ref, int32_t n_sel,
+                 const gci_window* win, const uint32_t* contig_win0, gci_ctx::ReadsRow& w, bool& row)
+{
+    row = false;
+    gci_ctx::CoverRec r;
+    if (cover_parse(bam, n_bytes, off, has_seq, ref_sel, n_ref, 0, 0, r) != GCI_OK) return GCI_E_MALFORMED;
+    if (r.contig < 0 || r.contig >= n_sel) return GCI_E_INVALID;            // the class bytes of another input: such a record is `none`
+    const uint8_t* p = bam + off;
+    int64_t win_b = INT64_MIN;
+    if (contig_win0) {                                                      // the contig's first window that ends behind pos
+        const gci_window* a = win + contig_win0[r.contig];
+        const gci_window* b = win + contig_win0[r.contig + 1];
+        const gci_window* it = std::upper_bound(a, b, (int64_t)r.pos, [](int64_t pos, const gci_window& x) { return pos < x.end; });
+        if (it == b) return GCI_OK;
+        win_b = it->begin;
+    }
+    const uint32_t l_read_name = p[12], n_cigar = rd16(p + 16);
+    const int32_t l_seq = (int32_t)rd32(p + 20);
+    const uint8_t* end = bam + off + 4 + (uint64_t)rd32(p);
+    w.nm = READS_NM_NONE;
+    bool have_nm = false;
+    for (const uint8_t* q = bam + off + 36 + l_read_name + 4ull * n_cigar + (has_seq ? (((uint64_t)(uint32_t)l_seq + 1) >> 1) + (uint64_t)(uint32_t)l_seq : 0ull);
+         q + 3 <= end && !have_nm;) {
+        const int64_t sz = aux_value_size(q + 3, end, q[2]);
+        if (sz < 0 || q + 3 + sz > end) break;
+        if (q[0] == 'N' && q[1] == 'M') { have_nm = true; if (!nm_value(q + 2, w.nm)) w.nm = READS_NM_NONE; }
+        q += 3 + sz;
+    }
+    int code = GCI_OK;
+    uint64_t N = 0;
+    w.M = w.I = w.D = w.S = 0;
+    for (uint32_t k = 0; k < r.n_ops; k++) {
+        const uint32_t v = rd32(bam + r.ops_off + 4ull * k);
+        const uint64_t len = v >> 4;
+        switch (v & 0xFu) {
+        case 0: case 7: case 8: w.M += len; break;
+        case 1: w.I += len; break;
+        case 2: w.D += len; break;
+        case 3: N += len; break;
+        case 4: w.S += len; break;
+        case 5: case 6: break;
+        default: code = GCI_E_MALFORMED; break;                             // (9 - 15 add to no total; the row is listed)
+        }
+    }
+    const uint64_t R = w.M + w.D + N;
+    w.end = (uint64_t)r.pos + R;
+    if ((int64_t)((uint64_t)r.pos + (R ? R : 1)) <= win_b) return GCI_OK;
+    w.contig = r.contig; w.pos = r.pos;
+    w.flag = (uint16_t)rd16(p + 18); w.mapq = p[13];
+    w.name_at = off + 36;
+    uint32_t nl = 0;
+    while (nl < l_read_name && p[36 + nl]) nl++;
+    w.name_len = (uint8_t)nl;
+    row = true;
+    return code;
+}
+
+void reads_dec6(std::string& s, int64_t n, uint64_t d)
+{
+    if (n < 0) s += '-';
+    const uint64_t a = n < 0 ? 0ull - (uint64_t)n : (uint64_t)n;
+    s += std::to_string(a / d);
+    s += '.';
+    uint64_t r = a % d;                                                     // (r < d < 2^59: r * 10 fits)
+    for (int k = 0; k < 6; k++) { r *= 10; s += (char)('0' + r / d); r %= d; }
+}
+
+// the row of w without the contig's name
+void reads_text(std::string& s, const gci_ctx::ReadsRow& w, uint32_t file_no, const uint8_t* bam, const uint8_t* contig, uint32_t contig_len)
+{
+    static const char* const names[13] = {"none", "secondary", "supplementary", "mapq", "clip", "identity", "kept", "error",
+                                          "shadowed", "unpaired", "contig", "overlap", "joined"};
+    s += std::to_string(file_no); s += '\t';
+    s.append((const char*)(bam + w.name_at), w.name_len); s += '\t';
+    if (contig) s.append((const char*)contig, contig_len);
+    s += '\t';
+    s += std::to_string(w.pos); s += '\t';
+    s += std::to_string(w.end); s += '\t';
+    s += (w.flag & 0x10) ? '-' : '+'; s += '\t';
+    s += std::to_string(w.flag); s += '\t';
+    s += std::to_string(w.mapq); s += '\t';
+    s += std::to_string(w.M); s += '\t';
+    s += std::to_string(w.I); s += '\t';
+    s += std::to_string(w.D); s += '\t';
+    s += std::to_string(w.S); s += '\t';
+    if (w.nm == READS_NM_NONE) s += '.'; else s += std::to_string(w.nm);
+    s += '\t';
+    const uint64_t den1 = w.M + w.I + w.S, den2 = w.M + w.I + w.D;
+    if (den1 == 0) s += '.'; else reads_dec6(s, (int64_t)w.S, den1);
+    s += '\t';
+    if (den2 == 0 || w.nm == READS_NM_NONE) s += '.'; else reads_dec6(s, (int64_t)den2 - w.nm, den2);
+    s += '\t';
+    s += names[w.cls < 13 ? w.cls : 7];
+    s += '\n';
 }
 
 // the maximal runs of covering operations of one record: emit(start, end) with `end` the last covered base, both clamped to `lim`;
@@ -867,6 +977,81 @@ int gci_bam_cover_write(gci_ctx* ctx, const uint8_t* bam, uint64_t, const uint64
         }
     });
     *status = ctx->cover_status;
+    return GCI_OK;
+}
+
+/* ---- filter_reads.py: the records of chosen classes over a set of regions as rows of text (k_reads.hip's twins: a record at a time) ---- */
+int gci_bam_reads_size(gci_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, const uint64_t* rec_off, uint32_t n_rec, int has_seq, const int32_t* ref_sel,
+                       int32_t n_ref, const uint8_t* cls, uint32_t class_mask, const gci_window* win, const uint32_t* contig_win0,
+                       const uint32_t* h_contig_name_len, uint32_t file_no, uint64_t* h_n_rows, uint64_t* h_n_bytes, uint64_t* status)
+{
+    if (!ctx || !h_n_rows || !h_n_bytes || !status || n_ref < 0 || (n_rec && (!bam || !rec_off || !ref_sel || !cls))) return GCI_E_INVALID;
+    const int lst = need_layout(ctx);
+    if (lst) return lst;
+    if ((class_mask & ~0x1F7Eu) || !h_contig_name_len || (contig_win0 && !win)) return GCI_E_INVALID;
+    for (int32_t c = 0; c < ctx->n_contigs; c++) if (h_contig_name_len[c] > 65535u) return GCI_E_INVALID;
+    ctx->reads_valid = false;
+    *h_n_rows = 0; *h_n_bytes = 0;
+    std::vector<gci_ctx::ReadsRow> all(n_rec);
+    std::vector<uint8_t> made(n_rec, 0);
+    std::atomic<uint64_t> st{~0ull};
+    parallel_blocks(ctx->threads, n_rec, 4096, [&](uint64_t lo, uint64_t hi) {
+        std::string text;
+        for (uint64_t i = lo; i < hi; i++) {
+            if (!(cls[i] < 32u && ((class_mask >> cls[i]) & 1u))) continue;  // (not read beyond its class byte)
+            bool row = false;
+            const int code = reads_record(bam, n_bytes, rec_off[i], has_seq != 0, ref_sel, n_ref, ctx->n_contigs, win, contig_win0, all[i], row);
+            if (code != GCI_OK) report(st, (uint32_t)i, code);
+            if (!row) continue;
+            all[i].cls = cls[i];
+            text.clear();
+            reads_text(text, all[i], file_no, bam, nullptr, 0);
+            all[i].byte0 = text.size() + h_contig_name_len[all[i].contig];   // (the row's length, until the scan below)
+            made[i] = 1;
+        }
+    });
+    ctx->reads_rows.clear();
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < n_rec; i++) {
+        if (!made[i]) continue;
+        const uint64_t len = all[i].byte0;
+        all[i].byte0 = total;
+        total += len;
+        ctx->reads_rows.push_back(all[i]);
+    }
+    ctx->reads_name_len.assign(h_contig_name_len, h_contig_name_len + ctx->n_contigs);
+    ctx->reads_total = total; ctx->reads_n_bytes = n_bytes; ctx->reads_n_rec = n_rec; ctx->reads_file_no = file_no;
+    ctx->reads_stream = bam; ctx->reads_off = rec_off;
+    ctx->reads_valid = true;
+    *status = st.load();
+    *h_n_rows = ctx->reads_rows.size();
+    *h_n_bytes = total;
+    return GCI_OK;
+}
+
+int gci_bam_reads_write(gci_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, const uint64_t* rec_off, uint32_t n_rec, const uint8_t* contig_names,
+                        const uint64_t* h_contig_name_off, const uint32_t* h_contig_name_len, uint8_t* out, uint64_t cap)
+{
+    if (!ctx || !h_contig_name_off || !h_contig_name_len || (n_rec && (!bam || !rec_off))) return GCI_E_INVALID;
+    const int lst = need_layout(ctx);
+    if (lst) return lst;
+    if (!ctx->reads_valid || n_rec != ctx->reads_n_rec || n_bytes != ctx->reads_n_bytes || bam != ctx->reads_stream || rec_off != ctx->reads_off ||
+        (size_t)ctx->n_contigs != ctx->reads_name_len.size())
+        return GCI_E_INVALID;
+    for (int32_t c = 0; c < ctx->n_contigs; c++) {
+        if (h_contig_name_len[c] != ctx->reads_name_len[(size_t)c] || (h_contig_name_len[c] && !contig_names)) return GCI_E_INVALID;
+    }
+    if (ctx->reads_total && !out) return GCI_E_INVALID;
+    if (cap < ctx->reads_total) return GCI_E_CAPACITY;
+    parallel_blocks(ctx->threads, ctx->reads_rows.size(), 1024, [&](uint64_t lo, uint64_t hi) {
+        std::string text;
+        for (uint64_t k = lo; k < hi; k++) {
+            const gci_ctx::ReadsRow& w = ctx->reads_rows[k];
+            text.clear();
+            reads_text(text, w, ctx->reads_file_no, bam, contig_names + h_contig_name_off[w.contig], h_contig_name_len[w.contig]);
+            memcpy(out + w.byte0, text.data(), text.size());
+        }
+    });
     return GCI_OK;
 }
 

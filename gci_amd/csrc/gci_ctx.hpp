@@ -138,6 +138,15 @@ struct gci_ctx {
     const void* cover_stream = nullptr;
     const void* cover_off = nullptr;
     DevBuf fate_rec, fate_chunk;            // k_fate.hip: per record (parse, NM, chunk counts and their scan) and per chunk (base sums)
+    // k_reads.hip: what gci_bam_reads_size keeps for gci_bam_reads_write -- per record (parse, totals, row length) and per workgroup
+    // of records (row bytes and their scan), per chunk (base sums), the contig name table, and what that call measured
+    DevBuf reads_rec, reads_chunk, reads_names;
+    bool reads_valid = false;
+    uint32_t reads_n_rec = 0, reads_file_no = 0;
+    uint64_t reads_n_bytes = 0, reads_rows = 0, reads_total = 0;
+    const void* reads_stream = nullptr;
+    const void* reads_off = nullptr;
+    std::vector<uint32_t> reads_name_len;   // ... and the contig name lengths its rows were measured with
     void* h_pinned = nullptr;               // staging for small uploads
     size_t h_pinned_cap = 0;
     // optional per-kernel HIP-event timing (gci_profile_*)
@@ -268,6 +277,21 @@ __device__ __forceinline__ uint32_t ndigits_fast(uint32_t v)
     uint32_t n = 1u + (v >= 10u) + (v >= 100u) + (v >= 1000u) + (v >= 10000u);
     if (__builtin_expect(v >= 100000u, 0)) n = ndigits(v);
     return n;
+}
+
+// the same for 64-bit values (coordinates, base totals), and the decimal digits of v, w = ndigits64(v) of them, at p (LDS or global)
+__device__ __forceinline__ uint32_t ndigits64(uint64_t v)
+{
+    if (v <= 0xFFFFFFFFull) return ndigits((uint32_t)v);
+    uint32_t n = 10;
+    for (v /= 10000000000ull; v; v /= 10) n++;
+    return n;
+}
+
+__device__ __forceinline__ void put_dec64(uint8_t* p, uint64_t v, uint32_t w)
+{
+    if (v <= 0xFFFFFFFFull) { uint32_t x = (uint32_t)v; for (uint32_t d = w; d-- > 0;) { p[d] = (uint8_t)('0' + x % 10u); x /= 10u; } }
+    else for (uint32_t d = w; d-- > 0;) { p[d] = (uint8_t)('0' + v % 10u); v /= 10u; }
 }
 
 // `lo < d <= hi` for an integer d as integer bounds: d in [ilo, ihi]  (empty range: ilo > ihi)

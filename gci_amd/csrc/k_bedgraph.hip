@@ -198,14 +198,6 @@ struct BgWin {                           // a window as the text passes see it
 
 struct BgLine { uint64_t start, end; uint64_t name_off; uint32_t name_len, len; int32_t depth; };
 
-__device__ __forceinline__ uint32_t bg_width(uint64_t v)
-{
-    if (v <= 0xFFFFFFFFull) return ndigits((uint32_t)v);
-    uint32_t n = 10;
-    for (v /= 10000000000ull; v; v /= 10) n++;
-    return n;
-}
-
 __device__ __forceinline__ uint32_t bg_depth_width(int32_t d)
 {
     return d < 0 ? 1u + ndigits((uint32_t)(-(int64_t)d)) : ndigits((uint32_t)d);
@@ -224,14 +216,8 @@ __device__ __forceinline__ BgLine bg_line(const gci_depth_run* __restrict__ runs
     L.start = (uint64_t)W.coord0 + me.start;
     L.end = (uint64_t)W.coord0 + rel_end;
     L.name_off = W.name_off; L.name_len = W.name_len; L.depth = me.depth;
-    L.len = W.name_len + 4u + bg_width(L.start) + bg_width(L.end) + bg_depth_width(me.depth);
+    L.len = W.name_len + 4u + ndigits64(L.start) + ndigits64(L.end) + bg_depth_width(me.depth);
     return L;
-}
-
-__device__ __forceinline__ void bg_put_dec(uint8_t* p, uint64_t v, uint32_t w)
-{
-    if (v <= 0xFFFFFFFFull) { uint32_t x = (uint32_t)v; for (uint32_t d = w; d-- > 0;) { p[d] = (uint8_t)('0' + x % 10u); x /= 10u; } }
-    else for (uint32_t d = w; d-- > 0;) { p[d] = (uint8_t)('0' + v % 10u); v /= 10u; }
 }
 
 __device__ __forceinline__ void bg_render(uint8_t* p, const BgLine& L, const uint8_t* __restrict__ names)
@@ -240,16 +226,16 @@ __device__ __forceinline__ void bg_render(uint8_t* p, const BgLine& L, const uin
     for (uint32_t i = 0; i < L.name_len; i++) p[i] = nm[i];
     p += L.name_len;
     *p++ = '\t';
-    uint32_t w = bg_width(L.start);
-    bg_put_dec(p, L.start, w); p += w;
+    uint32_t w = ndigits64(L.start);
+    put_dec64(p, L.start, w); p += w;
     *p++ = '\t';
-    w = bg_width(L.end);
-    bg_put_dec(p, L.end, w); p += w;
+    w = ndigits64(L.end);
+    put_dec64(p, L.end, w); p += w;
     *p++ = '\t';
     uint64_t mag = (uint64_t)L.depth;
     if (L.depth < 0) { *p++ = '-'; mag = (uint64_t)(-(int64_t)L.depth); }
     w = ndigits((uint32_t)mag);
-    bg_put_dec(p, mag, w); p += w;
+    put_dec64(p, mag, w); p += w;
     *p = '\n';
 }
 

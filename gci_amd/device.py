@@ -375,6 +375,33 @@ class Engine:
             self._raise_status(self._status.item(), "gci_bam_fate", rec_idx_base)
         return cls[:n], [int(c) for c in counts]
 
+    def bam_reads(self, d_stream: Buffer, d_rec_off: Buffer, has_seq: bool, d_ref_sel: Buffer, classes: Buffer, mask: int, names: Sequence[bytes],
+                  d_names: Buffer, d_win: Optional[Buffer] = None, d_win0: Optional[Buffer] = None, file_no: int = 1, check: bool = True,
+                  rec_idx_base: int = 0) -> Tuple[bytes, int]:
+        """-> (the rows of text of the records whose class -- bam_fate's bytes -- is a bit of the mask and whose span overlaps a window, in
+        record order; the number of rows): include/gci_hip.h gci_bam_reads_size / _write.  names: the selected contigs' names, d_names their
+        bytes back to back on the device; d_win int64 [n, 2] and d_win0 uint32 [n_sel + 1] as pipeline.merge_windows makes them (None: no
+        window test).  Needs the layout of the selected contigs.  Only the rows cross to the host."""
+        n = int(d_rec_off.shape[0])
+        name_len = np.array([len(x) for x in names], dtype=np.uint32)
+        name_off = np.zeros(max(len(names), 1), dtype=np.uint64)
+        name_off[1:len(names)] = np.cumsum(name_len[:-1], dtype=np.uint64)
+        vp = lambda a: a.ctypes.data_as(ctypes.c_void_p)                                   # noqa: E731
+        rows, size = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._chk(self.lib.gci_bam_reads_size(self.ctx, self._p(d_stream), int(d_stream.shape[0]), self._p(d_rec_off), n, int(has_seq), self._p(d_ref_sel),
+                                              int(d_ref_sel.shape[0]), self._p(classes), int(mask), self._p(d_win) if d_win0 is not None else None,
+                                              self._p(d_win0), vp(name_len), int(file_no), ctypes.byref(rows), ctypes.byref(size),
+                                              self._p(self._status)), "gci_bam_reads_size")
+        if check:
+            self._raise_status(self._status.item(), "gci_bam_reads_size", rec_idx_base)
+        total = int(size.value)
+        if total == 0:
+            return b"", 0
+        out = self.T.empty(total, self.T.uint8, self.device)
+        self._chk(self.lib.gci_bam_reads_write(self.ctx, self._p(d_stream), int(d_stream.shape[0]), self._p(d_rec_off), n, self._p(d_names), vp(name_off),
+                                               vp(name_len), self._p(out), total), "gci_bam_reads_write")
+        return out.cpu().numpy().tobytes(), int(rows.value)
+
     def track_add(self, acc: Buffer, add: Buffer) -> Buffer:
         """acc += add over the layout."""
         self._chk(self.lib.gci_track_add(self.ctx, self._p(acc), self._p(add)), "gci_track_add")

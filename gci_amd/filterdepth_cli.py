@@ -61,17 +61,24 @@ def build_parser(prog: str) -> argparse.ArgumentParser:
         "not its depth -- and the BAM file --cover names is read twice.")
     parser.add_argument("bams", metavar="in.bam", nargs="*", help="BAM file(s); their depths add per class, the contigs are those of the first.  "
                         "With --join: BAM and PAF files of one read set, joined by read name")
+    add_filter_arguments(parser, "GCI_fate", "write")
+    parser.add_argument("-J", dest="count_del", action="store_true", help="Count deletions as covered [False]")
+    return parser
+
+
+def add_filter_arguments(parser: argparse.ArgumentParser, prefix: str, verb: str) -> None:
+    """The options filter_depth.py and filter_reads.py share: where the output goes, the contigs, the record filter's thresholds, the
+    classes to `verb`, the join across files, host threads, -f."""
     parser.add_argument("-d", dest="directory", metavar="DIR", default=".", help="The directory of the output files [.]")
-    parser.add_argument("-o", "--output", dest="prefix", metavar="PREFIX", default="GCI_fate", help="Prefix of the output files [GCI_fate]")
+    parser.add_argument("-o", "--output", dest="prefix", metavar="PREFIX", default=prefix, help="Prefix of the output files [%s]" % prefix)
     parser.add_argument("--chrs", default="", help="A list of chromosomes separated by comma")
     parser.add_argument("-mq", "--map-qual", dest="map_qual", metavar="INT", type=int, default=30, help="Minium mapping quality for alignments [30]")
     parser.add_argument("-ip", "--iden-percent", dest="iden_percent", metavar="FLOAT", type=float, default=0.9,
                         help="Minimum identity (num_match_res/len_aln) of alignments [0.9]")
     parser.add_argument("-cp", "--clip-percent", dest="clip_percent", metavar="FLOAT", type=float, default=0.1,
                         help="Maximum clipped percentage of the alignment [0.1]")
-    parser.add_argument("-J", dest="count_del", action="store_true", help="Count deletions as covered [False]")
-    parser.add_argument("--classes", default=None, help="The classes to write, separated by comma [%s; with --join: %s]"
-                        % (",".join(pipeline.FATE_WANTED), ",".join(JOIN_DEFAULT)))
+    parser.add_argument("--classes", default=None, help="The classes to %s, separated by comma [%s; with --join: %s]"
+                        % (verb, ",".join(pipeline.FATE_WANTED), ",".join(JOIN_DEFAULT)))
     parser.add_argument("--join", action="store_true", help="Apply the join across files by read name and split `kept` by what it does [False]")
     parser.add_argument("-op", "--ovlp-percent", dest="ovlp_percent", metavar="FLOAT", type=float, default=None,
                         help="With --join: minimum overlapping percentage of the same read alignment between files [0.9]")
@@ -80,7 +87,6 @@ def build_parser(prog: str) -> argparse.ArgumentParser:
     parser.add_argument("--cover", metavar="N", type=int, default=None, help="With --join: the N-th BAM file of the command line gives the depth [1]")
     parser.add_argument("-t", "--threads", type=int, default=1, help="Host threads for the ingest paths that inflate on the host [1]")
     parser.add_argument("-f", "--force", action="store_true", help="Force rewriting of existing files [False]")
-    return parser
 
 
 def write_table(path: str, bams, counts, classes, targets, sums, join=None) -> None:
@@ -108,7 +114,8 @@ def write_table(path: str, bams, counts, classes, targets, sums, join=None) -> N
         f.write("\t".join(["total"] + [str(int(sums[c].sum())) for c in classes]) + "\n")
 
 
-def run(args) -> str:
+def checked_options(args):
+    """The option checks that need no file -> (classes, BAM files, pipeline.JoinFateOpts or None); every refusal exits."""
     if not args.bams:
         sys.exit("ERROR!!! No BAM file given")
     if not args.join:
@@ -139,9 +146,11 @@ def run(args) -> str:
                 sys.exit(f'ERROR!!! The file "{path}" does not exist')
         join = pipeline.JoinFateOpts(pafs, 50 if args.mq_cutoff is None else args.mq_cutoff, 0.9 if args.ovlp_percent is None else args.ovlp_percent,
                                      cover - 1)
-    table = f"{args.directory}/{args.prefix}.filter.txt"
-    for path in [f"{args.directory}/{args.prefix}.{c}.depth.gz" for c in classes] + [table]:
-        pipeline.refuse_overwrite(path, args.force)
+    return classes, bams, join
+
+
+def checked_files(args, bams) -> list:
+    """Every BAM file readable, one @SQ table, --chrs in it, the output directory there -> the chromosomes asked for; every refusal exits."""
     for path in bams:
         try:
             bamfmt.read_header(path)
@@ -157,6 +166,26 @@ def run(args) -> str:
             sys.exit(f'ERROR!!! The chromosome "{c}" of --chrs is not in the header of "{bams[0]}"')
     if not os.path.isdir(args.directory):
         os.makedirs(args.directory, exist_ok=True)
+    return chrs
+
+
+def exit_for_record(e: GciError) -> None:
+    """A GciError that names a record the reference would have raised on (or a malformed one) as the command line's message; any other
+    is raised again."""
+    if getattr(e, "in_join", False):
+        sys.exit(f'ERROR!!! The file "{getattr(e, "path", "?")}" holds an alignment of query length zero that the join across files divides by '
+                 f"(record {e.rec}): GCI.py would have raised ZeroDivisionError")
+    if e.status not in WHAT_THE_RECORD_IS or e.rec < 0:
+        raise e
+    sys.exit(f'ERROR!!! The file "{getattr(e, "path", "?")}" ' + WHAT_THE_RECORD_IS[e.status] % e.rec)
+
+
+def run(args) -> str:
+    classes, bams, join = checked_options(args)
+    table = f"{args.directory}/{args.prefix}.filter.txt"
+    for path in [f"{args.directory}/{args.prefix}.{c}.depth.gz" for c in classes] + [table]:
+        pipeline.refuse_overwrite(path, args.force)
+    chrs = checked_files(args, bams)
     opts = pipeline.FateOpts(args.map_qual, args.clip_percent, args.iden_percent, args.count_del)
     engine = pipeline.default_engine()
     try:
@@ -168,12 +197,7 @@ def run(args) -> str:
         sys.exit(f"ERROR!!! The {e.n_tracks} depth tracks of this run ({e.track_bytes} bytes each) do not fit into the free device memory "
                  f"({e.free_bytes} bytes)\nPlease ask for fewer classes (--classes) or fewer contigs (--chrs)")
     except GciError as e:
-        if getattr(e, "in_join", False):
-            sys.exit(f'ERROR!!! The file "{getattr(e, "path", "?")}" holds an alignment of query length zero that the join across files divides by '
-                     f"(record {e.rec}): GCI.py would have raised ZeroDivisionError")
-        if e.status not in WHAT_THE_RECORD_IS or e.rec < 0:
-            raise
-        sys.exit(f'ERROR!!! The file "{getattr(e, "path", "?")}" ' + WHAT_THE_RECORD_IS[e.status] % e.rec)
+        exit_for_record(e)
     sums = {}
     for c in classes:
         depths = result.tracks[c]

@@ -1497,6 +1497,16 @@ def _join_fates(engine: Engine, bam_files: Sequence[str], targets: List[str], op
     return fates[k], int(inputs[k].recs.shape[0]), counts
 
 
+def _join_row(bam_files: Sequence[str], join: JoinFateOpts, join_counts, join_n_rec: int, n_seen: int, n_kept: int) -> List[int]:
+    """The covered file's records per join class, once both passes saw the same records of it and agree on which of them pass
+    (gci_fate_refine checked each one)."""
+    row = join_counts[len(join.paf_files) + join.cover][_lib.JOIN_FATE_FIRST:_lib.JOIN_FATE_FIRST + len(JOIN_FATE_NAMES)]
+    if n_seen != join_n_rec or sum(row) != n_kept:
+        raise GciError(_lib.GCI_E_INVALID, 'the two passes over "%s" disagree: %d records and %d kept in the join, %d and %d in the walk'
+                       % (bam_files[join.cover], join_n_rec, sum(row), n_seen, n_kept))
+    return row
+
+
 def bam_filter_depth(engine: Engine, bam_files: Sequence[str], chrs: Sequence[str], opts: Optional[FateOpts], threads: int,
                      classes: Sequence[str], ivl_budget: Optional[int] = None, join: Optional[JoinFateOpts] = None) -> FilterDepth:
     """Per wanted class of the record filter (FATE_WANTED: the first test of read_sam a record fails, or `kept`) the per-base depth of
@@ -1557,15 +1567,157 @@ def bam_filter_depth(engine: Engine, bam_files: Sequence[str], chrs: Sequence[st
                 totals[c] = track
     result = FilterDepth({ALL_FATE_NAMES[c]: DepthTracks(engine, targets_length, totals[c]) for c in ids}, counts, visitor.flushes)
     if join is not None:
-        # both passes saw the same records of the covered file, and agree on which of them pass (gci_fate_refine checked each one)
-        k = len(join.paf_files) + join.cover
-        row = join_counts[k][_lib.JOIN_FATE_FIRST:_lib.JOIN_FATE_FIRST + len(JOIN_FATE_NAMES)]
-        if visitor.n_seen != join_n_rec or sum(row) != counts[0][_KEPT]:
-            raise GciError(_lib.GCI_E_INVALID, 'the two passes over "%s" disagree: %d records and %d kept in the join, %d and %d in the walk'
-                           % (bam_files[join.cover], join_n_rec, sum(row), visitor.n_seen, counts[0][_KEPT]))
-        counts[0] = counts[0] + row
-        result.join_files, result.join_counts, result.cover_file = list(join.paf_files) + list(bam_files), join_counts, k
+        counts[0] = counts[0] + _join_row(bam_files, join, join_counts, join_n_rec, visitor.n_seen, counts[0][_KEPT])
+        result.join_files, result.join_counts, result.cover_file = list(join.paf_files) + list(bam_files), join_counts, len(join.paf_files) + join.cover
     return result
+
+
+# ==============================================================================================
+# filter_reads.py: the reads over a set of regions, one row each, and what the record filter does with them
+# ==============================================================================================
+
+READS_COLUMNS = ("file", "name", "contig", "start", "end", "strand", "flag", "mapq", "M", "I", "D", "S", "NM", "clip", "identity", "class")
+
+
+def merge_windows(regions: Sequence[Tuple[str, int, int]], targets_length: Dict[str, int]) -> Tuple[np.ndarray, np.ndarray]:
+    """BED rows (contig, start, end) as the windows of gci_bam_reads_size -> (int64 [n, 2]: [begin, end) in contig coordinates, contig
+    after contig in the order of `targets_length`, per contig sorted, disjoint and not abutting; uint32 [n_sel + 1]: every contig's
+    first window, then n).  A row is clamped to its contig; a row on a contig that is not selected, and one that is empty after the
+    clamp, is dropped; rows that overlap or abut are merged."""
+    per = {t: [] for t in targets_length}
+    for name, start, end in regions:
+        if name in per:
+            a, b = max(int(start), 0), min(int(end), int(targets_length[name]))
+            if a < b:
+                per[name].append((a, b))
+    win, win0 = [], [0]
+    for t in targets_length:
+        for a, b in sorted(per[t]):
+            if len(win) > win0[-1] and a <= win[-1][1]:
+                win[-1][1] = max(win[-1][1], b)
+            else:
+                win.append([a, b])
+        win0.append(len(win))
+    return np.asarray(win, dtype=np.int64).reshape(-1, 2), np.asarray(win0, dtype=np.uint32)
+
+
+class FilterReads:
+    """What bam_filter_reads returns: files = the BAM files listed, counts[k][class id] = the records of file k per class (as
+    FilterDepth.counts; with `join` the covered file's row runs on through the join's classes), rows[k] = the rows written for it."""
+
+    def __init__(self, files: List[str], counts: List[List[int]], rows: List[int]):
+        self.files, self.counts, self.rows = files, counts, rows
+
+
+class _ReadsVisitor(_FateVisitor):
+    """Next to _FateVisitor, whose class bytes, join refinement and record counts it shares: per piece gci_bam_fate (+ gci_fate_refine),
+    then gci_bam_reads_size / _write over the class bytes, the rows to the host and behind the file `f`.  Only the rows cross the
+    link.  A file that is read again from its first record (abort_file) loses the rows written for it."""
+
+    def __init__(self, main: Engine, opts: FateOpts, mask: int, names: Sequence[bytes], windows, f, join_fate: Optional[Buffer] = None):
+        super().__init__(main, opts, [], 1, join_fate)
+        self.mask, self.names, self.windows, self.f = int(mask), list(names), windows, f
+        self.file_no, self.rows, self.mark = 0, 0, f.tell()
+        self._on_device: Dict[int, tuple] = {}
+
+    def begin_file(self) -> None:
+        super().begin_file()
+        self.rows, self.mark = 0, self.f.tell()
+
+    def abort_file(self) -> None:
+        self.f.seek(self.mark)
+        self.f.truncate()
+        self.begin_file()
+
+    def _tables(self, engine):
+        """The contig names and the windows on the engine's device, uploaded once."""
+        if id(engine) not in self._on_device:
+            d_names = engine.to_device(np.frombuffer(b"".join(self.names) + b"\0", dtype=np.uint8))
+            d_win = d_win0 = None
+            if self.windows is not None:
+                win, win0 = self.windows
+                d_win = engine.to_device(np.ascontiguousarray(win if win.shape[0] else np.zeros((1, 2), dtype=np.int64)))
+                d_win0 = engine.to_device(win0)
+            self._on_device[id(engine)] = (d_names, d_win, d_win0)
+        return self._on_device[id(engine)]
+
+    def visit(self, engine, d_stream, d_off, has_seq, ref_sel, rec_idx_base) -> None:
+        if engine.lengths != self.main.lengths:            # (the walk engine: a context of its own)
+            engine.set_layout(self.main.lengths)
+        o = self.opts
+        d_names, d_win, d_win0 = self._tables(engine)
+        what = "gci_bam_fate"
+        try:
+            with phases.gpu("record fate"):
+                cls, counts = engine.bam_fate(d_stream, d_off, has_seq, ref_sel, o.map_qual, o.clip_percent, o.iden_percent)
+                if self.join_fate is not None:
+                    what = "gci_fate_refine"
+                    self._refine(engine, cls, int(d_off.shape[0]), rec_idx_base)
+            what = "gci_bam_reads_size"
+            with phases.gpu("record rows"):
+                text, n_rows = engine.bam_reads(d_stream, d_off, has_seq, ref_sel, cls, self.mask, self.names, d_names, d_win, d_win0, self.file_no)
+        except GciError as e:
+            if e.rec < 0:
+                raise
+            raise _file_record_error(engine, e, what, rec_idx_base) from None
+        self.f.write(text)
+        self.rows += n_rows
+        self.n_seen += int(d_off.shape[0])
+        self.counts = [a + b for a, b in zip(self.counts, counts)]
+
+
+def bam_filter_reads(engine: Engine, bam_files: Sequence[str], chrs: Sequence[str], opts: Optional[FateOpts], threads: int, classes: Sequence[str],
+                     regions: Optional[Sequence[Tuple[str, int, int]]], out: str, join: Optional[JoinFateOpts] = None) -> FilterReads:
+    """`out`: one row per record of `bam_files` whose class (bam_filter_depth's: FATE_WANTED, with `join` JOIN_FATE_NAMES too, where
+    `kept` stands for the five of them) is among `classes` and whose reference span overlaps a row of `regions` (BED rows; None:
+    every such record), in the files' record order, file after file -- the columns READS_COLUMNS as include/gci_hip.h
+    (gci_bam_reads_size) states them, behind one `#file` line per listed file and the line of column names.  Contigs, @SQ check,
+    `join` and the errors raised are bam_filter_depth's; with `join` the file join.cover alone is listed."""
+    opts = opts or FateOpts()
+    wanted = FATE_WANTED + (JOIN_FATE_NAMES if join is not None else ())
+    mask = 0
+    for name in classes:
+        if name not in wanted:
+            raise ValueError('"%s" is not one of %s' % (name, ", ".join(wanted)))
+        mask |= _JOIN_FATE_MASK if (join is not None and name == "kept") else 1 << ALL_FATE_NAMES.index(name)
+    if not mask:
+        raise ValueError("no class selected")
+    if join is not None and not 0 <= join.cover < len(bam_files):
+        raise ValueError("cover = %d: there are %d BAM files" % (join.cover, len(bam_files)))
+    first = same_sq_table(bam_files)
+    targets_length = _targets_of(first, list(chrs))
+    targets = list(targets_length.keys())
+    if not targets:
+        raise ValueError("no contig selected")
+    engine.set_layout([targets_length[t] for t in targets])
+    join_fate, join_n_rec, join_counts = _join_fates(engine, bam_files, targets, opts, join, threads) if join is not None else (None, 0, [])
+    listed = list(bam_files) if join is None else [bam_files[join.cover]]
+    windows = None if regions is None else merge_windows(regions, targets_length)
+    counts, rows = [], []
+    try:
+        with open(out, "wb") as f:
+            for k, path in enumerate(listed):
+                f.write(b"#file\t%d\t%s\n" % (k + 1, os.fsencode(path)))
+            f.write(b"#" + "\t".join(READS_COLUMNS).encode() + b"\n")
+            visitor = _ReadsVisitor(engine, opts, mask, [t.encode() for t in targets], windows, f, join_fate)
+            for k, path in enumerate(listed):
+                visitor.file_no = k + 1
+                visitor.begin_file()
+                try:
+                    with phases.wall("bam_reads[%s]" % os.path.basename(path)):
+                        bam_join_input(engine, path, targets, visitor, threads)
+                except GciError as e:
+                    e.path = path                         # (which file the record index counts in: the command line says so)
+                    raise
+                counts.append(list(visitor.counts))
+                rows.append(visitor.rows)
+    except BaseException:
+        if os.path.exists(out):                           # (no half a table is left behind)
+            os.remove(out)
+        raise
+    if join is not None:
+        counts[0] = counts[0] + _join_row(bam_files, join, join_counts, join_n_rec, visitor.n_seen, counts[0][_KEPT])
+    return FilterReads(listed, counts, rows)
 
 
 # ==============================================================================================

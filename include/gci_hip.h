@@ -22,6 +22,7 @@
  *   gci_bam_cover_*, gci_track_add     bam_depth.py: the unfiltered per-base depth of BAM files, `samtools depth -a` (no counterpart in the reference)
  *   gci_bam_fate, gci_bam_cover_size_sel   filter_depth.py: which test of read_sam drops a record (GCI.py:152-168), and the depth of every such class
  *   gci_name_join_fate, gci_fate_refine    filter_depth.py --join: what the cross-file join (GCI.py:272-301) does with every record, and why
+ *   gci_bam_reads_size, gci_bam_reads_write   filter_reads.py: the records over a set of regions as rows of text, each with its class (no counterpart in the reference)
  *   gci_paf_filter_device   filter(), PAF path        GCI.py:211-254  (+ helpers 49-61, 64-96)
  *
  * Conventions
@@ -379,6 +380,43 @@ int gci_name_join_count(gci_ctx* ctx, const gci_join_file* h_files, int n_files,
 int gci_name_join_fate(gci_ctx* ctx, const gci_join_file* h_files, int n_files, double ovlp_percent, uint8_t* const* h_d_fate,
                        uint64_t* h_counts, uint64_t* d_status);
 int gci_fate_refine(gci_ctx* ctx, uint8_t* d_class, const uint8_t* d_join_fate, uint32_t n_rec, uint64_t* d_status);
+
+/* ---- filter_reads.py: the records of chosen classes over a set of regions, one row of text each (k_reads.hip) ----
+ * The same input as gci_bam_fate, d_class = its output (after gci_fate_refine where there is a join).  Needs gci_layout_set: the
+ * selected contigs, n_sel of them, in the order d_ref_sel numbers them.  A record is SELECTED when bit d_class[i] of class_mask is
+ * set and -- with windows -- its reference span overlaps one of its contig's windows.  Bits of class_mask for GCI_FATE_NONE,
+ * GCI_FATE_ERROR or a class that does not exist: GCI_E_INVALID.  A record whose class bit is clear is not read beyond its class
+ * byte, so a malformed record (class GCI_FATE_ERROR) is never touched.
+ *   windows    d_win: the windows of all selected contigs in CONTIG coordinates [begin, end), contig after contig, per contig
+ *              sorted, disjoint and not abutting; d_contig_win0[c] .. d_contig_win0[c + 1] (n_sel + 1 entries, device) are contig c's.
+ *              d_contig_win0 == NULL: no window test.  A record with reference span R at pos overlaps [B, E) when pos < E and
+ *              pos + max(R, 1) > B: a record that consumes no reference still sits on one base.
+ *   CIGAR      the record's own, or the CG:B,I (B,i) array behind a <l_seq>S<n>N placeholder (the rule of gci_bam_filter).  M is the
+ *              bases under M, = and X together, I, D, S and N the bases under those; R = M + D + N.  Totals are summed in 64 bits.
+ *   row        file_no name contig start end strand flag mapq M I D S NM clip identity class, tab-separated, '\n' at the end:
+ *              name = the bytes of read_name in front of its first NUL; contig = h_contig_name_len[c] (<= 65535) bytes at
+ *              d_contig_names + h_contig_name_off[c]; start = pos; end = pos + R (not clamped); strand = '-' with flag 0x10, else '+';
+ *              NM = the first NM tag as a signed decimal, '.' without one or with one of a non-integer type; clip = dec6(S, M + I + S),
+ *              identity = dec6(M + I + D - NM, M + I + D), each '.' where its denominator is 0, identity also where NM is '.';
+ *              dec6(n, d) = '-' if n < 0, |n| / d, '.', and the six digits of ((|n| % d) * 10^6) / d -- truncated, exact;
+ *              class = the name of d_class[i] (none secondary supplementary mapq clip identity kept error shadowed unpaired contig
+ *              overlap joined).  The class column is authoritative; the two decimals are for the eye.
+ *   *d_status  (smallest record index << 8 | -status, UINT64_MAX if none) for records whose class bit is set: GCI_E_MALFORMED for one
+ *              that runs past the end of the stream or contradicts its block_size (no row), and for operation codes 9 - 15 in a
+ *              selected record (they add to no total; the row is listed); GCI_E_INVALID for one d_class cannot belong to -- refID outside 0 .. n_ref - 1,
+ *              pos < 0, d_ref_sel[refID] outside 0 .. n_sel - 1 (no row).
+ * gci_bam_reads_size: *h_n_rows = the selected records, *h_n_bytes = the bytes of their rows; *d_status is complete.  Synchronises.
+ *   The scratch of this call stays in the context for the write call.
+ * gci_bam_reads_write: the rows of the input the size call in front of it on this context measured (same d_stream, n_bytes,
+ *   d_rec_off, n_rec and name lengths: else GCI_E_INVALID) to d_out[0 .. *h_n_bytes), in record order.  cap < *h_n_bytes:
+ *   GCI_E_CAPACITY, nothing is written.  Does not synchronise. */
+int gci_bam_reads_size(gci_ctx* ctx, const uint8_t* d_stream, uint64_t n_bytes, const uint64_t* d_rec_off, uint32_t n_rec, int has_seq,
+                       const int32_t* d_ref_sel, int32_t n_ref, const uint8_t* d_class, uint32_t class_mask, const gci_window* d_win,
+                       const uint32_t* d_contig_win0, const uint32_t* h_contig_name_len, uint32_t file_no, uint64_t* h_n_rows,
+                       uint64_t* h_n_bytes, uint64_t* d_status);
+int gci_bam_reads_write(gci_ctx* ctx, const uint8_t* d_stream, uint64_t n_bytes, const uint64_t* d_rec_off, uint32_t n_rec,
+                        const uint8_t* d_contig_names, const uint64_t* h_contig_name_off, const uint32_t* h_contig_name_len, uint8_t* d_out,
+                        uint64_t cap);
 
 /* Cross-rank name check for contig-sharded runs (exact).  gci_hash_bucket sorts the 64-bit name hashes of the
  * passing records into n_parts buckets by (hash >> 33) % n_parts; a bucket is part_cap + 1 uint64 words:
