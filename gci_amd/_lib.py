@@ -31,10 +31,26 @@ JOIN_FATE_FIRST = 8
 JOIN_FATE_CLASSES = 16        # GCI_JOIN_FATE_CLASSES: entries of a row of gci_name_join_fate's counts
 ALL_FATE_NAMES = FATE_NAMES + JOIN_FATE_NAMES                                # a class id is its index here
 READS_CLASS_MASK = 0x1F7E     # the classes gci_bam_reads_size lists: every one but none and error
+SWEEP_COLS = 4                # GCI_SWEEP_COLS: records, bases, records_others, bases_others
+SWEEP_COLUMNS = ("records", "bases", "records_others", "bases_others")
 PROF_COUNT = 19
 PROF_DEPTH_SCAN = 5          # k_tile_build: the pass that writes the depth track (+ text)
 PROF_TILE_PASS1 = 13
 PROF_TILE_DENSE = 14         # k_tile_dense<1>, <2>: the tiles the event-list kernels left over
+
+
+class SweepRows:
+    """The rows of gci_bam_sweep's table at `digits` = K, as the GCI_SWEEP_* macros of include/gci_hip.h number them: 256 of mapq; clip
+    0 .. B, undefined; identity <0, 0 .. B, >1, undefined."""
+
+    def __init__(self, digits: int):
+        if digits not in (1, 2, 3):
+            raise ValueError("digits = %r: 1, 2 or 3" % (digits,))
+        self.digits, self.bins = digits, 10 ** digits                            # GCI_SWEEP_BINS
+        b = self.bins
+        self.mapq0, self.clip0, self.clip_undef = 0, 256, 256 + b + 1            # GCI_SWEEP_MAPQ(0), _CLIP(K, 0), _CLIP_UNDEF(K)
+        self.iden_below, self.iden0, self.iden_above, self.iden_undef = 256 + b + 2, 256 + b + 3, 256 + 2 * b + 4, 256 + 2 * b + 5
+        self.rows = 256 + 2 * b + 6                                              # GCI_SWEEP_ROWS(K)
 
 
 class GciError(RuntimeError):
@@ -128,6 +144,8 @@ EXPORTS = [
     ("gci_bam_reads_size", c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_int, c_void_p, c_int32, c_void_p, c_uint32, c_void_p,
                                    c_void_p, c_void_p, c_uint32, POINTER(c_uint64), POINTER(c_uint64), c_void_p]),
     ("gci_bam_reads_write", c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64]),
+    ("gci_bam_sweep", c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_int, c_void_p, c_int32, c_void_p, c_void_p, c_int, c_double, c_double,
+                              c_int, c_void_p, c_void_p]),
     ("gci_depth_deflate_from_build", c_int, [c_void_p, c_void_p]),
     ("gci_depth_deflate_size", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("gci_depth_deflate_write", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p,

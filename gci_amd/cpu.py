@@ -42,7 +42,7 @@ gci_depth_build gci_gap_mask gci_max2 gci_issue_scan gci_issue_scan_windows gci_
 gci_depth_sum gci_range_sums gci_depth_deflate_from_build gci_depth_deflate_size gci_depth_deflate_write gci_depth_text_index
 gci_depth_text_parse gci_sdepth_index gci_sdepth_parse gci_depth_gz_scan gci_depth_gz_runs gci_depth_gz_expand gci_depth_runs_count
 gci_depth_runs_write gci_bedgraph_size gci_bedgraph_write gci_depth_hist gci_bam_cover_size gci_bam_cover_write gci_track_add
-gci_bam_fate gci_bam_cover_size_sel gci_name_join_fate gci_fate_refine gci_bam_reads_size gci_bam_reads_write""".split()
+gci_bam_fate gci_bam_cover_size_sel gci_name_join_fate gci_fate_refine gci_bam_reads_size gci_bam_reads_write gci_bam_sweep""".split()
 _PROTO = {name: (name, res, args) for name, res, args in _lib.EXPORTS}
 EXPORTS = [_PROTO[name] for name in _SEAMS] + [("gci_cpu_option", c_int, [c_void_p, c_char_p, c_int])]
 
@@ -223,6 +223,28 @@ class CpuEngine:
         if (out[int(size.value):] != 0xA5).any():
             raise CpuError(-1, "gci_bam_reads_write wrote behind its rows")
         return out[:int(size.value)].tobytes(), int(rows.value)
+
+    def bam_sweep(self, stream: np.ndarray, offs: np.ndarray, ref_sel: np.ndarray, map_qual: int, clip_percent: float, iden_percent: float,
+                  digits: int = 3, win: Optional[np.ndarray] = None, win0: Optional[np.ndarray] = None, has_seq: bool = True, check: bool = True,
+                  guard: int = 0) -> np.ndarray:
+        """device.Engine.bam_sweep's twin -> the table uint64 [GCI_SWEEP_ROWS(digits), 4]; win / win0 as for bam_reads.  guard: entries
+        of a pattern behind the table that must stay (the table itself is pre-filled with it)."""
+        stream = np.ascontiguousarray(stream, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        ref_sel = np.ascontiguousarray(ref_sel, dtype=np.int32)
+        if win0 is not None:
+            win, win0 = np.ascontiguousarray(win, dtype=np.int64).reshape(-1, 2), np.ascontiguousarray(win0, dtype=np.uint32)
+        cells = _lib.SWEEP_COLS * _lib.SweepRows(digits).rows
+        table = np.full(cells + guard, 0xA5A5A5A5A5A5A5A5, dtype=np.uint64)
+        self.last_status = np.zeros(1, dtype=np.uint64)
+        self._chk(self.lib.gci_bam_sweep(self.ctx, _p(stream), stream.shape[0], _p(offs), offs.shape[0], int(has_seq), _p(ref_sel), ref_sel.shape[0],
+                                         _p(win) if win0 is not None else None, _p(win0), int(map_qual), float(clip_percent), float(iden_percent),
+                                         int(digits), _p(table), _p(self.last_status)), "gci_bam_sweep")
+        if (table[cells:] != 0xA5A5A5A5A5A5A5A5).any():
+            raise CpuError(-1, "gci_bam_sweep wrote behind its table")
+        if check:
+            self._status(self.last_status, "gci_bam_sweep")
+        return table[:cells].reshape(-1, _lib.SWEEP_COLS)
 
     def track_add(self, acc: np.ndarray, add: np.ndarray) -> np.ndarray:
         self._chk(self.lib.gci_track_add(self.ctx, _p(acc), _p(add)), "gci_track_add")

@@ -48,6 +48,7 @@ extern "C" int gci_ctx_create(int device, void* stream, int own_stream, gci_ctx*
     { const char* fd = getenv("GCI_FORCE_DENSE"); if (fd && fd[0] == '1') ctx->sparse_max = -1; }   // testing / A-B timing
     { const char* m = getenv("GCI_JOIN"); ctx->join_mode = m && m[0] == 'c' ? 1 : m && m[0] == 'p' ? 2 : 0; }
     { const char* g = getenv("GCI_PAGES_GRID"); const long n = g ? atol(g) : 0; ctx->pg_grid_cap = n > 0 && n < (1 << 20) ? (uint32_t)n : 0u; }   // testing
+    { const char* g = getenv("GCI_SWEEP_GRID"); const long n = g ? atol(g) : 0; ctx->sweep_grid_cap = n > 0 && n < (1 << 20) ? (uint32_t)n : 0u; }   // testing
     hipError_t e = hipSetDevice(device);
     if (e != hipSuccess) { delete ctx; return GCI_E_HIP; }
     if (!own_stream) { ctx->stream = (hipStream_t)stream; }    // NULL = the device's default stream
@@ -80,7 +81,7 @@ extern "C" int gci_ctx_destroy(gci_ctx* ctx)
                       &ctx->tile_u64, &ctx->blk_u64, &ctx->join_table, &ctx->join_last, &ctx->join_hq, &ctx->join_fate, &ctx->part_a, &ctx->part_b, &ctx->part_hist, &ctx->part_blk, &ctx->conflict_table, &ctx->win,
                       &ctx->win_tile_first, &ctx->text_lut, &ctx->long_items, &ctx->pg_scan, &ctx->pg_first, &ctx->pg_list, &ctx->route_tab, &ctx->deflate_nruns, &ctx->deflate_runs, &ctx->deflate_tab, &ctx->dgz_tiles, &ctx->build_nruns, &ctx->build_runs, &ctx->join_bucket, &ctx->tail_gaps, &ctx->tail_sums, &ctx->class_sums, &ctx->crc_tabs, &ctx->inflate_sym, &ctx->inflate_nsym, &ctx->inflate_wstatus, &ctx->inflate_lists, &ctx->inflate_prof, &ctx->inflate_next, &ctx->inflate_sym2, &ctx->inflate_lists2,
                       &ctx->bg_tile_cnt, &ctx->bg_tile_off, &ctx->bg_blk, &ctx->bg_wtab, &ctx->bg_blk_bytes, &ctx->bg_blk_off, &ctx->bg_blk2, &ctx->hist_chunk_first,
-                      &ctx->cover_rec, &ctx->cover_chunk, &ctx->fate_rec, &ctx->fate_chunk, &ctx->reads_rec, &ctx->reads_chunk, &ctx->reads_names};
+                      &ctx->cover_rec, &ctx->cover_chunk, &ctx->fate_rec, &ctx->fate_chunk, &ctx->reads_rec, &ctx->reads_chunk, &ctx->reads_names, &ctx->sweep_rec, &ctx->sweep_chunk};
     for (DevBuf* b : bufs) if (b->p) (void)gci_dfree(b->p);
     for (DevBuf& b : ctx->paf_pool) if (b.p) (void)gci_dfree(b.p);
     if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);

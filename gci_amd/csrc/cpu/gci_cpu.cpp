@@ -389,6 +389,89 @@ int reads_record(const uint8_t* bam, uint64_t n_bytes, uint64_t off, bool has_se
     return code;
 }
 
+// filter_sweep.py, one record (include/gci_hip.h: gci_bam_sweep): `counted` says whether it is a primary record that overlaps a window;
+// then rows[3] are its rows in the mapq, clip and identity tables, pass[3] the three tests at the thresholds, each on its own, and M
+// the bases it covers.  The return value is what the status word says of the record (GCI_OK: nothing).
+uint32_t sweep_digits(uint64_t n, uint64_t d, int digits, bool& rest)      // floor(n * 10^digits / d) by long division, 0 <= n <= d
+{
+    uint64_t q = n / d, r = n % d;                                          // (r < d < 2^59: r * 10 fits)
+    for (int k = 0; k < digits; k++) { r *= 10; q = q * 10 + r / d; r %= d; }
+    rest = r != 0;
+    return (uint32_t)q;
+}
+
+int sweep_record(const uint8_t* bam, uint64_t n_bytes, uint64_t off, bool has_seq, const int32_t* ref_sel, int32_t n_ref, int32_t n_sel,
+                 const gci_window* win, const uint32_t* contig_win0, int map_qual, double clip_percent, double iden_percent, int digits,
+                 bool& counted, uint32_t rows[3], bool pass[3], uint64_t& M)
+{
+    counted = false;
+    gci_ctx::CoverRec r;
+    if (cover_parse(bam, n_bytes, off, has_seq, ref_sel, n_ref, 0x904, 0, r) != GCI_OK) return GCI_E_MALFORMED;
+    if (r.contig < 0) return GCI_OK;                                        // none, secondary or supplementary
+    int64_t win_b = INT64_MIN;
+    if (contig_win0) {                                                      // the contig's first window that ends behind pos
+        if (r.contig >= n_sel) return GCI_OK;
+        const gci_window* a = win + contig_win0[r.contig];
+        const gci_window* b = win + contig_win0[r.contig + 1];
+        const gci_window* it = std::upper_bound(a, b, (int64_t)r.pos, [](int64_t pos, const gci_window& x) { return pos < x.end; });
+        if (it == b) return GCI_OK;
+        win_b = it->begin;
+    }
+    const uint8_t* p = bam + off;
+    const uint32_t l_read_name = p[12], n_cigar = rd16(p + 16);
+    const int32_t l_seq = (int32_t)rd32(p + 20);
+    const uint8_t* end = bam + off + 4 + (uint64_t)rd32(p);
+    int64_t nm = 0;
+    bool have_nm = false, nm_ok = false;
+    for (const uint8_t* q = bam + off + 36 + l_read_name + 4ull * n_cigar + (has_seq ? (((uint64_t)(uint32_t)l_seq + 1) >> 1) + (uint64_t)(uint32_t)l_seq : 0ull);
+         q + 3 <= end && !have_nm;) {
+        const int64_t sz = aux_value_size(q + 3, end, q[2]);
+        if (sz < 0 || q + 3 + sz > end) break;
+        if (q[0] == 'N' && q[1] == 'M') { have_nm = true; nm_ok = nm_value(q + 2, nm); }
+        q += 3 + sz;
+    }
+    int code = GCI_OK;
+    uint64_t I = 0, D = 0, N = 0, S = 0;
+    M = 0;
+    for (uint32_t k = 0; k < r.n_ops; k++) {
+        const uint32_t v = rd32(bam + r.ops_off + 4ull * k);
+        const uint64_t len = v >> 4;
+        switch (v & 0xFu) {
+        case 0: case 7: case 8: M += len; break;
+        case 1: I += len; break;
+        case 2: D += len; break;
+        case 3: N += len; break;
+        case 4: S += len; break;
+        case 5: case 6: break;
+        default: code = GCI_E_MALFORMED; break;                             // (9 - 15 add to no total; the record is counted)
+        }
+    }
+    const uint64_t R = M + D + N;
+    if ((int64_t)((uint64_t)r.pos + (R ? R : 1)) <= win_b) return GCI_OK;
+    counted = true;
+    const uint32_t mapq = p[13];
+    const uint64_t den1 = M + I + S, den2 = M + I + D;
+    bool rest = false;
+    rows[0] = GCI_SWEEP_MAPQ(mapq);
+    pass[0] = (int)mapq >= map_qual;
+    pass[1] = pass[2] = false;
+    if (den1 == 0) rows[1] = GCI_SWEEP_CLIP_UNDEF(digits);
+    else {
+        const uint32_t q = sweep_digits(S, den1, digits, rest);
+        rows[1] = GCI_SWEEP_CLIP(digits, q + (rest ? 1u : 0u));
+        pass[1] = (double)S / (double)den1 <= clip_percent;
+    }
+    if (!nm_ok || den2 == 0) rows[2] = GCI_SWEEP_IDEN_UNDEF(digits);
+    else {
+        const int64_t num = (int64_t)den2 - nm;
+        if (num < 0) rows[2] = GCI_SWEEP_IDEN_BELOW(digits);
+        else if ((uint64_t)num > den2) rows[2] = GCI_SWEEP_IDEN_ABOVE(digits);
+        else rows[2] = GCI_SWEEP_IDEN(digits, sweep_digits((uint64_t)num, den2, digits, rest));
+        pass[2] = (double)num / (double)den2 >= iden_percent;
+    }
+    return code;
+}
+
 void reads_dec6(std::string& s, int64_t n, uint64_t d)
 {
     if (n < 0) s += '-';
@@ -1052,6 +1135,38 @@ int gci_bam_reads_write(gci_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, cons
             memcpy(out + w.byte0, text.data(), text.size());
         }
     });
+    return GCI_OK;
+}
+
+/* ---- filter_sweep.py: the three tables of the record filter's thresholds (k_sweep.hip's twin: a plain loop over the records) ------------ */
+int gci_bam_sweep(gci_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, const uint64_t* rec_off, uint32_t n_rec, int has_seq, const int32_t* ref_sel,
+                  int32_t n_ref, const gci_window* win, const uint32_t* contig_win0, int map_qual, double clip_percent, double iden_percent, int digits,
+                  uint64_t* h_table, uint64_t* status)
+{
+    if (!ctx || !h_table || !status || n_ref < 0 || (n_rec && (!bam || !rec_off || !ref_sel))) return GCI_E_INVALID;
+    if (digits < 1 || digits > 3 || (contig_win0 && !win)) return GCI_E_INVALID;
+    if (contig_win0) {
+        const int lst = need_layout(ctx);
+        if (lst) return lst;
+    }
+    const size_t cells = (size_t)GCI_SWEEP_COLS * GCI_SWEEP_ROWS(digits);
+    std::fill(h_table, h_table + cells, (uint64_t)0);
+    uint64_t st = ~0ull;
+    for (uint32_t i = 0; i < n_rec; i++) {
+        bool counted = false, pass[3];
+        uint32_t rows[3];
+        uint64_t M = 0;
+        const int code = sweep_record(bam, n_bytes, rec_off[i], has_seq != 0, ref_sel, n_ref, ctx->n_contigs, win, contig_win0, map_qual, clip_percent,
+                                      iden_percent, digits, counted, rows, pass, M);
+        if (code != GCI_OK) st = std::min(st, ((uint64_t)i << 8) | (uint64_t)(uint8_t)(-code));
+        if (!counted) continue;
+        for (int k = 0; k < 3; k++) {
+            uint64_t* row = h_table + (size_t)rows[k] * GCI_SWEEP_COLS;
+            row[0] += 1; row[1] += M;
+            if (pass[(k + 1) % 3] && pass[(k + 2) % 3]) { row[2] += 1; row[3] += M; }
+        }
+    }
+    *status = st;
     return GCI_OK;
 }
 

@@ -147,6 +147,8 @@ struct gci_ctx {
     const void* reads_stream = nullptr;
     const void* reads_off = nullptr;
     std::vector<uint32_t> reads_name_len;   // ... and the contig name lengths its rows were measured with
+    DevBuf sweep_rec, sweep_chunk;          // k_sweep.hip: per record (parse, NM, window, chunk counts and their scan) + the table, and per chunk (base sums)
+    uint32_t sweep_grid_cap = 0;            // GCI_SWEEP_GRID=<n>: at most n workgroups for k_sweep_bin (testing; 0: what the device holds)
     void* h_pinned = nullptr;               // staging for small uploads
     size_t h_pinned_cap = 0;
     // optional per-kernel HIP-event timing (gci_profile_*)

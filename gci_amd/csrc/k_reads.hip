@@ -6,8 +6,8 @@
 //   k_reads_parse    one lane per record whose class bit is set (the others are not read beyond their class byte): bounds, core fields,
 //                    the contig's first window that ends behind pos -- none: no row, no chunk --, the first NM tag, where the operations
 //                    lie (own CIGAR or CG array) and how many chunks they make
-//   k_reads_sum      one wave per chunk: the bases under S, M / = / X, I, D and N, summed over the wave; whether it holds a code 9 - 15;
-//                    no atomics
+//   k_cigar_sums     one wave per chunk: the bases under S, M / = / X, I, D and N, summed over the wave; whether it holds a code 9 - 15;
+//                    no atomics (gci_cigar_sums.hpp, shared with k_sweep.hip)
 //   k_reads_measure  one lane per record: adds the chunk sums, span and overlap (the windows of a contig are sorted and disjoint, so the
 //                    one k_reads_parse found is the only one to ask), the row's length, GCI_E_MALFORMED for codes 9 - 15 in a row;
 //                    rows and bytes per workgroup
@@ -16,7 +16,7 @@
 //                    (read names of 254 bytes, contig names of any length) renders them straight into memory
 // with exclusive scans between them (chunks per record; bytes and rows per workgroup, 64 bits).  What a row holds besides the two names
 // lives in the context between the two calls (ReadsRow): the write pass reads no record again but its name.
-#include "gci_cover_chunks.hpp"
+#include "gci_cigar_sums.hpp"
 
 #define RD_STAGE 49152                   // LDS bytes of staging: 16 for the alignment shift + the rows of a workgroup (~120 bytes each for HiFi names)
 #define RD_CONTIG_NAME_MAX 65535u
@@ -33,8 +33,6 @@ struct ReadsRow {                        // what a row holds besides the two nam
     uint16_t flag;
     uint8_t mapq, name_len;
 };
-
-struct ReadsSums { unsigned long long S, M, I, D, N, bad; };      // (bad: the chunk holds an operation code 9 - 15)
 
 struct ReadsScratch {                    // carved out of ctx->reads_rec
     unsigned long long* status;
@@ -174,40 +172,6 @@ __global__ __launch_bounds__(BLOCK) void k_reads_parse(const uint8_t* __restrict
     rows[i] = w;
 }
 
-// ---- step 2: one wave per chunk ---------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(BLOCK) void k_reads_sum(const uint8_t* __restrict__ bam, uint64_t n_bytes, const CoverRec* __restrict__ recs,
-                                                     const unsigned long long* __restrict__ chunk0, uint32_t n_rec, unsigned long long n_chunks,
-                                                     ReadsSums* __restrict__ sums)
-{
-    const int lane = threadIdx.x & 63;
-    const unsigned long long ch = (unsigned long long)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6);
-    if (ch >= n_chunks) return;                        // (the whole wave)
-    const uint32_t rec = cv_rec_of_chunk(chunk0, n_rec, ch);
-    const CoverRec r = recs[rec];
-    const CvChunk c = cv_chunk_of(bam, r, (uint32_t)(ch - chunk0[rec]));
-    unsigned long long s = 0, m = 0, ins = 0, del = 0, skip = 0;
-    bool bad = false;
-    for (uint32_t k0 = 0; k0 < c.n; k0 += 64) {
-        const uint32_t k = k0 + lane;
-        const uint32_t v = cv_op_word(bam, n_bytes, c, k, lane);
-        const uint32_t op = v & 0xFu, len = k < c.n ? v >> 4 : 0u;
-        bad |= k < c.n && op >= 9u;
-        s += op == 4u ? len : 0u;
-        m += ((0x181u >> op) & 1u) ? len : 0u;                                   // M = X
-        ins += op == 1u ? len : 0u;
-        del += op == 2u ? len : 0u;
-        skip += op == 3u ? len : 0u;
-    }
-    ReadsSums t;
-    t.S = wave_sum<unsigned long long>(s);
-    t.M = wave_sum<unsigned long long>(m);
-    t.I = wave_sum<unsigned long long>(ins);
-    t.D = wave_sum<unsigned long long>(del);
-    t.N = wave_sum<unsigned long long>(skip);
-    t.bad = __ballot(bad) != 0ull ? 1ull : 0ull;
-    if (lane == 0) sums[ch] = t;
-}
-
 // ---- a row, written once for the pass that measures it and the pass that renders it ---------------------------------------------------
 __device__ static const char RD_CLASS_NAME[13][14] = {"none", "secondary", "supplementary", "mapq", "clip", "identity", "kept", "error",
                                                       "shadowed", "unpaired", "contig", "overlap", "joined"};
@@ -281,7 +245,7 @@ __device__ __forceinline__ void rd_row(E& e, const ReadsRow& w, const CoverRec& 
 
 // ---- step 3: one lane per record ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(BLOCK) void k_reads_measure(uint32_t n_rec, const CoverRec* __restrict__ recs, const unsigned long long* __restrict__ chunk0,
-                                                         const ReadsSums* __restrict__ sums, const uint32_t* __restrict__ contig_name_len,
+                                                         const CigarSums* __restrict__ sums, const uint32_t* __restrict__ contig_name_len,
                                                          uint32_t file_no, ReadsRow* __restrict__ rows, uint32_t* __restrict__ blk_bytes,
                                                          uint32_t* __restrict__ blk_rows, unsigned long long* __restrict__ status)
 {
@@ -295,7 +259,7 @@ __global__ __launch_bounds__(BLOCK) void k_reads_measure(uint32_t n_rec, const C
             ReadsRow w = rows[i];
             unsigned long long N = 0, bad = 0;
             for (unsigned long long ch = chunk0[i], e = chunk0[i + 1]; ch < e; ch++) {
-                const ReadsSums s = sums[ch];
+                const CigarSums s = sums[ch];
                 w.S += s.S; w.M += s.M; w.I += s.I; w.D += s.D; N += s.N; bad |= s.bad;
             }
             const unsigned long long R = w.M + w.D + N;                          // (every total is below 2^57)
@@ -382,13 +346,13 @@ extern "C" int gci_bam_reads_size(gci_ctx* ctx, const uint8_t* d_stream, uint64_
         HIPCHK(hipMemcpyAsync(&n_chunks, R.chunk0 + n_rec, 8, hipMemcpyDeviceToHost, ctx->stream));
         HIPCHK(hipStreamSynchronize(ctx->stream));
         if (n_chunks > 0x7FFFFFFFull) return GCI_E_INVALID;                  // (2^42 operations in one call)
-        ReadsSums* sums = nullptr;
+        CigarSums* sums = nullptr;
         if (n_chunks) {
-            GCI_TRY(gci_ensure(ctx, ctx->reads_chunk, sizeof(ReadsSums) * (size_t)n_chunks));
-            sums = (ReadsSums*)ctx->reads_chunk.p;
-            hipLaunchKernelGGL(k_reads_sum, dim3((uint32_t)((n_chunks + BLOCK / 64 - 1) / (BLOCK / 64))), dim3(BLOCK), 0, ctx->stream, d_stream, n_bytes,
-                               R.recs, R.chunk0, n_rec, n_chunks, sums);
-            LAUNCHCHK("k_reads_sum");
+            GCI_TRY(gci_ensure(ctx, ctx->reads_chunk, sizeof(CigarSums) * (size_t)n_chunks));
+            sums = (CigarSums*)ctx->reads_chunk.p;
+            hipLaunchKernelGGL(k_cigar_sums, cigar_sums_grid(n_chunks), dim3(BLOCK), 0, ctx->stream, d_stream, n_bytes, R.recs, R.chunk0, n_rec, n_chunks,
+                               sums);
+            LAUNCHCHK("k_cigar_sums");
         }
         hipLaunchKernelGGL(k_reads_measure, dim3(groups), dim3(BLOCK), 0, ctx->stream, n_rec, R.recs, R.chunk0, sums, d_name_len, file_no, R.rows,
                            R.blk_bytes, R.blk_rows, R.status);

@@ -402,6 +402,23 @@ class Engine:
                                                vp(name_len), self._p(out), total), "gci_bam_reads_write")
         return out.cpu().numpy().tobytes(), int(rows.value)
 
+    def bam_sweep(self, d_stream: Buffer, d_rec_off: Buffer, has_seq: bool, d_ref_sel: Buffer, map_qual: int, clip_percent: float, iden_percent: float,
+                  digits: int = 3, d_win: Optional[Buffer] = None, d_win0: Optional[Buffer] = None, check: bool = True,
+                  rec_idx_base: int = 0) -> np.ndarray:
+        """-> the table uint64 [GCI_SWEEP_ROWS(digits), 4] (records, bases, records_others, bases_others; the rows as _lib.SweepRows
+        numbers them) of the primary records of an inflated BAM stream (has_seq) or a heads stream: their MAPQ, clip and identity
+        quotients, and what passes the other two tests at these thresholds (include/gci_hip.h: gci_bam_sweep).  d_win / d_win0 as for
+        bam_reads (None: no window test; with windows the layout of the selected contigs is needed)."""
+        n = int(d_rec_off.shape[0])
+        table = np.zeros((_lib.SweepRows(digits).rows, _lib.SWEEP_COLS), dtype=np.uint64)
+        self._chk(self.lib.gci_bam_sweep(self.ctx, self._p(d_stream), int(d_stream.shape[0]), self._p(d_rec_off), n, int(has_seq), self._p(d_ref_sel),
+                                         int(d_ref_sel.shape[0]), self._p(d_win) if d_win0 is not None else None, self._p(d_win0), int(map_qual),
+                                         float(clip_percent), float(iden_percent), int(digits), table.ctypes.data_as(ctypes.c_void_p),
+                                         self._p(self._status)), "gci_bam_sweep")
+        if check:
+            self._raise_status(self._status.item(), "gci_bam_sweep", rec_idx_base)
+        return table
+
     def track_add(self, acc: Buffer, add: Buffer) -> Buffer:
         """acc += add over the layout."""
         self._chk(self.lib.gci_track_add(self.ctx, self._p(acc), self._p(add)), "gci_track_add")

@@ -1721,6 +1721,133 @@ def bam_filter_reads(engine: Engine, bam_files: Sequence[str], chrs: Sequence[st
 
 
 # ==============================================================================================
+# filter_sweep.py: how the record filter's three thresholds cut a BAM file
+# ==============================================================================================
+
+SWEEP_COLUMNS = ("value",) + _lib.SWEEP_COLUMNS + ("kept_at", "kept_bases_at")
+
+
+class FilterSweep:
+    """What bam_filter_sweep returns: files = the BAM files, tables[k] = file k's table uint64 [GCI_SWEEP_ROWS(digits), 4] (records,
+    bases, records_others, bases_others; the rows as _lib.SweepRows(digits) numbers them)."""
+
+    def __init__(self, files: List[str], tables: List[np.ndarray], digits: int):
+        self.files, self.tables, self.digits = files, tables, digits
+
+
+class _SweepVisitor(StreamVisitor):
+    """Per piece of a file ONE gci_bam_sweep call; the pieces' tables add on the host (a table is 72 KB at three digits)."""
+
+    def __init__(self, main: Engine, opts: FateOpts, digits: int, windows):
+        self.main, self.opts, self.digits, self.windows = main, opts, int(digits), windows
+        self.table = np.zeros((_lib.SweepRows(self.digits).rows, _lib.SWEEP_COLS), dtype=np.uint64)
+        self._on_device: Dict[int, tuple] = {}
+
+    def begin_file(self) -> None:
+        self.table[:] = 0
+
+    abort_file = begin_file
+
+    def _windows(self, engine):
+        """The windows on the engine's device, uploaded once."""
+        if self.windows is None:
+            return None, None
+        if id(engine) not in self._on_device:
+            win, win0 = self.windows
+            self._on_device[id(engine)] = (engine.to_device(np.ascontiguousarray(win if win.shape[0] else np.zeros((1, 2), dtype=np.int64))),
+                                           engine.to_device(win0))
+        return self._on_device[id(engine)]
+
+    def visit(self, engine, d_stream, d_off, has_seq, ref_sel, rec_idx_base) -> None:
+        if engine.lengths != self.main.lengths:            # (the walk engine: a context of its own)
+            engine.set_layout(self.main.lengths)
+        o = self.opts
+        d_win, d_win0 = self._windows(engine)
+        try:
+            with phases.gpu("record sweep"):
+                self.table += engine.bam_sweep(d_stream, d_off, has_seq, ref_sel, o.map_qual, o.clip_percent, o.iden_percent, self.digits, d_win, d_win0)
+        except GciError as e:
+            if e.rec < 0:
+                raise
+            raise _file_record_error(engine, e, "gci_bam_sweep", rec_idx_base) from None
+
+
+def bam_filter_sweep(engine: Engine, bam_files: Sequence[str], chrs: Sequence[str], opts: Optional[FateOpts], threads: int, digits: int = 3,
+                     regions: Optional[Sequence[Tuple[str, int, int]]] = None) -> FilterSweep:
+    """Per file of `bam_files` the distribution of MAPQ, clip quotient and identity quotient over its primary records (those
+    bam_filter_depth puts into mapq, clip, identity or kept), `digits` decimal digits a quotient, weighted by records and by covered
+    bases, and beside both what passes the other two tests at `opts`' thresholds (include/gci_hip.h: gci_bam_sweep).  regions (BED
+    rows; None: every primary record): only the records whose reference span overlaps one.  Contigs and @SQ check are
+    bam_filter_depth's.  A malformed record raises GciError with .path and the record's index in the file; a record GCI.py would raise on
+    (no NM tag, a zero denominator) is counted on an `undefined` row."""
+    opts = opts or FateOpts()
+    rows = _lib.SweepRows(int(digits))                     # (digits outside 1 .. 3: ValueError)
+    first = same_sq_table(bam_files)
+    targets_length = _targets_of(first, list(chrs))
+    targets = list(targets_length.keys())
+    if not targets:
+        raise ValueError("no contig selected")
+    engine.set_layout([targets_length[t] for t in targets])
+    windows = None if regions is None else merge_windows(regions, targets_length)
+    visitor = _SweepVisitor(engine, opts, rows.digits, windows)
+    tables = []
+    for path in bam_files:
+        visitor.begin_file()
+        try:
+            with phases.wall("bam_sweep[%s]" % os.path.basename(path)):
+                bam_join_input(engine, path, targets, visitor, threads)
+        except GciError as e:
+            e.path = path                                 # (which file the record index counts in: the command line says so)
+            raise
+        tables.append(visitor.table.copy())
+    return FilterSweep(list(bam_files), tables, rows.digits)
+
+
+def sweep_value(rows, row: int) -> str:
+    """The `value` column of row `row` of a sweep table: the MAPQ, the quotient 0.000 .. 1.000 rendered from the integer row, or the
+    name of a special row."""
+    if row < rows.clip0:
+        return str(row)
+    if row in (rows.clip_undef, rows.iden_undef):
+        return "undefined"
+    if row == rows.iden_below:
+        return "<0"
+    if row == rows.iden_above:
+        return ">1"
+    b = row - (rows.clip0 if row < rows.clip_undef else rows.iden0)
+    return "%d.%0*d" % (b // rows.bins, rows.digits, b % rows.bins)
+
+
+def sweep_text(table: np.ndarray, digits: int) -> str:
+    """The three tables `#mapq`, `#clip`, `#identity` of one file as filter_sweep.py writes them: every row, in table order, with the
+    columns SWEEP_COLUMNS.  kept_at / kept_bases_at: what would be `kept` if this one threshold were set to the row's value while the
+    other two stay -- the sum of the _others columns over the rows that pass then (mapq: rows >= v; clip: numeric rows <= v; identity:
+    numeric rows >= v, plus `>1`); `-` on the special rows."""
+    rows = _lib.SweepRows(digits)
+    t = [[int(x) for x in r] for r in np.asarray(table).tolist()]
+    kept = {}                                             # row -> (records, bases)
+    acc = [0, 0]
+    for r in range(rows.clip0 - 1, -1, -1):               # mapq: from 255 down
+        acc = [acc[0] + t[r][2], acc[1] + t[r][3]]
+        kept[r] = tuple(acc)
+    acc = [0, 0]
+    for r in range(rows.clip0, rows.clip_undef):          # clip: from 0 up
+        acc = [acc[0] + t[r][2], acc[1] + t[r][3]]
+        kept[r] = tuple(acc)
+    acc = [t[rows.iden_above][2], t[rows.iden_above][3]]
+    for r in range(rows.iden_above - 1, rows.iden0 - 1, -1):      # identity: from 1 down, behind `>1`
+        acc = [acc[0] + t[r][2], acc[1] + t[r][3]]
+        kept[r] = tuple(acc)
+    out = []
+    for name, a, b in (("mapq", 0, rows.clip0), ("clip", rows.clip0, rows.iden_below), ("identity", rows.iden_below, rows.rows)):
+        out.append("#%s\n%s\n" % (name, "\t".join(SWEEP_COLUMNS)))
+        for r in range(a, b):
+            k = kept.get(r, ("-", "-"))
+            out.append("\t".join([sweep_value(rows, r)] + [str(x) for x in t[r]] + [str(k[0]), str(k[1])]) + "\n")
+    return "".join(out)
+
+
+# ==============================================================================================
 # contig-sharded run (one process per GPU; SURVEY.md section 8e)
 # ==============================================================================================
 

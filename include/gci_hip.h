@@ -23,6 +23,7 @@
  *   gci_bam_fate, gci_bam_cover_size_sel   filter_depth.py: which test of read_sam drops a record (GCI.py:152-168), and the depth of every such class
  *   gci_name_join_fate, gci_fate_refine    filter_depth.py --join: what the cross-file join (GCI.py:272-301) does with every record, and why
  *   gci_bam_reads_size, gci_bam_reads_write   filter_reads.py: the records over a set of regions as rows of text, each with its class (no counterpart in the reference)
+ *   gci_bam_sweep                          filter_sweep.py: the distribution of MAPQ, clip and identity over the primary records, and what every value of each threshold would keep (no counterpart in the reference)
  *   gci_paf_filter_device   filter(), PAF path        GCI.py:211-254  (+ helpers 49-61, 64-96)
  *
  * Conventions
@@ -417,6 +418,51 @@ int gci_bam_reads_size(gci_ctx* ctx, const uint8_t* d_stream, uint64_t n_bytes, 
 int gci_bam_reads_write(gci_ctx* ctx, const uint8_t* d_stream, uint64_t n_bytes, const uint64_t* d_rec_off, uint32_t n_rec,
                         const uint8_t* d_contig_names, const uint64_t* h_contig_name_off, const uint32_t* h_contig_name_len, uint8_t* d_out,
                         uint64_t cap);
+
+/* ---- filter_sweep.py: how the record filter's three thresholds cut a BAM stream (k_sweep.hip) ----
+ * The same input as gci_bam_fate, plus the windows of gci_bam_reads_size.  Every PRIMARY record is counted once in each of three
+ * tables, by its MAPQ, its clip quotient and its identity quotient, so that what each threshold TAKEN ALONE would keep can be read
+ * off for every value of it.  A record is primary when gci_bam_fate would not call it none, secondary or supplementary: flag & 0x904
+ * clear, refID in 0 .. n_ref - 1, pos >= 0, d_ref_sel[refID] >= 0.  MAPQ settles nothing here: the first NM tag and the CIGAR are read
+ * for every primary record (the record's own, or the CG:B,I / B,i array behind a <l_seq>S<n>N placeholder: the rule of gci_bam_filter).
+ *   windows    as for gci_bam_reads_size (d_contig_win0 == NULL: no window test).  A primary record counts only if it overlaps a
+ *              window of its contig: pos < E and pos + max(R, 1) > B, R the bases under M, D, N, = and X.  With windows the call needs
+ *              gci_layout_set (the selected contigs, n_sel of them, index d_contig_win0); a record whose d_ref_sel[refID] >= n_sel has
+ *              no window.  Without windows no layout is needed.
+ *   totals     S, M (the bases under M, = and X together), I, D, N: summed in 64 bits, every one below 2^57.  NM: the first NM tag.
+ *   weights    every row carries `records` (1 per record) and `bases` (M per record).
+ *   digits     K in 1 .. 3 (else GCI_E_INVALID), B = 10^K = GCI_SWEEP_BINS(K).
+ *   mapq       row = the MAPQ byte.
+ *   clip       S / (M + I + S), ROUNDED UP to K digits: row b in 0 .. B holds the quotients in ((b - 1) / B, b / B], so that
+ *              "clip <= b / B" is "row <= b"; `undefined` when the denominator is 0.
+ *   identity   (M + I + D - NM) / (M + I + D), TRUNCATED to K digits: row b in 0 .. B holds [b / B, (b + 1) / B), so that
+ *              "identity >= b / B" is "row >= b"; `<0` for a negative numerator, `>1` for one beyond the denominator (a negative NM);
+ *              `undefined` without an NM tag, with one of a non-integer type, or with a zero denominator.
+ *              The K digits come from long division in 64-bit integers (a remainder times ten fits); "rounded up" is the truncation
+ *              plus one when a remainder is left.  No floating point takes part in the binning.
+ *   flags      at the call's thresholds, each on its own (no short circuit): pm = mapq >= map_qual; pc = the filter's clip test,
+ *              pi = its identity test (the IEEE f64 quotients of gci_bam_filter); an undefined quantity fails its test.
+ *   h_table    host, GCI_SWEEP_ROWS(K) rows of GCI_SWEEP_COLS uint64 -- records, bases, records_others, bases_others -- where the
+ *              `_others` columns count the row's records that pass the OTHER TWO tests.  Rows: 256 of mapq; clip 0 .. B, undefined;
+ *              identity <0, 0 .. B, >1, undefined (the macros below).
+ *   *d_status  (smallest record index << 8 | -status, UINT64_MAX if none): GCI_E_MALFORMED for a record that runs past the end of the
+ *              stream or contradicts its block_size (not counted), and for operation codes 9 - 15 in a counted record (they add to no
+ *              total; the record is counted).  Nothing else: a record GCI.py would raise on (no NM, a zero denominator) is counted on
+ *              its `undefined` row.
+ * Synchronises.  GCI_SWEEP_GRID=<n> in the environment (read by gci_ctx_create) caps the workgroups of the binning kernel: testing. */
+#define GCI_SWEEP_COLS 4
+#define GCI_SWEEP_BINS(digits) ((digits) == 1 ? 10 : (digits) == 2 ? 100 : 1000)
+#define GCI_SWEEP_MAPQ(q) (q)                                                     /* q in 0 .. 255 */
+#define GCI_SWEEP_CLIP(digits, b) (256 + (b))                                     /* b in 0 .. B */
+#define GCI_SWEEP_CLIP_UNDEF(digits) (256 + GCI_SWEEP_BINS(digits) + 1)
+#define GCI_SWEEP_IDEN_BELOW(digits) (256 + GCI_SWEEP_BINS(digits) + 2)           /* <0 */
+#define GCI_SWEEP_IDEN(digits, b) (256 + GCI_SWEEP_BINS(digits) + 3 + (b))        /* b in 0 .. B */
+#define GCI_SWEEP_IDEN_ABOVE(digits) (256 + 2 * GCI_SWEEP_BINS(digits) + 4)       /* >1 */
+#define GCI_SWEEP_IDEN_UNDEF(digits) (256 + 2 * GCI_SWEEP_BINS(digits) + 5)
+#define GCI_SWEEP_ROWS(digits) (256 + 2 * GCI_SWEEP_BINS(digits) + 6)
+int gci_bam_sweep(gci_ctx* ctx, const uint8_t* d_stream, uint64_t n_bytes, const uint64_t* d_rec_off, uint32_t n_rec, int has_seq,
+                  const int32_t* d_ref_sel, int32_t n_ref, const gci_window* d_win, const uint32_t* d_contig_win0, int map_qual,
+                  double clip_percent, double iden_percent, int digits, uint64_t* h_table, uint64_t* d_status);
 
 /* Cross-rank name check for contig-sharded runs (exact).  gci_hash_bucket sorts the 64-bit name hashes of the
  * passing records into n_parts buckets by (hash >> 33) % n_parts; a bucket is part_cap + 1 uint64 words:
