@@ -58,6 +58,21 @@ struct gci_ctx {
     bool reads_valid = false;
     const void* reads_stream = nullptr;
     const void* reads_off = nullptr;
+    // clip_sites.py: the events the last gci_bam_clip_size found (left, then right, each in record order) and the sites the last
+    // gci_clip_sites_size found, with what each call measured
+    std::vector<gci_ivl> clip_left, clip_right;
+    uint64_t clip_status = ~0ull;
+    bool clip_valid = false;
+    uint32_t clip_n_rec = 0;
+    const void* clip_stream = nullptr;
+    const void* clip_off = nullptr;
+    std::vector<gci_clip_site> sites;
+    bool sites_valid = false;
+    const void* sites_left = nullptr;
+    const void* sites_right = nullptr;
+    const void* sites_depth = nullptr;
+    int32_t sites_min_reads = 0;
+    uint32_t sites_windows = 0;
 };
 
 namespace {
@@ -690,6 +705,7 @@ int gci_layout_set(gci_ctx* ctx, int32_t n_contigs, const int64_t* h_lengths)
     ctx->total = at > 0 ? at : GCI_TILE;
     ctx->n_contigs = n_contigs;
     ctx->bg_track = nullptr; ctx->bg_text_run0 = nullptr;
+    ctx->clip_valid = false; ctx->sites_valid = false;
     return GCI_OK;
 }
 int64_t gci_layout_total(gci_ctx* ctx) { return ctx ? ctx->total : 0; }
@@ -1060,6 +1076,152 @@ int gci_bam_cover_write(gci_ctx* ctx, const uint8_t* bam, uint64_t, const uint64
         }
     });
     *status = ctx->cover_status;
+    return GCI_OK;
+}
+
+/* ---- clip_sites.py: where alignments break off (k_clips.hip's twins, from the text of include/gci_hip.h: a record, an element at a time) ---- */
+int gci_bam_clip_size(gci_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, const uint64_t* rec_off, uint32_t n_rec, int has_seq, const int32_t* ref_sel,
+                      int32_t n_ref, uint32_t excl_flags, int min_mapq, int min_clip, uint64_t* h_counts, uint64_t* status)
+{
+    if (!ctx || !h_counts || !status || n_ref < 0 || min_clip < 1 || (n_rec && (!bam || !rec_off || !ref_sel))) return GCI_E_INVALID;
+    const int lst = need_layout(ctx);
+    if (lst) return lst;
+    ctx->clip_valid = false;
+    ctx->clip_left.clear(); ctx->clip_right.clear();
+    uint64_t st = ~0ull, counted = 0;
+    auto is_clip = [](uint32_t w) { return (w & 0xFu) == 4u || (w & 0xFu) == 5u; };       // S, H
+    for (uint32_t i = 0; i < n_rec; i++) {
+        const uint64_t off = rec_off[i];
+        const uint64_t word = ((uint64_t)i << 8) | (uint64_t)(uint8_t)(-GCI_E_MALFORMED);
+        if (off > n_bytes || n_bytes - off < 36) { st = std::min(st, word); continue; }
+        const uint8_t* p = bam + off;
+        const int32_t block_size = (int32_t)rd32(p), ref_id = (int32_t)rd32(p + 4), pos = (int32_t)rd32(p + 8);
+        const uint32_t l_read_name = p[12], n_cigar = rd16(p + 16), flag = rd16(p + 18);
+        const int mapq = p[13];
+        const int32_t l_seq = (int32_t)rd32(p + 20);
+        const uint64_t rec_end = off + 4 + (uint64_t)(uint32_t)block_size;
+        const uint64_t cig_off = off + 36 + l_read_name;
+        const uint64_t aux_off = cig_off + 4ull * n_cigar + (has_seq ? (((uint64_t)(uint32_t)l_seq + 1) >> 1) + (uint64_t)(uint32_t)l_seq : 0ull);
+        if (block_size < 32 || rec_end > n_bytes || l_seq < 0 || aux_off > rec_end) { st = std::min(st, word); continue; }
+        if ((flag & excl_flags) || mapq < min_mapq || ref_id < 0 || ref_id >= n_ref || pos < 0 || ref_sel[ref_id] < 0) continue;      // skipped
+        // the operations: the record's own, or the first CG:B,I / B,i array behind <l_seq>S (none usable: R counts as 0)
+        const uint8_t* ops = bam + cig_off;
+        uint64_t n = n_cigar;
+        if (n > 0 && (rd32(ops) & 0xFu) == 4u && (rd32(ops) >> 4) == (uint32_t)l_seq) {
+            n = 0;
+            const uint8_t* end = bam + rec_end;
+            for (const uint8_t* q = bam + aux_off; q + 3 <= end;) {
+                const int64_t sz = aux_value_size(q + 3, end, q[2]);
+                if (sz < 0 || q + 3 + sz > end) break;
+                if (q[0] == 'C' && q[1] == 'G') {
+                    if (q[2] == 'B' && (q[3] == 'I' || q[3] == 'i')) {
+                        const uint32_t cg_len = rd32(q + 4);
+                        if (cg_len >= n_cigar && cg_len < (1u << 29)) { ops = q + 8; n = cg_len; }
+                    }
+                    break;
+                }
+                q += 3 + sz;
+            }
+        }
+        uint64_t R = 0;
+        bool bad = false;
+        for (uint64_t k = 0; k < n; k++) {
+            const uint32_t w = rd32(ops + 4 * k), op = w & 0xFu;
+            if (op >= 9u) bad = true;
+            else if (op == 0u || op == 2u || op == 3u || op == 7u || op == 8u) R += w >> 4;       // M D N = X
+        }
+        if (R == 0) continue;                                               // skipped as well
+        counted++;
+        if (bad) st = std::min(st, word);
+        uint64_t lead = 0, trail = 0;
+        if (is_clip(rd32(ops))) {
+            lead = rd32(ops) >> 4;
+            if (n > 1 && is_clip(rd32(ops + 4))) lead += rd32(ops + 4) >> 4;
+        }
+        if (is_clip(rd32(ops + 4 * (n - 1)))) {
+            trail = rd32(ops + 4 * (n - 1)) >> 4;
+            if (n > 1 && is_clip(rd32(ops + 4 * (n - 2)))) trail += rd32(ops + 4 * (n - 2)) >> 4;
+        }
+        const int32_t contig = ref_sel[ref_id];
+        const uint64_t L = contig < ctx->n_contigs ? (uint64_t)ctx->len[(size_t)contig] : 0;
+        const uint64_t right = (uint64_t)pos + R - 1;
+        if (lead >= (uint64_t)min_clip && (uint64_t)pos < L) ctx->clip_left.push_back(gci_ivl{contig, pos, pos, 0});
+        if (trail >= (uint64_t)min_clip && right < L) ctx->clip_right.push_back(gci_ivl{contig, (int32_t)right, (int32_t)right, 0});
+    }
+    ctx->clip_status = st;
+    ctx->clip_valid = true; ctx->clip_n_rec = n_rec; ctx->clip_stream = bam; ctx->clip_off = rec_off;
+    h_counts[0] = counted; h_counts[1] = ctx->clip_left.size(); h_counts[2] = ctx->clip_right.size();
+    *status = st;
+    return GCI_OK;
+}
+
+int gci_bam_clip_write(gci_ctx* ctx, const uint8_t* bam, uint64_t, const uint64_t* rec_off, uint32_t n_rec, int, gci_ivl* out, uint64_t cap,
+                       uint64_t* status)
+{
+    if (!ctx || !status || (n_rec && (!bam || !rec_off))) return GCI_E_INVALID;
+    const int lst = need_layout(ctx);
+    if (lst) return lst;
+    if (!ctx->clip_valid || ctx->clip_n_rec != n_rec || bam != ctx->clip_stream || rec_off != ctx->clip_off) return GCI_E_INVALID;
+    const uint64_t total = ctx->clip_left.size() + ctx->clip_right.size();
+    if (total && !out) return GCI_E_INVALID;
+    if (cap < total) return GCI_E_CAPACITY;
+    std::copy(ctx->clip_left.begin(), ctx->clip_left.end(), out);
+    std::copy(ctx->clip_right.begin(), ctx->clip_right.end(), out + ctx->clip_left.size());
+    *status = ctx->clip_status;
+    return GCI_OK;
+}
+
+int gci_clip_sites_size(gci_ctx* ctx, const int32_t* left, const int32_t* right, const int32_t* depth, int32_t min_reads,
+                        const gci_window* h_windows, uint32_t n_windows, uint64_t* h_n_sites)
+{
+    if (!ctx || !left || !right || !h_n_sites || min_reads < 1 || (n_windows && !h_windows)) return GCI_E_INVALID;
+    const int lst = need_layout(ctx);
+    if (lst) return lst;
+    if ((((uintptr_t)left) | ((uintptr_t)right) | ((uintptr_t)depth)) & 15u) return GCI_E_INVALID;
+    ctx->sites_valid = false;
+    *h_n_sites = 0;
+    std::vector<gci_window> ws;
+    if (n_windows == 0) {
+        for (int32_t c = 0; c < ctx->n_contigs; c++) ws.push_back(gci_window{ctx->off[(size_t)c], ctx->off[(size_t)c] + ctx->len[(size_t)c]});
+    } else {
+        int64_t at = 0;
+        for (uint32_t i = 0; i < n_windows; i++) {
+            gci_window w = h_windows[i];
+            w.begin = std::max<int64_t>(w.begin, 0);
+            w.end = std::max(std::min(w.end, ctx->total), w.begin);
+            if (w.begin < at) return GCI_E_INVALID;                        // not sorted and disjoint
+            at = w.end;
+            ws.push_back(w);
+        }
+    }
+    ctx->sites.clear();
+    for (const gci_window& w : ws) {
+        for (int64_t p = w.begin; p < w.end; p++) {
+            if (left[p] < min_reads && right[p] < min_reads) continue;
+            const int32_t c = (int32_t)(std::upper_bound(ctx->off.begin(), ctx->off.end(), p) - ctx->off.begin()) - 1;
+            const int64_t pos = p - ctx->off[(size_t)c];
+            if (pos >= ctx->len[(size_t)c]) continue;                       // padding
+            ctx->sites.push_back(gci_clip_site{c, (int32_t)pos, left[p], right[p], depth ? depth[p] : 0, 0});
+        }
+    }
+    ctx->sites_valid = true; ctx->sites_left = left; ctx->sites_right = right; ctx->sites_depth = depth;
+    ctx->sites_min_reads = min_reads; ctx->sites_windows = n_windows;
+    *h_n_sites = ctx->sites.size();
+    return GCI_OK;
+}
+
+int gci_clip_sites_write(gci_ctx* ctx, const int32_t* left, const int32_t* right, const int32_t* depth, int32_t min_reads,
+                         const gci_window* h_windows, uint32_t n_windows, gci_clip_site* out, uint64_t cap)
+{
+    if (!ctx || !left || !right || min_reads < 1 || (n_windows && !h_windows)) return GCI_E_INVALID;
+    const int lst = need_layout(ctx);
+    if (lst) return lst;
+    if (!ctx->sites_valid || left != ctx->sites_left || right != ctx->sites_right || depth != ctx->sites_depth || min_reads != ctx->sites_min_reads ||
+        n_windows != ctx->sites_windows)
+        return GCI_E_INVALID;
+    if (!ctx->sites.empty() && !out) return GCI_E_INVALID;
+    if (cap < ctx->sites.size()) return GCI_E_CAPACITY;
+    std::copy(ctx->sites.begin(), ctx->sites.end(), out);
     return GCI_OK;
 }
 

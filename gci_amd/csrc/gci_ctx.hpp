@@ -149,6 +149,20 @@ struct gci_ctx {
     std::vector<uint32_t> reads_name_len;   // ... and the contig name lengths its rows were measured with
     DevBuf sweep_rec, sweep_chunk;          // k_sweep.hip: per record (parse, NM, window, chunk counts and their scan) + the table, and per chunk (base sums)
     uint32_t sweep_grid_cap = 0;            // GCI_SWEEP_GRID=<n>: at most n workgroups for k_sweep_bin (testing; 0: what the device holds)
+    // k_clips.hip: what gci_bam_clip_size keeps for gci_bam_clip_write -- per record (parse, end clips, events, ranks, right site) and
+    // per chunk (base sums) --, and what gci_clip_sites_size keeps for gci_clip_sites_write -- per window tile its sites and their scan
+    DevBuf clip_rec, clip_chunk, clip_tiles;
+    bool clip_valid = false;
+    uint32_t clip_n_rec = 0;
+    uint64_t clip_n_left = 0, clip_n_right = 0;
+    const void* clip_stream = nullptr;
+    const void* clip_off = nullptr;
+    uint64_t clip_sites_epoch = 0, clip_sites_total = 0;      // (epoch 0: no size call yet)
+    const void* clip_sites_left = nullptr;
+    const void* clip_sites_right = nullptr;
+    const void* clip_sites_depth = nullptr;
+    int32_t clip_sites_min_reads = 0;
+    uint32_t clip_sites_windows = 0;
     void* h_pinned = nullptr;               // staging for small uploads
     size_t h_pinned_cap = 0;
     // optional per-kernel HIP-event timing (gci_profile_*)

@@ -25,6 +25,7 @@ REC_DTYPE = np.dtype([("name_hash", "<u8"), ("contig", "<i4"), ("start", "<i4"),
 assert REC_DTYPE.itemsize == 32
 IVL_DTYPE = np.dtype([("contig", "<i4"), ("start", "<i4"), ("end", "<i4"), ("pad", "<i4")])
 RUN_DTYPE = np.dtype([("start", "<u4"), ("depth", "<i4")])          # gci_depth_run
+SITE_DTYPE = np.dtype([("contig", "<i4"), ("pos", "<i4"), ("left", "<i4"), ("right", "<i4"), ("depth", "<i4"), ("pad", "<i4")])      # gci_clip_site
 
 _M64 = (1 << 64) - 1
 Buffer = Any                  # a device buffer of the engine's provider: hbm.Buf or Buffer
@@ -418,6 +419,43 @@ class Engine:
         if check:
             self._raise_status(self._status.item(), "gci_bam_sweep", rec_idx_base)
         return table
+
+    # ---- clip_sites.py: where alignments break off (include/gci_hip.h: gci_bam_clip_*, gci_clip_sites_*; k_clips.hip) ----
+    def bam_clip(self, d_stream: Buffer, d_rec_off: Buffer, has_seq: bool, d_ref_sel: Buffer, excl_flags: int = 0x704, min_mapq: int = 0,
+                 min_clip: int = 100, check: bool = True, rec_idx_base: int = 0) -> Tuple[Buffer, Buffer, List[int]]:
+        """-> (the left events, the right events, [records counted, left events, right events]): per counted record of an inflated BAM
+        stream (has_seq) or a heads stream one interval int32 [n, 4] (contig, site, site, 0) where its alignment begins / ends with a clip
+        of at least min_clip bases beyond it, each half in record order, for depth_build with flank 0.  Needs the layout of the selected
+        contigs."""
+        n = int(d_rec_off.shape[0])
+        counts = (ctypes.c_uint64 * 3)()
+        self._chk(self.lib.gci_bam_clip_size(self.ctx, self._p(d_stream), int(d_stream.shape[0]), self._p(d_rec_off), n, int(has_seq),
+                                             self._p(d_ref_sel), int(d_ref_sel.shape[0]), int(excl_flags), int(min_mapq), int(min_clip), counts,
+                                             self._p(self._status)), "gci_bam_clip_size")
+        if check:
+            self._raise_status(self._status.item(), "gci_bam_clip_size", rec_idx_base)
+        n_left, n_right = int(counts[1]), int(counts[2])
+        out = self.T.empty((max(n_left + n_right, 1), 4), self.T.int32, self.device)
+        self._chk(self.lib.gci_bam_clip_write(self.ctx, self._p(d_stream), int(d_stream.shape[0]), self._p(d_rec_off), n, int(has_seq),
+                                              self._p(out), n_left + n_right, self._p(self._status)), "gci_bam_clip_write")
+        return out[:n_left], out[n_left:n_left + n_right], [int(c) for c in counts]
+
+    def clip_sites(self, left: Buffer, right: Buffer, depth: Optional[Buffer], min_reads: int,
+                   windows: Sequence[Tuple[int, int]] = ()) -> np.ndarray:
+        """-> SITE_DTYPE [n]: the elements of the tracks `left` / `right` with left >= min_reads or right >= min_reads inside the sorted,
+        disjoint [begin, end) windows of track elements (none: every contig), in ascending order, with the depth there (0 without a depth
+        track)."""
+        nw = len(windows)
+        arr = self._window_array(windows)
+        n = ctypes.c_uint64(0)
+        head = (self.ctx, self._p(left), self._p(right), self._p(depth), int(min_reads), arr, nw)
+        self._chk(self.lib.gci_clip_sites_size(*head, ctypes.byref(n)), "gci_clip_sites_size")
+        total = int(n.value)
+        if total == 0:
+            return np.zeros(0, dtype=SITE_DTYPE)
+        out = self.T.empty((total, 6), self.T.int32, self.device)
+        self._chk(self.lib.gci_clip_sites_write(*head, self._p(out), total), "gci_clip_sites_write")
+        return np.ascontiguousarray(out.cpu().numpy()).view(SITE_DTYPE).reshape(-1)[:total]
 
     def track_add(self, acc: Buffer, add: Buffer) -> Buffer:
         """acc += add over the layout."""

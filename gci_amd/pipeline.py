@@ -29,7 +29,7 @@ from typing import Dict, List, Optional, Sequence, Set, Tuple
 import numpy as np
 
 from . import hbm, hostio, phases, score
-from .device import Buffer, Engine, JoinInput, REC_DTYPE, name_hash_np
+from .device import Buffer, Engine, JoinInput, REC_DTYPE, SITE_DTYPE, name_hash_np
 from . import _lib
 from ._lib import GciError, REC_HQ, REC_PASS
 from .formats import bam as bamfmt
@@ -1322,6 +1322,150 @@ def bam_raw_depth(engine: Engine, bam_files: Sequence[str], chrs: Sequence[str] 
     depths = DepthTracks(engine, targets_length, total)
     depths.cover_flushes = visitor.flushes
     return depths
+
+
+# ==============================================================================================
+# clip_sites.py: where alignments break off, base by base
+# ==============================================================================================
+
+CLIP_MIN_CLIP = 100                        # a choice for long reads, not a measurement
+CLIP_MIN_READS = 3
+_CLIP_TRACKS = ("left", "right", "depth")
+
+
+class ClipSites:
+    """What bam_clip_sites returns: left / right / depth = the three DepthTracks (per base the records whose alignment begins / ends
+    there with a clip beyond it; the read-mapping depth), sites = device.SITE_DTYPE [n] in contig order and then by position, counts[k]
+    = [records counted, left events, right events] of file k, flushes = how often intervals were built into a track before their file
+    was through."""
+
+    def __init__(self, left: DepthTracks, right: DepthTracks, depth: DepthTracks, sites: np.ndarray, counts: List[List[int]], flushes: int):
+        self.left, self.right, self.depth, self.sites, self.counts, self.flushes = left, right, depth, sites, counts, flushes
+
+
+class _ClipVisitor(StreamVisitor):
+    """_CoverVisitor with two more tracks: every piece goes through gci_bam_cover_* (the depth) and gci_bam_clip_* (the left and the
+    right events), so a file is read once; three _IntervalCollectors with the flush and hand-over rules of _CoverVisitor."""
+
+    def __init__(self, main: Engine, opts: CoverOpts, min_clip: int, budget: int):
+        self.main, self.opts, self.min_clip, self.budget = main, opts, int(min_clip), max(int(budget), 1)
+        self.collectors = {name: _IntervalCollector() for name in _CLIP_TRACKS}
+        self.counts = [0, 0, 0]
+
+    flushes = property(lambda self: sum(c.flushes for c in self.collectors.values()))
+
+    def begin_file(self) -> None:
+        for c in self.collectors.values():
+            c.reset()
+        self.counts = [0, 0, 0]
+
+    abort_file = begin_file
+
+    def visit(self, engine, d_stream, d_off, has_seq, ref_sel, rec_idx_base) -> None:
+        if engine.lengths != self.main.lengths:            # (the walk engine: a context of its own)
+            engine.set_layout(self.main.lengths)
+        try:
+            with phases.gpu("record cover"):
+                ivl = engine.bam_cover(d_stream, d_off, has_seq, ref_sel, self.opts.excl, self.opts.min_mapq, self.opts.count_del)
+        except GciError as e:
+            if e.rec < 0:
+                raise
+            raise _file_record_error(engine, e, "gci_bam_cover_size", rec_idx_base) from None
+        try:
+            with phases.gpu("record clips"):
+                left, right, counts = engine.bam_clip(d_stream, d_off, has_seq, ref_sel, self.opts.excl, self.opts.min_mapq, self.min_clip)
+        except GciError as e:
+            if e.rec < 0:
+                raise
+            raise _file_record_error(engine, e, "gci_bam_clip_size", rec_idx_base) from None
+        self.counts = [a + b for a, b in zip(self.counts, counts)]
+        for name, part in zip(_CLIP_TRACKS, (left, right, ivl)):
+            c = self.collectors[name]
+            c.add(part)
+            if c.n_ivl > self.budget:
+                c.flush(engine)
+            if engine is not self.main:                    # (made in that engine's stream order, used in the caller's from file_done on)
+                c.hand_over(self.main.stream)
+
+    def file_done(self) -> Dict[str, Buffer]:
+        """The file's three tracks (the caller's engine and stream)."""
+        return {name: self.collectors[name].finish(self.main) for name in _CLIP_TRACKS}
+
+
+def bam_clip_sites(engine: Engine, bam_files: Sequence[str], chrs: Sequence[str] = (), cover_opts: Optional[CoverOpts] = None, threads: int = 1,
+                   min_clip: int = CLIP_MIN_CLIP, min_reads: int = CLIP_MIN_READS, regions: Optional[Sequence[Tuple[str, int, int]]] = None,
+                   ivl_budget: Optional[int] = None) -> ClipSites:
+    """Where the alignments of `bam_files` break off (include/gci_hip.h: gci_bam_clip_size, gci_clip_sites_size): per base the counted
+    records whose alignment begins (left) or ends (right) there with a clip of at least `min_clip` bases beyond it, the read-mapping
+    depth as bam_raw_depth counts it with the same options, and the bases where left or right reaches `min_reads`.  Several files add;
+    the contigs are the first file's (restricted by `chrs`), a file with another @SQ table raises SqMismatch.  regions: only the sites
+    inside these (contig, start, end) rows are listed (merge_windows' rules); the tracks are whole.
+    Raises TracksDoNotFit before anything is read when the tracks of the run are more than the device has free."""
+    opts = cover_opts or CoverOpts()
+    if int(min_clip) < 1 or int(min_reads) < 1:
+        raise ValueError("min_clip and min_reads are at least 1")
+    first = same_sq_table(bam_files)
+    targets_length = _targets_of(first, list(chrs))
+    targets = list(targets_length.keys())
+    if not targets:
+        raise ValueError("no contig selected")
+    engine.set_layout([targets_length[t] for t in targets])
+    # three tracks, one more while intervals are built in parts -- and with several files a second set, the file's next to the sum of
+    # the files before it
+    n_tracks = 3 * (2 if len(bam_files) > 1 else 1) + 1
+    track_bytes, free = 4 * int(engine.total), device_memory_free(engine)
+    if n_tracks * track_bytes > free:
+        raise TracksDoNotFit(n_tracks, track_bytes, free)
+    visitor = _ClipVisitor(engine, opts, min_clip, COVER_IVL_BUDGET if ivl_budget is None else ivl_budget)
+    totals: Dict[str, Buffer] = {}
+    counts = []
+    for path in bam_files:
+        visitor.begin_file()
+        try:
+            with phases.wall("bam_clip[%s]" % os.path.basename(path)):
+                bam_join_input(engine, path, targets, visitor, threads)
+        except BaseException as e:
+            visitor.abort_file()
+            if isinstance(e, GciError):
+                e.path = path                             # (which file the record index counts in: the command line says so)
+            raise
+        counts.append(list(visitor.counts))
+        for name, track in visitor.file_done().items():
+            if name in totals:
+                engine.track_add(totals[name], track)
+            else:
+                totals[name] = track
+    windows: List[Tuple[int, int]] = []
+    if regions is not None:
+        win, win0 = merge_windows(regions, targets_length)
+        for c in range(len(targets)):
+            o = int(engine.offsets[c])
+            windows += [(o + int(a), o + int(b)) for a, b in win[int(win0[c]):int(win0[c + 1])].tolist()]
+    with phases.gpu("clip sites"):
+        if regions is not None and not windows:
+            sites = np.zeros(0, dtype=SITE_DTYPE)
+        else:
+            sites = engine.clip_sites(totals["left"], totals["right"], totals["depth"], int(min_reads), windows)
+    tracks = {name: DepthTracks(engine, targets_length, totals[name]) for name in _CLIP_TRACKS}
+    return ClipSites(tracks["left"], tracks["right"], tracks["depth"], sites, counts, visitor.flushes)
+
+
+def clip_sites_bed(sites: np.ndarray, targets: Sequence[str]) -> str:
+    """`contig\\tpos\\tpos+1\\tleft\\tright\\tdepth\\n` per site, no header line: a BED file bedgraph_cli.parse_regions reads."""
+    return "".join("%s\t%d\t%d\t%d\t%d\t%d\n" % (targets[c], p, p + 1, l, r, d)
+                   for c, p, l, r, d in zip(sites["contig"].tolist(), sites["pos"].tolist(), sites["left"].tolist(), sites["right"].tolist(),
+                                            sites["depth"].tolist()))
+
+
+def clip_summary_text(bam_files: Sequence[str], counts: Sequence[Sequence[int]], n_sites: int, options: Sequence[Tuple[str, object]]) -> str:
+    """The text of {PREFIX}.clip.txt: per file and in total the records counted, the left and the right events; the sites; the options."""
+    lines = ["#file\trecords\tleft_events\tright_events\tpath"]
+    for k, (path, row) in enumerate(zip(bam_files, counts), 1):
+        lines.append("%d\t%d\t%d\t%d\t%s" % (k, row[0], row[1], row[2], path))
+    lines.append("total\t%d\t%d\t%d\t." % tuple(sum(int(row[j]) for row in counts) for j in range(3)))
+    lines.append("sites\t%d" % n_sites)
+    lines += ["%s\t%s" % (name, value) for name, value in options]
+    return "\n".join(lines) + "\n"
 
 
 # ==============================================================================================

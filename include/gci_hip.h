@@ -464,6 +464,59 @@ int gci_bam_sweep(gci_ctx* ctx, const uint8_t* d_stream, uint64_t n_bytes, const
                   const int32_t* d_ref_sel, int32_t n_ref, const gci_window* d_win, const uint32_t* d_contig_win0, int map_qual,
                   double clip_percent, double iden_percent, int digits, uint64_t* h_table, uint64_t* d_status);
 
+/* ---- clip_sites.py: where alignments break off, base by base (k_clips.hip) -------------------------------------------------------------
+ * gci_bam_clip_size / _write: the same input as gci_bam_cover_size (the inflated stream plus record offsets, or a heads stream with
+ * has_seq = 0); they need gci_layout_set.  Per record:
+ *   skipped    exactly the skip rule of gci_bam_cover_size with the same excl_flags (0x704 by default: supplementary alignments count) and
+ *              min_mapq; its CIGAR is not read.  A record whose R (below) is 0 is skipped as well.
+ *   operations the record's own, or the CG:B,I / B,i array behind a <l_seq>S<n>N placeholder (the rule of gci_bam_filter: the first
+ *              operation is S of length l_seq, the FIRST CG tag counts).  Such a first operation without a usable tag: R counts as 0, the
+ *              record is skipped.
+ *   R          the bases under M, =, X, D and N, summed in 64 bits.
+ *   lead       len(op[0]) if op[0] is S or H, plus len(op[1]) if op[0] and op[1] are both S or H; only the first two operations are looked
+ *              at.  trail: the same over op[n - 1], op[n - 2].  H counts like S (minimap2 writes supplementary alignments with hard
+ *              clips); with R > 0 no operation counts on both sides.
+ *   events     a LEFT event at pos if lead >= min_clip, a RIGHT event at pos + R - 1 if trail >= min_clip.  The site is computed in 64
+ *              bits (pos + R may exceed int32); one at or beyond the contig's length is not emitted and not counted.  min_clip < 1:
+ *              GCI_E_INVALID.
+ *   *d_status  as gci_bam_cover_size reports it (smallest record index << 8 | -status, UINT64_MAX if none): GCI_E_MALFORMED for a
+ *              record that runs past the end of the stream or contradicts its block_size, and for operation codes 9 - 15 in a record
+ *              that is not skipped (they add nothing to R).
+ *   h_counts   host, 3 entries: the records counted (not skipped), the left events, the right events.  The size call synchronises.
+ * gci_bam_clip_write emits gci_ivl{contig, site, site, 0}: the left events to d_out[0 .. n_left), the right events to d_out[n_left ..
+ * n_left + n_right), each in RECORD ORDER (ranks from an exclusive scan; no atomics: the output is deterministic).  cap < n_left +
+ * n_right: GCI_E_CAPACITY, nothing is written.  The size call's scratch stays in the context for it; another stream, offsets or n_rec
+ * than the size call in front of it on this context measured: GCI_E_INVALID.  gci_depth_build with flank 0 over either half gives that
+ * side's track: per base the number of events there.
+ *
+ * gci_clip_sites_size / _write: the elements of two such tracks where left >= min_reads or right >= min_reads, in ascending flat order.
+ *   input      whole tracks of gci_layout_total() elements, 16-byte aligned (else GCI_E_INVALID); d_depth == NULL: the depth column is 0.
+ *   windows    [begin, end) in flat track elements, clamped to the track, sorted and disjoint (else GCI_E_INVALID), as gci_depth_hist
+ *              takes them; n_windows == 0: every contig of the layout.  Only elements inside a window are looked at.
+ *   a site     contig and pos from the layout's contig offsets, left, right and depth the three tracks' values there.  Elements of the
+ *              padding between contigs are never sites.  min_reads < 1: GCI_E_INVALID.
+ *   write      the sites of the size call in front of it on this context (same tracks, min_reads and n_windows, nothing between the two
+ *              that sets windows: else GCI_E_INVALID) to d_out[0 .. *h_n_sites).  cap too small: GCI_E_CAPACITY, nothing is written.
+ * The size pass reads the left and right tracks once, 16 bytes a lane, and leaves one count per 4096-element tile of the windows; the
+ * counts are scanned; the write pass looks only at tiles with a count and stores by rank inside the tile.  No global atomics. */
+typedef struct gci_clip_site {
+    int32_t contig;
+    int32_t pos;
+    int32_t left;
+    int32_t right;
+    int32_t depth;
+    int32_t pad;
+} gci_clip_site;
+int gci_bam_clip_size(gci_ctx* ctx, const uint8_t* d_stream, uint64_t n_bytes, const uint64_t* d_rec_off, uint32_t n_rec, int has_seq,
+                      const int32_t* d_ref_sel, int32_t n_ref, uint32_t excl_flags, int min_mapq, int min_clip, uint64_t* h_counts,
+                      uint64_t* d_status);
+int gci_bam_clip_write(gci_ctx* ctx, const uint8_t* d_stream, uint64_t n_bytes, const uint64_t* d_rec_off, uint32_t n_rec, int has_seq,
+                       gci_ivl* d_out, uint64_t cap, uint64_t* d_status);
+int gci_clip_sites_size(gci_ctx* ctx, const int32_t* d_left, const int32_t* d_right, const int32_t* d_depth, int32_t min_reads,
+                        const gci_window* h_windows, uint32_t n_windows, uint64_t* h_n_sites);
+int gci_clip_sites_write(gci_ctx* ctx, const int32_t* d_left, const int32_t* d_right, const int32_t* d_depth, int32_t min_reads,
+                         const gci_window* h_windows, uint32_t n_windows, gci_clip_site* d_out, uint64_t cap);
+
 /* Cross-rank name check for contig-sharded runs (exact).  gci_hash_bucket sorts the 64-bit name hashes of the
  * passing records into n_parts buckets by (hash >> 33) % n_parts; a bucket is part_cap + 1 uint64 words:
  * [0] = number of hashes the sender had for it (> part_cap: overflow), [1..] = the hashes.  After ONE all-to-all of
