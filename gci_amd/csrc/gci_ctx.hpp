@@ -100,6 +100,7 @@ struct gci_ctx {
     uint64_t pg_blob_off = 0;
     uint64_t pg_blob_bytes = 0;               // total size of the blob the size call measured (without its 16 guard bytes)
     std::vector<DevBuf> paf_pool;           // K2's scratch, in the order a call asks for it (k_paf.hip: PafScratch)
+    uint64_t paf_global_groups = 0;         // tokeniser workgroups of the last PAF call that walked global memory
     DevBuf crc_tabs;                        // k_bgzf_crc: the 32 look-up tables (k_crc_tables), made on first use
     bool crc_tabs_ready = false;            // ... set once k_crc_tables has been launched without an error
     uint32_t inflate_last_n = 0;            // members of the last gci_bgzf_inflate_device call (0: the wave decoder was not used)

@@ -496,10 +496,13 @@ struct PafEmit { uint32_t query; int32_t target; int64_t s, e, qlen; };
 void merge_span(std::vector<std::pair<int64_t, int64_t>>& p, int64_t& covered, int64_t& bs, int64_t& be)
 {
     std::sort(p.begin(), p.end());
-    covered = 0;
-    int64_t best = -1;
-    bs = be = 0;
+    // GCI.py:83-93 holds the first sorted block against itself: one whose end lies before its start does not reach its own start,
+    // is counted, and is taken up again -- it is counted twice.  The longest piece is the maximum over ALL pieces, whatever their
+    // sign (the first one stands until a longer one comes).
     int64_t lo = p[0].first, hi = p[0].second;
+    covered = hi < lo ? hi - lo : 0;
+    int64_t best = hi - lo;
+    bs = lo; be = hi;
     for (size_t i = 1; i <= p.size(); i++) {
         if (i < p.size() && hi >= p[i].first) { hi = std::max(hi, p[i].second); continue; }
         covered += hi - lo;
@@ -508,13 +511,15 @@ void merge_span(std::vector<std::pair<int64_t, int64_t>>& p, int64_t& covered, i
     }
 }
 
-bool is_space(uint8_t c) { return c == ' ' || c == '\t' || c == '\n' || c == '\r' || c == 0x0b || c == 0x0c; }
+// the blanks of int() on an ASCII column (0x09 - 0x0d and ' '), and those of str.strip(), which takes 0x1c - 0x1f as well
+bool is_int_space(uint8_t c) { return c == ' ' || (c >= 0x09 && c <= 0x0d); }
+bool is_space(uint8_t c) { return is_int_space(c) || (c >= 0x1c && c <= 0x1f); }
 
 // Python's int() on a column: optional blanks, optional sign, digits with single underscores between them
 bool parse_int(const uint8_t* a, const uint8_t* b, int64_t& v)
 {
-    while (a < b && is_space(*a)) a++;
-    while (b > a && is_space(b[-1])) b--;
+    while (a < b && is_int_space(*a)) a++;
+    while (b > a && is_int_space(b[-1])) b--;
     bool neg = false;
     if (a < b && (*a == '+' || *a == '-')) { neg = *a == '-'; a++; }
     if (a >= b) return false;

@@ -33,7 +33,9 @@ struct PafTargets {
     uint32_t mask;
 };
 
-__device__ __forceinline__ bool is_space(uint8_t c) { return c == ' ' || c == '\t' || c == '\n' || c == '\r' || c == 0x0b || c == 0x0c; }
+// the blanks of int() on an ASCII column (0x09 - 0x0d and ' '), and those of str.strip(), which takes 0x1c - 0x1f as well
+__device__ __forceinline__ bool is_int_space(uint8_t c) { return c == ' ' || (c >= 0x09 && c <= 0x0d); }
+__device__ __forceinline__ bool is_space(uint8_t c) { return is_int_space(c) || (c >= 0x1c && c <= 0x1f); }
 
 // a line starts at p: the first byte of the file, or behind '\n', or behind a '\r' that is not followed by '\n'
 //
@@ -132,9 +134,9 @@ template <typename Src>
 __device__ __forceinline__ bool parse_int(const Src src, uint64_t a, uint64_t b, int64_t& v)
 {
     Window<Src> text(src, a);
-    while (a < b && is_space(text[a])) a++;
-    if (Src::WIDE) { if (b > a && is_space(src[b - 1])) { do b--; while (b > a && is_space(src[b - 1])); } }
-    else while (b > a && is_space(text[b - 1])) b--;
+    while (a < b && is_int_space(text[a])) a++;
+    if (Src::WIDE) { if (b > a && is_int_space(src[b - 1])) { do b--; while (b > a && is_int_space(src[b - 1])); } }
+    else while (b > a && is_int_space(text[b - 1])) b--;
     bool neg = false;
     if (a < b && (text[a] == '+' || text[a] == '-')) { neg = text[a] == '-'; a++; }
     if (a >= b) return false;
@@ -281,7 +283,8 @@ __device__ __forceinline__ uint32_t paf_line(const Src text, uint64_t a, uint64_
 // One lane per line, one workgroup per BLOCK consecutive lines.  Their bytes are one stretch of the text, [start of the first,
 // start of the line behind the last): the workgroup copies it into LDS with aligned 16-byte loads -- ONE coalesced trip to memory
 // -- and the lanes walk their lines there (round 3 walked ~150 bytes of global memory byte by byte per lane: 165 GB/s).  A
-// stretch that does not fit (lines of kilobytes: cg:Z: tags) is walked in global memory as before.
+// stretch that does not fit (lines of kilobytes: cg:Z: tags) is walked in global memory as before; status[1] counts the workgroups
+// that did (gci_paf_global_groups: which of the two walks ran is otherwise invisible, they give the same hits).
 #define PAF_LDS_BYTES 49152
 __global__ __launch_bounds__(BLOCK) void k_paf_tokenise(const uint8_t* __restrict__ text, uint64_t hi, const uint64_t* __restrict__ starts,
                                                         uint32_t n_lines, uint64_t line_base, PafTargets T, int map_qual, int mq_cutoff,
@@ -309,7 +312,7 @@ __global__ __launch_bounds__(BLOCK) void k_paf_tokenise(const uint8_t* __restric
             *reinterpret_cast<uint4*>(s_text + 16u * v) = x;
         }
         __syncthreads();
-    }
+    } else if (threadIdx.x == 0) atomicAdd(status + 1, 1ull);
     if (i >= n_lines) return;
     PafHitD h;
     uint32_t f;
@@ -373,10 +376,13 @@ __device__ __forceinline__ void merge_span(int64_t* __restrict__ pa, int64_t* __
         while (j > 0 && (pa[j - 1] > xa || (pa[j - 1] == xa && pb[j - 1] > xb))) { pa[j] = pa[j - 1]; pb[j] = pb[j - 1]; j--; }
         pa[j] = xa; pb[j] = xb;
     }
-    covered = 0;
-    int64_t best = -1;
-    bs = be = 0;
+    // GCI.py:83-93 holds the first sorted block against itself: one whose end lies before its start does not reach its own start,
+    // is counted, and is taken up again -- it is counted twice.  The longest piece is the maximum over ALL pieces, whatever their
+    // sign (the first one stands until a longer one comes).
     int64_t lo = pa[0], hi = pb[0];
+    covered = hi < lo ? hi - lo : 0;
+    int64_t best = hi - lo;
+    bs = lo; be = hi;
     for (uint32_t i = 1; i <= n; i++) {
         if (i < n && hi >= pa[i]) { hi = hi > pb[i] ? hi : pb[i]; continue; }
         covered += hi - lo;
@@ -415,12 +421,12 @@ __global__ __launch_bounds__(BLOCK) void k_paf_score(const PafHitD* __restrict__
             // instead of the dependent trips through the scratch lists below.
             const PafHitD x = hits[order[a0]];
             if (x.qlen == 0) atomicMin(status, ((unsigned long long)order[a0] << 8) | (unsigned)(-GCI_E_ZERO_DIV));
-            else if ((x.te - x.ts > -1 && (x.ts > 0x7fffffffLL || x.ts < -0x80000000LL || x.te > 0x7fffffffLL || x.te < -0x80000000LL)) ||
+            else if (x.ts > 0x7fffffffLL || x.ts < -0x80000000LL || x.te > 0x7fffffffLL || x.te < -0x80000000LL ||
                      x.qlen > 0x7fffffffLL || x.qlen < -0x80000000LL || x.qn_len > 0xFFFF)
                 atomicMin(status, ((unsigned long long)table[s] << 8) | (unsigned)(-GCI_E_INVALID));
             else {
-                const bool block = x.te - x.ts > -1;                  // (merge_span's "longest block" starts from length -1)
-                r.name_hash = x.qhash; r.contig = x.t; r.start = block ? (int32_t)x.ts : 0; r.end = block ? (int32_t)x.te : 0;
+                // (the one block is the longest piece whatever its sign, as in merge_span)
+                r.name_hash = x.qhash; r.contig = x.t; r.start = (int32_t)x.ts; r.end = (int32_t)x.te;
                 r.qlen = (int32_t)x.qlen; r.rec_idx = s; r.mapq = 0;
                 r.flags = (uint8_t)(GCI_REC_PASS | ((hq[s] >> 32) ? GCI_REC_HQ : 0)); r.name_len = (uint16_t)x.qn_len;
                 name_off = x.qn_off;
@@ -579,6 +585,10 @@ extern "C" int gci_paf_pool_release(gci_ctx* ctx)
     return GCI_OK;
 }
 
+// How many workgroups of the tokeniser walked global memory in the last gci_paf_filter_device / gci_paf_hits_device of this context
+// (the files and error lines it got to): their 256 lines and the alignment slack did not fit the LDS copy.
+extern "C" uint64_t gci_paf_global_groups(const gci_ctx* ctx) { return ctx ? ctx->paf_global_groups : 0; }
+
 namespace {
 
 #define PAF_ALLOC(var, type, count)                                         \
@@ -635,13 +645,14 @@ struct PafStageA {
     std::vector<uint32_t> hits_upto;
     int n_ok = 0, pending_status = GCI_OK;
     uint64_t pending_line = 0;
+    uint64_t global_groups = 0;              // workgroups of the tokeniser that walked global memory
 };
 
 int paf_stage_a(gci_ctx* ctx, PafScratch& S, const uint8_t* d_text, const uint64_t* h_file_end, int n_files, const PafTargets& T,
                 int map_qual, int mq_cutoff, double iden_percent, PafStageA& A)
 {
     hipStream_t st = ctx->stream;
-    PAF_ALLOC(d_status, unsigned long long, 1);
+    PAF_ALLOC(d_status, unsigned long long, 2);
     A.file_hits.assign(n_files, nullptr);
     A.hits_upto.assign(n_files + 1, 0);
     A.n_ok = n_files;
@@ -672,12 +683,15 @@ int paf_stage_a(gci_ctx* ctx, PafScratch& S, const uint8_t* d_text, const uint64
         PAF_ALLOC(d_flag, uint32_t, n_lines + 1);
         PAF_ALLOC(d_blk2, uint32_t, n_lines / TILE + 2);
         HIPCHK(hipMemsetAsync(d_status, 0xFF, 8, st));
+        HIPCHK(hipMemsetAsync(d_status + 1, 0, 8, st));
         hipLaunchKernelGGL(k_paf_tokenise, dim3((n_lines + BLOCK - 1) / BLOCK), dim3(BLOCK), PAF_LDS_BYTES + 16, st, d_text, hi, (const uint64_t*)d_starts,
                            n_lines, (uint64_t)0, T, map_qual, mq_cutoff, iden_percent, d_hit, d_flag, d_status);
         LAUNCHCHK("k_paf_tokenise");
-        unsigned long long h_status = 0;
-        HIPCHK(hipMemcpyAsync(&h_status, d_status, 8, hipMemcpyDeviceToHost, st));
+        unsigned long long h_word[2] = {0, 0};
+        HIPCHK(hipMemcpyAsync(h_word, d_status, 16, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));
+        const unsigned long long h_status = h_word[0];
+        A.global_groups += h_word[1];
         if (h_status != ~0ull) {
             // The reference reads and scores file after file: an error in the scoring of an EARLIER file comes first.
             // Remember this one; the caller scores the files before it.
@@ -782,7 +796,9 @@ extern "C" int gci_paf_filter_device(gci_ctx* ctx, const uint8_t* d_text, const 
     int rc = paf_targets(ctx, S, targets, n_targets, T);
     if (rc) return rc;
     PafStageA A;
+    ctx->paf_global_groups = 0;
     rc = paf_stage_a(ctx, S, d_text, h_file_end, n_files, T, map_qual, mq_cutoff, iden_percent, A);
+    ctx->paf_global_groups = A.global_groups;
     if (rc) return rc;
     auto pending = [&]() { if (err_line) *err_line = A.pending_line; return A.pending_status; };
     gci_paf_dev* H = new (std::nothrow) gci_paf_dev();
@@ -827,7 +843,9 @@ extern "C" int gci_paf_hits_device(gci_ctx* ctx, const uint8_t* d_text, const ui
     int rc = paf_targets(ctx, S, targets, n_targets, T);
     if (rc) return rc;
     PafStageA A;
+    ctx->paf_global_groups = 0;
     rc = paf_stage_a(ctx, S, d_text, h_file_end, n_files, T, map_qual, mq_cutoff, iden_percent, A);
+    ctx->paf_global_groups = A.global_groups;
     if (rc) return rc;
     if (A.pending_status != GCI_OK) { if (err_line) *err_line = A.pending_line; return A.pending_status; }
     gci_paf_hits* H = new (std::nothrow) gci_paf_hits();

@@ -845,6 +845,10 @@ class Engine:
         finally:
             self.lib.gci_paf_dev_free(handle)
 
+    def paf_global_groups(self) -> int:
+        """Workgroups of the tokeniser that walked global memory instead of an LDS copy in the last paf_filter*() / paf_hits_text()."""
+        return int(self.lib.gci_paf_global_groups(self.ctx))
+
     # ---- the PAF filter in two halves (runs that shard a PAF file by byte range: shard.paf_by_byte_range) ----
     PAF_HIT_BYTES = 80
 

@@ -219,7 +219,7 @@ def paf_filter(paths, targets, map_qual: int, mq_cutoff: int, iden_percent: floa
     st = lib.gci_paf_filter(ptrs, sizes, n, tarr, len(tnames), int(map_qual), int(mq_cutoff), float(iden_percent),
                             int(threads or default_threads()), ctypes.byref(handle), ctypes.byref(line))
     if st != 0:
-        raise GciError(st, "gci_paf_filter: %s (line %d)" % (lib.gci_strerror(st).decode(), line.value))
+        raise GciError(st, "gci_paf_filter: %s (line %d)" % (lib.gci_strerror(st).decode(), line.value), rec=int(line.value))
     try:
         out = []
         for f in range(n):

@@ -210,11 +210,12 @@ def merge_gaps_depths(depths: DepthTracks = None, Ns_bed=None, lazy: bool = Fals
 
 def _merge_span(pairs: List[Tuple[int, int]]) -> Tuple[int, int, int]:
     """Union of closed-touching blocks: (covered length, start, end of the longest merged block,
-    the leftmost one on ties)."""
+    the leftmost one on ties).  GCI.py:83-93 holds the first sorted block against itself: one whose end lies before
+    its start is counted twice, and the longest piece is the maximum over all pieces, whatever their sign."""
     pairs = sorted(pairs)
-    covered = 0
-    best = (-1, 0, 0)
     lo, hi = pairs[0]
+    covered = hi - lo if hi < lo else 0
+    best = (hi - lo, lo, hi)
     for a, b in pairs[1:] + [(None, None)]:
         if a is not None and hi >= a:
             hi = max(hi, b)

@@ -949,6 +949,10 @@ int gci_paf_score_device(gci_ctx* ctx, const uint8_t* d_names, uint8_t* d_hits, 
 /* The PAF filter's pooled scratch (kept in the context between calls, up to 16 GB) given back to the driver: for a host whose other
  * stages allocate through an allocator of their own.  Synchronises when there is something to free. */
 int gci_paf_pool_release(gci_ctx* ctx);
+/* The tokeniser parses a workgroup's 256 lines from a copy in LDS, or -- when their stretch and its alignment slack exceed 49152
+ * bytes -- walks them in global memory: the number of workgroups that did in the last gci_paf_filter_device /
+ * gci_paf_hits_device of this context.  The two walks give the same hits; this tells them apart. */
+uint64_t gci_paf_global_groups(const gci_ctx* ctx);
 
 /* ---- the way of a memory-mapped input file to the device (staging.cpp) ---------------------------------------------------------
  * A ring of n_slots pinned host buffers of slot_bytes each, filled by `threads` host threads (parallel memcpy out of the page
