@@ -27,6 +27,7 @@ REC_DTYPE = np.dtype([("name_hash", "<u8"), ("contig", "<i4"), ("start", "<i4"),
 IVL_DTYPE = np.dtype([("contig", "<i4"), ("start", "<i4"), ("end", "<i4"), ("pad", "<i4")])
 RUN_DTYPE = np.dtype([("start", "<u4"), ("depth", "<i4")])          # gci_depth_run
 SITE_DTYPE = np.dtype([("contig", "<i4"), ("pos", "<i4"), ("left", "<i4"), ("right", "<i4"), ("depth", "<i4"), ("pad", "<i4")])      # gci_clip_site
+INDEL_SITE_DTYPE = np.dtype([("contig", "<i4"), ("start", "<i4"), ("end", "<i4"), ("del", "<i4"), ("ins", "<i4"), ("depth", "<i4")])      # gci_indel_site
 GCI_TILE = 4096
 
 
@@ -43,7 +44,8 @@ gci_depth_build gci_gap_mask gci_max2 gci_issue_scan gci_issue_scan_windows gci_
 gci_depth_sum gci_range_sums gci_depth_deflate_from_build gci_depth_deflate_size gci_depth_deflate_write gci_depth_text_index
 gci_depth_text_parse gci_sdepth_index gci_sdepth_parse gci_depth_gz_scan gci_depth_gz_runs gci_depth_gz_expand gci_depth_runs_count
 gci_depth_runs_write gci_bedgraph_size gci_bedgraph_write gci_depth_hist gci_bam_cover_size gci_bam_cover_write gci_track_add
-gci_bam_fate gci_bam_cover_size_sel gci_name_join_fate gci_fate_refine gci_bam_reads_size gci_bam_reads_write gci_bam_sweep gci_bam_clip_size gci_bam_clip_write gci_clip_sites_size gci_clip_sites_write""".split()
+gci_bam_fate gci_bam_cover_size_sel gci_name_join_fate gci_fate_refine gci_bam_reads_size gci_bam_reads_write gci_bam_sweep gci_bam_clip_size gci_bam_clip_write gci_clip_sites_size gci_clip_sites_write
+gci_bam_indel_size gci_bam_indel_write gci_indel_sites_size gci_indel_sites_write""".split()
 _PROTO = {name: (name, res, args) for name, res, args in _lib.EXPORTS}
 EXPORTS = [_PROTO[name] for name in _SEAMS] + [("gci_cpu_option", c_int, [c_void_p, c_char_p, c_int])]
 
@@ -291,6 +293,51 @@ class CpuEngine:
         if (out[total:] != -0x5A5A5A5B).any():
             raise CpuError(-1, "gci_clip_sites_write wrote behind its sites")
         return out.view(SITE_DTYPE).reshape(-1)[:total]
+
+    # ---- indel_sites.py (k_indels.hip's twins)
+    def bam_indel(self, stream: np.ndarray, offs: np.ndarray, ref_sel: np.ndarray, has_seq: bool = True, excl_flags: int = 0x704, min_mapq: int = 0,
+                  min_len: int = 50, check: bool = True, cap: Optional[int] = None, guard: int = 0):
+        """device.Engine.bam_indel's twin -> (the deletions, the insertions as IVL_DTYPE, [records counted, deletions, insertions]).
+        cap: the room offered to the write call (default: what the size call asked for); guard: entries of a pattern behind it that must
+        stay (the buffer itself is pre-filled with it)."""
+        stream = np.ascontiguousarray(stream, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        ref_sel = np.ascontiguousarray(ref_sel, dtype=np.int32)
+        counts = np.zeros(3, dtype=np.uint64)
+        self.last_status = np.zeros(1, dtype=np.uint64)
+        self._chk(self.lib.gci_bam_indel_size(self.ctx, _p(stream), stream.shape[0], _p(offs), offs.shape[0], int(has_seq), _p(ref_sel), ref_sel.shape[0],
+                                              int(excl_flags), int(min_mapq), int(min_len), _p(counts), _p(self.last_status)), "gci_bam_indel_size")
+        if check:
+            self._status(self.last_status, "gci_bam_indel_size")
+        n_del, n_ins = int(counts[1]), int(counts[2])
+        room = n_del + n_ins if cap is None else int(cap)
+        out = np.full((max(room, n_del + n_ins) + guard + 1, 4), -0x5A5A5A5B, dtype=np.int32)
+        self.last_out = out
+        self._chk(self.lib.gci_bam_indel_write(self.ctx, _p(stream), stream.shape[0], _p(offs), offs.shape[0], int(has_seq), _p(out), room,
+                                               _p(self.last_status)), "gci_bam_indel_write")
+        if (out[n_del + n_ins:] != -0x5A5A5A5B).any():
+            raise CpuError(-1, "gci_bam_indel_write wrote behind its events")
+        ivl = out.view(IVL_DTYPE).reshape(-1)
+        return ivl[:n_del], ivl[n_del:n_del + n_ins], [int(c) for c in counts]
+
+    def indel_sites(self, dele: np.ndarray, ins: np.ndarray, depth: Optional[np.ndarray], min_reads: int,
+                    windows: Sequence[Tuple[int, int]] = (), cap: Optional[int] = None) -> np.ndarray:
+        """device.Engine.indel_sites's twin -> INDEL_SITE_DTYPE [n].  cap: the room offered to the write call."""
+        nw = len(windows)
+        w = (_Window * max(nw, 1))()
+        for i, (a, b) in enumerate(windows):
+            w[i].begin, w[i].end = int(a), int(b)
+        n = ctypes.c_uint64(0)
+        head = (self.ctx, _p(dele), _p(ins), _p(depth), int(min_reads), w, nw)
+        self._chk(self.lib.gci_indel_sites_size(*head, ctypes.byref(n)), "gci_indel_sites_size")
+        total = int(n.value)
+        room = total if cap is None else int(cap)
+        out = np.full((max(room, total) + 1, 6), -0x5A5A5A5B, dtype=np.int32)
+        self.last_out = out
+        self._chk(self.lib.gci_indel_sites_write(*head, _p(out), room), "gci_indel_sites_write")
+        if (out[total:] != -0x5A5A5A5B).any():
+            raise CpuError(-1, "gci_indel_sites_write wrote behind its sites")
+        return out.view(INDEL_SITE_DTYPE).reshape(-1)[:total]
 
     def track_add(self, acc: np.ndarray, add: np.ndarray) -> np.ndarray:
         self._chk(self.lib.gci_track_add(self.ctx, _p(acc), _p(add)), "gci_track_add")

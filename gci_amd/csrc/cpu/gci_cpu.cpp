@@ -73,6 +73,22 @@ struct gci_ctx {
     const void* sites_depth = nullptr;
     int32_t sites_min_reads = 0;
     uint32_t sites_windows = 0;
+    // indel_sites.py: the events the last gci_bam_indel_size found (deletions, then insertions, each in record and operation order)
+    // and the sites the last gci_indel_sites_size found, with what each call measured
+    std::vector<gci_ivl> indel_del, indel_ins;
+    uint64_t indel_status = ~0ull;
+    bool indel_valid = false;
+    uint32_t indel_n_rec = 0;
+    uint64_t indel_n_bytes = 0;
+    const void* indel_stream = nullptr;
+    const void* indel_off = nullptr;
+    std::vector<gci_indel_site> isites;
+    bool isites_valid = false;
+    const void* isites_del = nullptr;
+    const void* isites_ins = nullptr;
+    const void* isites_depth = nullptr;
+    int32_t isites_min_reads = 0;
+    uint32_t isites_windows = 0;
 };
 
 namespace {
@@ -706,6 +722,7 @@ int gci_layout_set(gci_ctx* ctx, int32_t n_contigs, const int64_t* h_lengths)
     ctx->n_contigs = n_contigs;
     ctx->bg_track = nullptr; ctx->bg_text_run0 = nullptr;
     ctx->clip_valid = false; ctx->sites_valid = false;
+    ctx->indel_valid = false; ctx->isites_valid = false;
     return GCI_OK;
 }
 int64_t gci_layout_total(gci_ctx* ctx) { return ctx ? ctx->total : 0; }
@@ -1222,6 +1239,155 @@ int gci_clip_sites_write(gci_ctx* ctx, const int32_t* left, const int32_t* right
     if (!ctx->sites.empty() && !out) return GCI_E_INVALID;
     if (cap < ctx->sites.size()) return GCI_E_CAPACITY;
     std::copy(ctx->sites.begin(), ctx->sites.end(), out);
+    return GCI_OK;
+}
+
+/* ---- indel_sites.py: long insertions and deletions in reads (k_indels.hip's twins, from the text of include/gci_hip.h: a record, an operation,
+ * an element at a time) ---- */
+int gci_bam_indel_size(gci_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, const uint64_t* rec_off, uint32_t n_rec, int has_seq, const int32_t* ref_sel,
+                       int32_t n_ref, uint32_t excl_flags, int min_mapq, int min_len, uint64_t* h_counts, uint64_t* status)
+{
+    if (!ctx || !h_counts || !status || n_ref < 0 || min_len < 1 || (n_rec && (!bam || !rec_off || !ref_sel))) return GCI_E_INVALID;
+    const int lst = need_layout(ctx);
+    if (lst) return lst;
+    ctx->indel_valid = false;
+    ctx->indel_del.clear(); ctx->indel_ins.clear();
+    uint64_t st = ~0ull, counted = 0;
+    for (uint32_t i = 0; i < n_rec; i++) {
+        const uint64_t off = rec_off[i];
+        const uint64_t word = ((uint64_t)i << 8) | (uint64_t)(uint8_t)(-GCI_E_MALFORMED);
+        if (off > n_bytes || n_bytes - off < 36) { st = std::min(st, word); continue; }
+        const uint8_t* p = bam + off;
+        const int32_t block_size = (int32_t)rd32(p), ref_id = (int32_t)rd32(p + 4), pos = (int32_t)rd32(p + 8);
+        const uint32_t l_read_name = p[12], n_cigar = rd16(p + 16), flag = rd16(p + 18);
+        const int mapq = p[13];
+        const int32_t l_seq = (int32_t)rd32(p + 20);
+        const uint64_t rec_end = off + 4 + (uint64_t)(uint32_t)block_size;
+        const uint64_t cig_off = off + 36 + l_read_name;
+        const uint64_t aux_off = cig_off + 4ull * n_cigar + (has_seq ? (((uint64_t)(uint32_t)l_seq + 1) >> 1) + (uint64_t)(uint32_t)l_seq : 0ull);
+        if (block_size < 32 || rec_end > n_bytes || l_seq < 0 || aux_off > rec_end) { st = std::min(st, word); continue; }
+        if ((flag & excl_flags) || mapq < min_mapq || ref_id < 0 || ref_id >= n_ref || pos < 0 || ref_sel[ref_id] < 0) continue;      // skipped
+        counted++;
+        // the operations: the record's own, or the first CG:B,I / B,i array behind <l_seq>S (none usable: the record's own stay)
+        const uint8_t* ops = bam + cig_off;
+        uint64_t n = n_cigar;
+        if (n > 0 && (rd32(ops) & 0xFu) == 4u && (rd32(ops) >> 4) == (uint32_t)l_seq) {
+            const uint8_t* end = bam + rec_end;
+            for (const uint8_t* q = bam + aux_off; q + 3 <= end;) {
+                const int64_t sz = aux_value_size(q + 3, end, q[2]);
+                if (sz < 0 || q + 3 + sz > end) break;
+                if (q[0] == 'C' && q[1] == 'G') {
+                    if (q[2] == 'B' && (q[3] == 'I' || q[3] == 'i')) {
+                        const uint32_t cg_len = rd32(q + 4);
+                        if (cg_len >= n_cigar && cg_len < (1u << 29)) { ops = q + 8; n = cg_len; }
+                    }
+                    break;
+                }
+                q += 3 + sz;
+            }
+        }
+        const int32_t contig = ref_sel[ref_id];
+        const uint64_t L = contig < ctx->n_contigs ? std::min<uint64_t>((uint64_t)ctx->len[(size_t)contig], 0x7FFFFFFEull) : 0;
+        uint64_t at = (uint64_t)pos;
+        bool bad = false;
+        for (uint64_t k = 0; k < n; k++) {
+            const uint32_t w = rd32(ops + 4 * k), op = w & 0xFu;
+            const uint64_t len = w >> 4;
+            if (op >= 9u) { bad = true; continue; }
+            if (op == 2u && len >= (uint64_t)min_len && at < L)
+                ctx->indel_del.push_back(gci_ivl{contig, (int32_t)at, (int32_t)(std::min(at + len, L) - 1), 0});
+            if (op == 1u && len >= (uint64_t)min_len) {
+                const uint64_t site = at > 0 ? at - 1 : 0;
+                if (site < L) ctx->indel_ins.push_back(gci_ivl{contig, (int32_t)site, (int32_t)site, 0});
+            }
+            if (op == 0u || op == 2u || op == 3u || op == 7u || op == 8u) at += len;              // M D N = X
+        }
+        if (bad) st = std::min(st, word);
+    }
+    ctx->indel_status = st;
+    ctx->indel_valid = true; ctx->indel_n_rec = n_rec; ctx->indel_n_bytes = n_bytes; ctx->indel_stream = bam; ctx->indel_off = rec_off;
+    h_counts[0] = counted; h_counts[1] = ctx->indel_del.size(); h_counts[2] = ctx->indel_ins.size();
+    *status = st;
+    return GCI_OK;
+}
+
+int gci_bam_indel_write(gci_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, const uint64_t* rec_off, uint32_t n_rec, int, gci_ivl* out, uint64_t cap,
+                        uint64_t* status)
+{
+    if (!ctx || !status || (n_rec && (!bam || !rec_off))) return GCI_E_INVALID;
+    const int lst = need_layout(ctx);
+    if (lst) return lst;
+    if (!ctx->indel_valid || ctx->indel_n_rec != n_rec || ctx->indel_n_bytes != n_bytes || bam != ctx->indel_stream || rec_off != ctx->indel_off)
+        return GCI_E_INVALID;
+    const uint64_t total = ctx->indel_del.size() + ctx->indel_ins.size();
+    if (total && !out) return GCI_E_INVALID;
+    if (cap < total) return GCI_E_CAPACITY;
+    std::copy(ctx->indel_del.begin(), ctx->indel_del.end(), out);
+    std::copy(ctx->indel_ins.begin(), ctx->indel_ins.end(), out + ctx->indel_del.size());
+    *status = ctx->indel_status;
+    return GCI_OK;
+}
+
+int gci_indel_sites_size(gci_ctx* ctx, const int32_t* del, const int32_t* ins, const int32_t* depth, int32_t min_reads, const gci_window* h_windows,
+                         uint32_t n_windows, uint64_t* h_n_sites)
+{
+    if (!ctx || !del || !ins || !h_n_sites || min_reads < 1 || (n_windows && !h_windows)) return GCI_E_INVALID;
+    const int lst = need_layout(ctx);
+    if (lst) return lst;
+    if ((((uintptr_t)del) | ((uintptr_t)ins) | ((uintptr_t)depth)) & 15u) return GCI_E_INVALID;
+    ctx->isites_valid = false;
+    *h_n_sites = 0;
+    std::vector<gci_window> ws;
+    if (n_windows == 0) {
+        for (int32_t c = 0; c < ctx->n_contigs; c++) ws.push_back(gci_window{ctx->off[(size_t)c], ctx->off[(size_t)c] + ctx->len[(size_t)c]});
+    } else {
+        int64_t at = 0;
+        for (uint32_t i = 0; i < n_windows; i++) {
+            gci_window w = h_windows[i];
+            w.begin = std::max<int64_t>(w.begin, 0);
+            w.end = std::max(std::min(w.end, ctx->total), w.begin);
+            if (w.begin < at) return GCI_E_INVALID;                        // not sorted and disjoint
+            at = w.end;
+            ws.push_back(w);
+        }
+    }
+    ctx->isites.clear();
+    for (const gci_window& w : ws) {
+        bool open = false;                                                  // a run never crosses from one window into the next
+        for (int64_t p = w.begin; p < w.end; p++) {
+            const int32_t c = (int32_t)(std::upper_bound(ctx->off.begin(), ctx->off.end(), p) - ctx->off.begin()) - 1;
+            const int64_t pos = p - ctx->off[(size_t)c];
+            const bool hot = pos < ctx->len[(size_t)c] && (del[p] >= min_reads || ins[p] >= min_reads);
+            if (open && (!hot || pos == 0)) open = false;                   // ... nor from one contig into the next
+            if (!hot) continue;
+            if (!open) {
+                ctx->isites.push_back(gci_indel_site{c, (int32_t)pos, (int32_t)pos, del[p], ins[p], depth ? depth[p] : 0});
+                open = true;
+            }
+            gci_indel_site& s = ctx->isites.back();
+            s.end = (int32_t)pos + 1;
+            s.del = std::max(s.del, del[p]); s.ins = std::max(s.ins, ins[p]);
+            if (depth) s.depth = std::max(s.depth, depth[p]);
+        }
+    }
+    ctx->isites_valid = true; ctx->isites_del = del; ctx->isites_ins = ins; ctx->isites_depth = depth;
+    ctx->isites_min_reads = min_reads; ctx->isites_windows = n_windows;
+    *h_n_sites = ctx->isites.size();
+    return GCI_OK;
+}
+
+int gci_indel_sites_write(gci_ctx* ctx, const int32_t* del, const int32_t* ins, const int32_t* depth, int32_t min_reads, const gci_window* h_windows,
+                          uint32_t n_windows, gci_indel_site* out, uint64_t cap)
+{
+    if (!ctx || !del || !ins || min_reads < 1 || (n_windows && !h_windows)) return GCI_E_INVALID;
+    const int lst = need_layout(ctx);
+    if (lst) return lst;
+    if (!ctx->isites_valid || del != ctx->isites_del || ins != ctx->isites_ins || depth != ctx->isites_depth || min_reads != ctx->isites_min_reads ||
+        n_windows != ctx->isites_windows)
+        return GCI_E_INVALID;
+    if (!ctx->isites.empty() && !out) return GCI_E_INVALID;
+    if (cap < ctx->isites.size()) return GCI_E_CAPACITY;
+    std::copy(ctx->isites.begin(), ctx->isites.end(), out);
     return GCI_OK;
 }
 

@@ -164,6 +164,22 @@ struct gci_ctx {
     const void* clip_sites_depth = nullptr;
     int32_t clip_sites_min_reads = 0;
     uint32_t clip_sites_windows = 0;
+    // k_indels.hip: what gci_bam_indel_size keeps for gci_bam_indel_write -- per record (parse, chunk counts, counted) and per chunk
+    // (base sums, reference length, deletions, insertions and their scans) --, and what gci_indel_sites_size keeps for
+    // gci_indel_sites_write -- per window tile its run starts and their scan
+    DevBuf indel_rec, indel_chunk, indel_tiles;
+    bool indel_valid = false;
+    uint32_t indel_n_rec = 0;
+    int indel_min_len = 0;
+    uint64_t indel_n_bytes = 0, indel_n_chunks = 0, indel_n_del = 0, indel_n_ins = 0;
+    const void* indel_stream = nullptr;
+    const void* indel_off = nullptr;
+    uint64_t indel_sites_epoch = 0, indel_sites_total = 0;    // (epoch 0: no size call yet)
+    const void* indel_sites_del = nullptr;
+    const void* indel_sites_ins = nullptr;
+    const void* indel_sites_depth = nullptr;
+    int32_t indel_sites_min_reads = 0;
+    uint32_t indel_sites_windows = 0;
     void* h_pinned = nullptr;               // staging for small uploads
     size_t h_pinned_cap = 0;
     // optional per-kernel HIP-event timing (gci_profile_*)
@@ -570,3 +586,25 @@ int gci_launch_reduce_tiles(gci_ctx* ctx, const long long* tile_sum, unsigned lo
 int gci_launch_contig_text_off(gci_ctx* ctx, const uint64_t* tile_off, uint64_t* contig_off);
 // the windows of an issue scan, clamped to the track, with their tiles: ctx->win, win_tile_first (n_win + 1 entries), win_n, win_tiles
 int gci_set_windows(gci_ctx* ctx, const gci_window* h_win, uint32_t n_win);
+
+// the windows of a sites call (k_clips.hip, k_indels.hip) on the host: clamped as gci_set_windows clamps them, none: every contig of the
+// layout; false when they are not sorted and disjoint
+static inline bool gci_site_windows(const gci_ctx* ctx, const gci_window* h_windows, uint32_t n_windows, std::vector<gci_window>& ws)
+{
+    ws.clear();
+    if (n_windows == 0) {
+        for (int32_t c = 0; c < ctx->n_contigs; c++) ws.push_back(gci_window{ctx->off[(size_t)c], ctx->off[(size_t)c] + ctx->len[(size_t)c]});
+        return true;
+    }
+    int64_t at = 0;
+    for (uint32_t i = 0; i < n_windows; i++) {
+        gci_window w = h_windows[i];
+        if (w.begin < 0) w.begin = 0;
+        if (w.end > ctx->total) w.end = ctx->total;
+        if (w.end < w.begin) w.end = w.begin;
+        if (w.begin < at) return false;
+        at = w.end;
+        ws.push_back(w);
+    }
+    return true;
+}

@@ -352,27 +352,6 @@ __global__ __launch_bounds__(BLOCK) void k_clip_sites_write(const int32_t* __res
     }
 }
 
-// the windows of a sites call on the host: clamped as gci_set_windows clamps them; false when they are not sorted and disjoint
-static bool clip_windows(const gci_ctx* ctx, const gci_window* h_windows, uint32_t n_windows, std::vector<gci_window>& ws)
-{
-    ws.clear();
-    if (n_windows == 0) {                              // every contig of the layout
-        for (int32_t c = 0; c < ctx->n_contigs; c++) ws.push_back(gci_window{ctx->off[(size_t)c], ctx->off[(size_t)c] + ctx->len[(size_t)c]});
-        return true;
-    }
-    int64_t at = 0;
-    for (uint32_t i = 0; i < n_windows; i++) {
-        gci_window w = h_windows[i];
-        if (w.begin < 0) w.begin = 0;
-        if (w.end > ctx->total) w.end = ctx->total;
-        if (w.end < w.begin) w.end = w.begin;
-        if (w.begin < at) return false;
-        at = w.end;
-        ws.push_back(w);
-    }
-    return true;
-}
-
 struct ClipTileScratch { uint32_t* cnt; unsigned long long* off; unsigned long long* blk; };
 
 static inline ClipTileScratch cl_tile_scratch(gci_ctx* ctx, int64_t tiles)
@@ -393,7 +372,7 @@ extern "C" int gci_clip_sites_size(gci_ctx* ctx, const int32_t* d_left, const in
     if ((((uintptr_t)d_left) | ((uintptr_t)d_right) | ((uintptr_t)d_depth)) & 15u) return GCI_E_INVALID;      // whole tracks, as allocated
     if (n_windows >= (1u << 31)) return GCI_E_INVALID;
     std::vector<gci_window> ws;
-    if (!clip_windows(ctx, h_windows, n_windows, ws)) return GCI_E_INVALID;
+    if (!gci_site_windows(ctx, h_windows, n_windows, ws)) return GCI_E_INVALID;
     ctx->clip_sites_epoch = 0;
     *h_n_sites = 0;
     GCI_TRY(gci_set_windows(ctx, ws.data(), (uint32_t)ws.size()));

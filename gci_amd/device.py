@@ -26,6 +26,7 @@ assert REC_DTYPE.itemsize == 32
 IVL_DTYPE = np.dtype([("contig", "<i4"), ("start", "<i4"), ("end", "<i4"), ("pad", "<i4")])
 RUN_DTYPE = np.dtype([("start", "<u4"), ("depth", "<i4")])          # gci_depth_run
 SITE_DTYPE = np.dtype([("contig", "<i4"), ("pos", "<i4"), ("left", "<i4"), ("right", "<i4"), ("depth", "<i4"), ("pad", "<i4")])      # gci_clip_site
+INDEL_SITE_DTYPE = np.dtype([("contig", "<i4"), ("start", "<i4"), ("end", "<i4"), ("del", "<i4"), ("ins", "<i4"), ("depth", "<i4")])      # gci_indel_site
 
 _M64 = (1 << 64) - 1
 Buffer = Any                  # a device buffer of the engine's provider: hbm.Buf or Buffer
@@ -456,6 +457,44 @@ class Engine:
         out = self.T.empty((total, 6), self.T.int32, self.device)
         self._chk(self.lib.gci_clip_sites_write(*head, self._p(out), total), "gci_clip_sites_write")
         return np.ascontiguousarray(out.cpu().numpy()).view(SITE_DTYPE).reshape(-1)[:total]
+
+    # ---- indel_sites.py: long insertions and deletions in reads (include/gci_hip.h: gci_bam_indel_*, gci_indel_sites_*; k_indels.hip) ----
+    def bam_indel(self, d_stream: Buffer, d_rec_off: Buffer, has_seq: bool, d_ref_sel: Buffer, excl_flags: int = 0x704, min_mapq: int = 0,
+                  min_len: int = 50, check: bool = True, rec_idx_base: int = 0) -> Tuple[Buffer, Buffer, List[int]]:
+        """-> (the deletions, the insertions, [records counted, deletions, insertions]): two views of one buffer of intervals int32
+        [n, 4] -- per D operation of at least min_len bases in a counted record of an inflated BAM stream (has_seq) or a heads stream
+        (contig, first deleted base, last deleted base, 0), per such I operation (contig, site, site, 0) with the site the base in front
+        of the inserted bases --, each in (record, operation) order, for depth_build with flank 0.  Needs the layout of the selected
+        contigs."""
+        n = int(d_rec_off.shape[0])
+        counts = (ctypes.c_uint64 * 3)()
+        self._chk(self.lib.gci_bam_indel_size(self.ctx, self._p(d_stream), int(d_stream.shape[0]), self._p(d_rec_off), n, int(has_seq),
+                                              self._p(d_ref_sel), int(d_ref_sel.shape[0]), int(excl_flags), int(min_mapq), int(min_len), counts,
+                                              self._p(self._status)), "gci_bam_indel_size")
+        if check:
+            self._raise_status(self._status.item(), "gci_bam_indel_size", rec_idx_base)
+        n_del, n_ins = int(counts[1]), int(counts[2])
+        out = self.T.empty((max(n_del + n_ins, 1), 4), self.T.int32, self.device)
+        self._chk(self.lib.gci_bam_indel_write(self.ctx, self._p(d_stream), int(d_stream.shape[0]), self._p(d_rec_off), n, int(has_seq),
+                                               self._p(out), n_del + n_ins, self._p(self._status)), "gci_bam_indel_write")
+        return out[:n_del], out[n_del:n_del + n_ins], [int(c) for c in counts]
+
+    def indel_sites(self, dele: Buffer, ins: Buffer, depth: Optional[Buffer], min_reads: int,
+                    windows: Sequence[Tuple[int, int]] = ()) -> np.ndarray:
+        """-> INDEL_SITE_DTYPE [n]: the maximal runs of elements of the tracks `dele` / `ins` with del >= min_reads or ins >= min_reads
+        inside the sorted, disjoint [begin, end) windows of track elements (none: every contig), in ascending order: contig, start, end
+        (exclusive) and the maxima of the two tracks and of `depth` (0 without a depth track) over the run."""
+        nw = len(windows)
+        arr = self._window_array(windows)
+        n = ctypes.c_uint64(0)
+        head = (self.ctx, self._p(dele), self._p(ins), self._p(depth), int(min_reads), arr, nw)
+        self._chk(self.lib.gci_indel_sites_size(*head, ctypes.byref(n)), "gci_indel_sites_size")
+        total = int(n.value)
+        if total == 0:
+            return np.zeros(0, dtype=INDEL_SITE_DTYPE)
+        out = self.T.empty((total, 6), self.T.int32, self.device)
+        self._chk(self.lib.gci_indel_sites_write(*head, self._p(out), total), "gci_indel_sites_write")
+        return np.ascontiguousarray(out.cpu().numpy()).view(INDEL_SITE_DTYPE).reshape(-1)[:total]
 
     def track_add(self, acc: Buffer, add: Buffer) -> Buffer:
         """acc += add over the layout."""

@@ -29,7 +29,7 @@ from typing import Dict, List, Optional, Sequence, Set, Tuple
 import numpy as np
 
 from . import hbm, hostio, phases, score
-from .device import Buffer, Engine, JoinInput, REC_DTYPE, SITE_DTYPE, name_hash_np
+from .device import Buffer, Engine, INDEL_SITE_DTYPE, JoinInput, REC_DTYPE, SITE_DTYPE, name_hash_np
 from . import _lib
 from ._lib import GciError, REC_HQ, REC_PASS
 from .formats import bam as bamfmt
@@ -1348,9 +1348,12 @@ class _ClipVisitor(StreamVisitor):
     """_CoverVisitor with two more tracks: every piece goes through gci_bam_cover_* (the depth) and gci_bam_clip_* (the left and the
     right events), so a file is read once; three _IntervalCollectors with the flush and hand-over rules of _CoverVisitor."""
 
-    def __init__(self, main: Engine, opts: CoverOpts, min_clip: int, budget: int):
-        self.main, self.opts, self.min_clip, self.budget = main, opts, int(min_clip), max(int(budget), 1)
-        self.collectors = {name: _IntervalCollector() for name in _CLIP_TRACKS}
+    TRACKS = _CLIP_TRACKS                              # the two halves of the event call, then the depth
+    PHASE, CALL = "record clips", "gci_bam_clip_size"
+
+    def __init__(self, main: Engine, opts: CoverOpts, min_bases: int, budget: int):
+        self.main, self.opts, self.min_bases, self.budget = main, opts, int(min_bases), max(int(budget), 1)
+        self.collectors = {name: _IntervalCollector() for name in self.TRACKS}
         self.counts = [0, 0, 0]
 
     flushes = property(lambda self: sum(c.flushes for c in self.collectors.values()))
@@ -1361,6 +1364,10 @@ class _ClipVisitor(StreamVisitor):
         self.counts = [0, 0, 0]
 
     abort_file = begin_file
+
+    def events(self, engine, d_stream, d_off, has_seq, ref_sel):
+        """-> (the first half, the second half, the three counts) of the piece."""
+        return engine.bam_clip(d_stream, d_off, has_seq, ref_sel, self.opts.excl, self.opts.min_mapq, self.min_bases)
 
     def visit(self, engine, d_stream, d_off, has_seq, ref_sel, rec_idx_base) -> None:
         if engine.lengths != self.main.lengths:            # (the walk engine: a context of its own)
@@ -1373,14 +1380,14 @@ class _ClipVisitor(StreamVisitor):
                 raise
             raise _file_record_error(engine, e, "gci_bam_cover_size", rec_idx_base) from None
         try:
-            with phases.gpu("record clips"):
-                left, right, counts = engine.bam_clip(d_stream, d_off, has_seq, ref_sel, self.opts.excl, self.opts.min_mapq, self.min_clip)
+            with phases.gpu(self.PHASE):
+                first, second, counts = self.events(engine, d_stream, d_off, has_seq, ref_sel)
         except GciError as e:
             if e.rec < 0:
                 raise
-            raise _file_record_error(engine, e, "gci_bam_clip_size", rec_idx_base) from None
+            raise _file_record_error(engine, e, self.CALL, rec_idx_base) from None
         self.counts = [a + b for a, b in zip(self.counts, counts)]
-        for name, part in zip(_CLIP_TRACKS, (left, right, ivl)):
+        for name, part in zip(self.TRACKS, (first, second, ivl)):
             c = self.collectors[name]
             c.add(part)
             if c.n_ivl > self.budget:
@@ -1390,7 +1397,55 @@ class _ClipVisitor(StreamVisitor):
 
     def file_done(self) -> Dict[str, Buffer]:
         """The file's three tracks (the caller's engine and stream)."""
-        return {name: self.collectors[name].finish(self.main) for name in _CLIP_TRACKS}
+        return {name: self.collectors[name].finish(self.main) for name in self.TRACKS}
+
+
+def _event_tracks(engine: Engine, bam_files: Sequence[str], chrs: Sequence[str], make_visitor, threads: int, wall: str,
+                  regions: Optional[Sequence[Tuple[str, int, int]]]):
+    """What bam_clip_sites and bam_indel_sites share: the layout of the first file's contigs (restricted by `chrs`), the TracksDoNotFit
+    check before anything is read, every file once through make_visitor(engine)'s three collectors, the files' tracks added up
+    -> (targets_length, the three summed tracks by name, counts per file, the visitor, the windows of `regions` in flat track elements
+    -- None: `regions` holds no window of a selected contig)."""
+    first = same_sq_table(bam_files)
+    targets_length = _targets_of(first, list(chrs))
+    targets = list(targets_length.keys())
+    if not targets:
+        raise ValueError("no contig selected")
+    engine.set_layout([targets_length[t] for t in targets])
+    # three tracks, one more while intervals are built in parts -- and with several files a second set, the file's next to the sum of
+    # the files before it
+    n_tracks = 3 * (2 if len(bam_files) > 1 else 1) + 1
+    track_bytes, free = 4 * int(engine.total), device_memory_free(engine)
+    if n_tracks * track_bytes > free:
+        raise TracksDoNotFit(n_tracks, track_bytes, free)
+    visitor = make_visitor(engine)
+    totals: Dict[str, Buffer] = {}
+    counts = []
+    for path in bam_files:
+        visitor.begin_file()
+        try:
+            with phases.wall("%s[%s]" % (wall, os.path.basename(path))):
+                bam_join_input(engine, path, targets, visitor, threads)
+        except BaseException as e:
+            visitor.abort_file()
+            if isinstance(e, GciError):
+                e.path = path                             # (which file the record index counts in: the command line says so)
+            raise
+        counts.append(list(visitor.counts))
+        for name, track in visitor.file_done().items():
+            if name in totals:
+                engine.track_add(totals[name], track)
+            else:
+                totals[name] = track
+    windows: Optional[List[Tuple[int, int]]] = []
+    if regions is not None:
+        win, win0 = merge_windows(regions, targets_length)
+        for c in range(len(targets)):
+            o = int(engine.offsets[c])
+            windows += [(o + int(a), o + int(b)) for a, b in win[int(win0[c]):int(win0[c + 1])].tolist()]
+        if not windows:
+            windows = None
+    return targets_length, totals, counts, visitor, windows
 
 
 def bam_clip_sites(engine: Engine, bam_files: Sequence[str], chrs: Sequence[str] = (), cover_opts: Optional[CoverOpts] = None, threads: int = 1,
@@ -1405,45 +1460,11 @@ def bam_clip_sites(engine: Engine, bam_files: Sequence[str], chrs: Sequence[str]
     opts = cover_opts or CoverOpts()
     if int(min_clip) < 1 or int(min_reads) < 1:
         raise ValueError("min_clip and min_reads are at least 1")
-    first = same_sq_table(bam_files)
-    targets_length = _targets_of(first, list(chrs))
-    targets = list(targets_length.keys())
-    if not targets:
-        raise ValueError("no contig selected")
-    engine.set_layout([targets_length[t] for t in targets])
-    # three tracks, one more while intervals are built in parts -- and with several files a second set, the file's next to the sum of
-    # the files before it
-    n_tracks = 3 * (2 if len(bam_files) > 1 else 1) + 1
-    track_bytes, free = 4 * int(engine.total), device_memory_free(engine)
-    if n_tracks * track_bytes > free:
-        raise TracksDoNotFit(n_tracks, track_bytes, free)
-    visitor = _ClipVisitor(engine, opts, min_clip, COVER_IVL_BUDGET if ivl_budget is None else ivl_budget)
-    totals: Dict[str, Buffer] = {}
-    counts = []
-    for path in bam_files:
-        visitor.begin_file()
-        try:
-            with phases.wall("bam_clip[%s]" % os.path.basename(path)):
-                bam_join_input(engine, path, targets, visitor, threads)
-        except BaseException as e:
-            visitor.abort_file()
-            if isinstance(e, GciError):
-                e.path = path                             # (which file the record index counts in: the command line says so)
-            raise
-        counts.append(list(visitor.counts))
-        for name, track in visitor.file_done().items():
-            if name in totals:
-                engine.track_add(totals[name], track)
-            else:
-                totals[name] = track
-    windows: List[Tuple[int, int]] = []
-    if regions is not None:
-        win, win0 = merge_windows(regions, targets_length)
-        for c in range(len(targets)):
-            o = int(engine.offsets[c])
-            windows += [(o + int(a), o + int(b)) for a, b in win[int(win0[c]):int(win0[c + 1])].tolist()]
+    budget = COVER_IVL_BUDGET if ivl_budget is None else ivl_budget
+    targets_length, totals, counts, visitor, windows = _event_tracks(engine, bam_files, chrs, lambda e: _ClipVisitor(e, opts, min_clip, budget),
+                                                                     threads, "bam_clip", regions)
     with phases.gpu("clip sites"):
-        if regions is not None and not windows:
+        if windows is None:
             sites = np.zeros(0, dtype=SITE_DTYPE)
         else:
             sites = engine.clip_sites(totals["left"], totals["right"], totals["depth"], int(min_reads), windows)
@@ -1461,6 +1482,77 @@ def clip_sites_bed(sites: np.ndarray, targets: Sequence[str]) -> str:
 def clip_summary_text(bam_files: Sequence[str], counts: Sequence[Sequence[int]], n_sites: int, options: Sequence[Tuple[str, object]]) -> str:
     """The text of {PREFIX}.clip.txt: per file and in total the records counted, the left and the right events; the sites; the options."""
     lines = ["#file\trecords\tleft_events\tright_events\tpath"]
+    for k, (path, row) in enumerate(zip(bam_files, counts), 1):
+        lines.append("%d\t%d\t%d\t%d\t%s" % (k, row[0], row[1], row[2], path))
+    lines.append("total\t%d\t%d\t%d\t." % tuple(sum(int(row[j]) for row in counts) for j in range(3)))
+    lines.append("sites\t%d" % n_sites)
+    lines += ["%s\t%s" % (name, value) for name, value in options]
+    return "\n".join(lines) + "\n"
+
+
+# ==============================================================================================
+# indel_sites.py: long insertions and deletions in reads, base by base
+# ==============================================================================================
+
+INDEL_MIN_LEN = 50                         # the conventional floor of a structural variant: a choice, not a measurement
+INDEL_MIN_READS = 3
+_INDEL_TRACKS = ("del", "ins", "depth")
+
+
+class IndelSites:
+    """What bam_indel_sites returns: dele / ins / depth = the three DepthTracks (per base the counted records that delete it with one
+    long D; the long insertions anchored at it; the read-mapping depth), sites = device.INDEL_SITE_DTYPE [n] in contig order and then
+    by position, counts[k] = [records counted, deletions, insertions] of file k, flushes = how often intervals were built into a track
+    before their file was through."""
+
+    def __init__(self, dele: DepthTracks, ins: DepthTracks, depth: DepthTracks, sites: np.ndarray, counts: List[List[int]], flushes: int):
+        self.dele, self.ins, self.depth, self.sites, self.counts, self.flushes = dele, ins, depth, sites, counts, flushes
+
+
+class _IndelVisitor(_ClipVisitor):
+    """_ClipVisitor with gci_bam_indel_* as the event call: the deletions and the insertions of every piece next to its cover."""
+
+    TRACKS = _INDEL_TRACKS
+    PHASE, CALL = "record indels", "gci_bam_indel_size"
+
+    def events(self, engine, d_stream, d_off, has_seq, ref_sel):
+        return engine.bam_indel(d_stream, d_off, has_seq, ref_sel, self.opts.excl, self.opts.min_mapq, self.min_bases)
+
+
+def bam_indel_sites(engine: Engine, bam_files: Sequence[str], chrs: Sequence[str] = (), cover_opts: Optional[CoverOpts] = None, threads: int = 1,
+                    min_len: int = INDEL_MIN_LEN, min_reads: int = INDEL_MIN_READS, regions: Optional[Sequence[Tuple[str, int, int]]] = None,
+                    ivl_budget: Optional[int] = None) -> IndelSites:
+    """The long insertions and deletions the reads of `bam_files` carry (include/gci_hip.h: gci_bam_indel_size, gci_indel_sites_size):
+    per base the counted records that delete it with one D operation of at least `min_len` bases, the I operations of at least
+    `min_len` bases anchored at it (the base in front of the inserted bases), the read-mapping depth as bam_raw_depth counts it with
+    the same options -- without count_del it does not count a read over the bases it deletes: the reads that span a deleted base are
+    depth + del --, and the runs of bases where del or ins reaches `min_reads`.  Files, contigs, regions and TracksDoNotFit as in
+    bam_clip_sites."""
+    opts = cover_opts or CoverOpts()
+    if int(min_len) < 1 or int(min_reads) < 1:
+        raise ValueError("min_len and min_reads are at least 1")
+    budget = COVER_IVL_BUDGET if ivl_budget is None else ivl_budget
+    targets_length, totals, counts, visitor, windows = _event_tracks(engine, bam_files, chrs, lambda e: _IndelVisitor(e, opts, min_len, budget),
+                                                                     threads, "bam_indel", regions)
+    with phases.gpu("indel sites"):
+        if windows is None:
+            sites = np.zeros(0, dtype=INDEL_SITE_DTYPE)
+        else:
+            sites = engine.indel_sites(totals["del"], totals["ins"], totals["depth"], int(min_reads), windows)
+    tracks = {name: DepthTracks(engine, targets_length, totals[name]) for name in _INDEL_TRACKS}
+    return IndelSites(tracks["del"], tracks["ins"], tracks["depth"], sites, counts, visitor.flushes)
+
+
+def indel_sites_bed(sites: np.ndarray, targets: Sequence[str]) -> str:
+    """`contig\\tstart\\tend\\tdel\\tins\\tdepth\\n` per site, no header line: a BED file bedgraph_cli.parse_regions reads."""
+    return "".join("%s\t%d\t%d\t%d\t%d\t%d\n" % (targets[c], a, b, d, i, x)
+                   for c, a, b, d, i, x in zip(*(sites[f].tolist() for f in ("contig", "start", "end", "del", "ins", "depth"))))
+
+
+def indel_summary_text(bam_files: Sequence[str], counts: Sequence[Sequence[int]], n_sites: int, options: Sequence[Tuple[str, object]]) -> str:
+    """The text of {PREFIX}.indel.txt: per file and in total the records counted, the deletions and the insertions; the sites; the
+    options."""
+    lines = ["#file\trecords\tdeletions\tinsertions\tpath"]
     for k, (path, row) in enumerate(zip(bam_files, counts), 1):
         lines.append("%d\t%d\t%d\t%d\t%s" % (k, row[0], row[1], row[2], path))
     lines.append("total\t%d\t%d\t%d\t." % tuple(sum(int(row[j]) for row in counts) for j in range(3)))

@@ -517,6 +517,66 @@ int gci_clip_sites_size(gci_ctx* ctx, const int32_t* d_left, const int32_t* d_ri
 int gci_clip_sites_write(gci_ctx* ctx, const int32_t* d_left, const int32_t* d_right, const int32_t* d_depth, int32_t min_reads,
                          const gci_window* h_windows, uint32_t n_windows, gci_clip_site* d_out, uint64_t cap);
 
+/* ---- indel_sites.py: long insertions and deletions in reads, base by base (k_indels.hip) ------------------------------------------------
+ * gci_bam_indel_size / _write: the same input as gci_bam_cover_size (the inflated stream plus record offsets, or a heads stream with
+ * has_seq = 0); they need gci_layout_set.  Per record:
+ *   counted    exactly when gci_bam_cover_size does not skip it with the same excl_flags (0x704 by default: supplementary alignments
+ *              count) and min_mapq: flag, MAPQ, refID, pos and d_ref_sel are the whole skip rule.  A skipped record's CIGAR is not read.
+ *   operations the record's own, or the first CG:B,I / B,i array behind a <l_seq>S<n>N placeholder, by the rule of gci_bam_cover_size.
+ *              A placeholder without a usable tag stays as it is: it holds no I or D and emits nothing.
+ *   at         of an operation: pos plus the lengths of all M, =, X, D and N operations in front of it in the record, in 64 bits.
+ *   L          the contig's length as the layout has it, capped at 0x7FFFFFFE (as the cover pass caps it); a d_ref_sel beyond the
+ *              layout: 0.
+ *   deletion   a D operation of length >= min_len with at < L: the interval [at, min(at + len, L) - 1], both ends inclusive.  One with
+ *              at >= L is not emitted and not counted.
+ *   insertion  an I operation of length >= min_len: its site is the reference base in front of the inserted bases (VCF's anchor), at - 1
+ *              if at > 0, else 0.  A site at or beyond L is not emitted and not counted.
+ *   otherwise  operations are never merged (5D5D is two deletions of 5); N consumes reference and is no event; P, S, H and operations
+ *              of length zero move nothing.  min_len < 1: GCI_E_INVALID.
+ *   *d_status  as gci_bam_cover_size reports it (smallest record index << 8 | -status, UINT64_MAX if none): GCI_E_MALFORMED for a
+ *              record that runs past the end of the stream or contradicts its block_size, and for operation codes 9 - 15 in a counted
+ *              record (they move nothing).
+ *   h_counts   host, 3 entries: the records counted, the deletions, the insertions.  The size call synchronises.
+ * gci_bam_indel_write emits gci_ivl{contig, start, end, 0}: the deletions to d_out[0 .. n_del), the insertions (start == end == site)
+ * to d_out[n_del .. n_del + n_ins), each half in (record, operation) order; the ranks come from exclusive scans, no atomics: two runs
+ * give the same bytes.  cap < n_del + n_ins: GCI_E_CAPACITY, nothing is written.  The size call's scratch stays in the context for it;
+ * another stream, n_bytes, offsets or n_rec than the size call in front of it on this context measured: GCI_E_INVALID.
+ * gci_depth_build with flank 0 over the first half gives the del track (per base the counted records that delete it with one long
+ * D), over the second half the ins track (per base the long insertions anchored there).  The depth of gci_bam_cover_size without
+ * count_del does not count a read over the bases it deletes: the reads that span a deleted base are depth + del.
+ *
+ * gci_indel_sites_size / _write: the runs of hot elements of two such tracks.
+ *   input      whole tracks of gci_layout_total() elements, 16-byte aligned (else GCI_E_INVALID); d_depth == NULL: the depth column is 0.
+ *   windows    as gci_clip_sites_size takes them: [begin, end) in flat track elements, clamped, sorted and disjoint (else
+ *              GCI_E_INVALID); n_windows == 0: every contig of the layout.
+ *   hot        an element with del >= min_reads or ins >= min_reads that lies inside a window and inside its contig (never in the
+ *              padding between contigs).  min_reads < 1: GCI_E_INVALID.
+ *   a site     a maximal run of consecutive hot elements of one contig inside one window (two touching windows cut a run in two):
+ *              contig, start and end (exclusive) as positions on the contig, and the maximum over the run of the del track, the ins
+ *              track and the depth track.  Sites come in ascending flat order.
+ *   write      the sites of the size call in front of it on this context (same tracks, min_reads and n_windows, nothing between the two
+ *              that sets windows: else GCI_E_INVALID) to d_out[0 .. *h_n_sites).  cap too small: GCI_E_CAPACITY, nothing is written.
+ * The size pass reads the del and ins tracks once, 16 bytes a lane, marks the run starts and leaves one count per 4096-element tile of
+ * the windows; the counts are scanned; the write pass stores the starts of the tiles that hold one by rank, and a wave per site walks
+ * the run to its end and takes the three maxima -- the depth track is read only there.  No global atomics. */
+typedef struct gci_indel_site {
+    int32_t contig;
+    int32_t start;
+    int32_t end;
+    int32_t del;
+    int32_t ins;
+    int32_t depth;
+} gci_indel_site;
+int gci_bam_indel_size(gci_ctx* ctx, const uint8_t* d_stream, uint64_t n_bytes, const uint64_t* d_rec_off, uint32_t n_rec, int has_seq,
+                       const int32_t* d_ref_sel, int32_t n_ref, uint32_t excl_flags, int min_mapq, int min_len, uint64_t* h_counts,
+                       uint64_t* d_status);
+int gci_bam_indel_write(gci_ctx* ctx, const uint8_t* d_stream, uint64_t n_bytes, const uint64_t* d_rec_off, uint32_t n_rec, int has_seq,
+                        gci_ivl* d_out, uint64_t cap, uint64_t* d_status);
+int gci_indel_sites_size(gci_ctx* ctx, const int32_t* d_del, const int32_t* d_ins, const int32_t* d_depth, int32_t min_reads,
+                         const gci_window* h_windows, uint32_t n_windows, uint64_t* h_n_sites);
+int gci_indel_sites_write(gci_ctx* ctx, const int32_t* d_del, const int32_t* d_ins, const int32_t* d_depth, int32_t min_reads,
+                          const gci_window* h_windows, uint32_t n_windows, gci_indel_site* d_out, uint64_t cap);
+
 /* Cross-rank name check for contig-sharded runs (exact).  gci_hash_bucket sorts the 64-bit name hashes of the
  * passing records into n_parts buckets by (hash >> 33) % n_parts; a bucket is part_cap + 1 uint64 words:
  * [0] = number of hashes the sender had for it (> part_cap: overflow), [1..] = the hashes.  After ONE all-to-all of
