@@ -7,10 +7,11 @@ import subprocess
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 LIB = os.path.join(CSRC, "libgci_hip.so")
-SOURCES = [os.path.join(CSRC, f) for f in ("api_ctx.hip", "k_filter.hip", "k_join.hip", "k_depth.hip", "k_track.hip", "k_bedgraph.hip", "k_hist.hip", "k_depth_parse.hip", "k_sdepth.hip", "k_deflate.hip", "k_depth_gz.hip", "k_paf.hip", "k_inflate.hip", "k_inflate_wave.hip", "k_records.hip", "k_pages.hip", "k_cover.hip", "k_fate.hip", "k_reads.hip", "k_sweep.hip", "k_clips.hip", "k_indels.hip", "k_shard.hip", "k_hbm.hip", "host_io.cpp", "staging.cpp")]
+SOURCES = [os.path.join(CSRC, f) for f in ("api_ctx.hip", "k_filter.hip", "k_join.hip", "k_depth.hip", "k_track.hip", "k_bedgraph.hip", "k_hist.hip", "k_depth_parse.hip", "k_sdepth.hip", "k_deflate.hip", "k_depth_gz.hip", "k_paf.hip", "k_inflate.hip", "k_inflate_wave.hip", "k_records.hip", "k_pages.hip", "k_cover.hip", "k_fate.hip", "k_reads.hip", "k_sweep.hip", "k_clips.hip", "k_indels.hip", "k_mismatch.hip", "k_shard.hip", "k_hbm.hip", "host_io.cpp", "staging.cpp")]
 DEPS = SOURCES + [os.path.join(CSRC, "gci_common.h"), os.path.join(CSRC, "gci_ctx.hpp"), os.path.join(CSRC, "gci_wave.hpp"),
                   os.path.join(CSRC, "gci_text_tiles.hpp"), os.path.join(CSRC, "gci_crc_gf2.hpp"), os.path.join(CSRC, "gci_deflate_codes.hpp"),
                   os.path.join(CSRC, "gci_cover_chunks.hpp"), os.path.join(CSRC, "gci_cigar_sums.hpp"), os.path.join(CSRC, "gci_ratio.hpp"),
+                  os.path.join(CSRC, "gci_site_tiles.hpp"),
                   os.path.join(_HERE, "..", "include", "gci_hip.h")]
 
 

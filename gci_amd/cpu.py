@@ -28,6 +28,7 @@ IVL_DTYPE = np.dtype([("contig", "<i4"), ("start", "<i4"), ("end", "<i4"), ("pad
 RUN_DTYPE = np.dtype([("start", "<u4"), ("depth", "<i4")])          # gci_depth_run
 SITE_DTYPE = np.dtype([("contig", "<i4"), ("pos", "<i4"), ("left", "<i4"), ("right", "<i4"), ("depth", "<i4"), ("pad", "<i4")])      # gci_clip_site
 INDEL_SITE_DTYPE = np.dtype([("contig", "<i4"), ("start", "<i4"), ("end", "<i4"), ("del", "<i4"), ("ins", "<i4"), ("depth", "<i4")])      # gci_indel_site
+MISMATCH_SITE_DTYPE = np.dtype([("contig", "<i4"), ("start", "<i4"), ("end", "<i4"), ("mismatch", "<i4"), ("depth", "<i4")])      # gci_mismatch_site
 GCI_TILE = 4096
 
 
@@ -45,7 +46,8 @@ gci_depth_sum gci_range_sums gci_depth_deflate_from_build gci_depth_deflate_size
 gci_depth_text_parse gci_sdepth_index gci_sdepth_parse gci_depth_gz_scan gci_depth_gz_runs gci_depth_gz_expand gci_depth_runs_count
 gci_depth_runs_write gci_bedgraph_size gci_bedgraph_write gci_depth_hist gci_bam_cover_size gci_bam_cover_write gci_track_add
 gci_bam_fate gci_bam_cover_size_sel gci_name_join_fate gci_fate_refine gci_bam_reads_size gci_bam_reads_write gci_bam_sweep gci_bam_clip_size gci_bam_clip_write gci_clip_sites_size gci_clip_sites_write
-gci_bam_indel_size gci_bam_indel_write gci_indel_sites_size gci_indel_sites_write""".split()
+gci_bam_indel_size gci_bam_indel_write gci_indel_sites_size gci_indel_sites_write
+gci_fasta_codes gci_bam_mismatch_size gci_bam_mismatch_write gci_mismatch_sites_size gci_mismatch_sites_write""".split()
 _PROTO = {name: (name, res, args) for name, res, args in _lib.EXPORTS}
 EXPORTS = [_PROTO[name] for name in _SEAMS] + [("gci_cpu_option", c_int, [c_void_p, c_char_p, c_int])]
 
@@ -338,6 +340,80 @@ class CpuEngine:
         if (out[total:] != -0x5A5A5A5B).any():
             raise CpuError(-1, "gci_indel_sites_write wrote behind its sites")
         return out.view(INDEL_SITE_DTYPE).reshape(-1)[:total]
+
+    # ---- mismatch_sites.py (k_mismatch.hip's twins)
+    def fasta_codes(self, text: np.ndarray, bodies: np.ndarray, dst: np.ndarray, codes: Optional[np.ndarray] = None,
+                    before_codes=None) -> Tuple[np.ndarray, np.ndarray]:
+        """device.Engine.fasta_codes's twin -> (the uint8 code array of the layout, the uint32 sequence-byte count of every 4096-byte tile).
+        codes: the array to write into (default: a new one filled with 15)."""
+        text = np.ascontiguousarray(text, dtype=np.uint8)
+        n = text.shape[0]
+        if text.ctypes.data & 15:                                              # (the call wants the text 16-byte aligned)
+            room = np.zeros(n + 16, dtype=np.uint8)
+            shift = (-room.ctypes.data) & 15
+            room[shift:shift + n] = text
+            text = room[shift:shift + n]
+        bodies = np.ascontiguousarray(bodies, dtype=np.int64).reshape(-1, 2)
+        dst = np.ascontiguousarray(dst, dtype=np.int64)
+        seq = np.zeros(n + 1, dtype=np.int64)                                  # gci_fasta_n_scan's tile counts: in a body, not dropped
+        for a, b in bodies.tolist():
+            seq[a] += 1
+            seq[min(b, n)] -= 1
+        is_seq = (np.cumsum(seq[:n]) > 0) & (text != 10) & (text != 13) & (text != 32)
+        kept = np.add.reduceat(is_seq.astype(np.uint32), np.arange(0, n, 4096)).astype(np.uint32) if n else np.zeros(0, dtype=np.uint32)
+        kept0 = np.concatenate(([0], np.cumsum(kept, dtype=np.uint64))).astype(np.uint64)
+        if before_codes is not None:
+            before_codes(kept)
+        if codes is None:
+            codes = np.full(max(self.total, 1), 15, dtype=np.uint8)
+        self._chk(self.lib.gci_fasta_codes(self.ctx, _p(text), n, _p(bodies), bodies.shape[0], _p(dst), _p(kept0), _p(codes)), "gci_fasta_codes")
+        return codes, kept
+
+    def sync(self) -> None:
+        pass
+
+    def bam_mismatch(self, stream: np.ndarray, offs: np.ndarray, ref_sel: np.ndarray, codes: np.ndarray, has_seq: bool = True, excl_flags: int = 0x704,
+                     min_mapq: int = 0, check: bool = True, cap: Optional[int] = None, guard: int = 0):
+        """device.Engine.bam_mismatch's twin -> (the events as IVL_DTYPE, [records counted, mismatches, pairs compared]).  cap, guard: as
+        bam_indel takes them."""
+        stream = np.ascontiguousarray(stream, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        ref_sel = np.ascontiguousarray(ref_sel, dtype=np.int32)
+        counts = np.zeros(3, dtype=np.uint64)
+        self.last_status = np.zeros(1, dtype=np.uint64)
+        self._chk(self.lib.gci_bam_mismatch_size(self.ctx, _p(stream), stream.shape[0], _p(offs), offs.shape[0], int(has_seq), _p(ref_sel),
+                                                 ref_sel.shape[0], int(excl_flags), int(min_mapq), _p(codes), _p(counts), _p(self.last_status)),
+                  "gci_bam_mismatch_size")
+        if check:
+            self._status(self.last_status, "gci_bam_mismatch_size")
+        n = int(counts[1])
+        room = n if cap is None else int(cap)
+        out = np.full((max(room, n) + guard + 1, 4), -0x5A5A5A5B, dtype=np.int32)
+        self.last_out = out
+        self._chk(self.lib.gci_bam_mismatch_write(self.ctx, _p(stream), stream.shape[0], _p(offs), offs.shape[0], int(has_seq), _p(codes), _p(out),
+                                                  room, _p(self.last_status)), "gci_bam_mismatch_write")
+        if (out[n:] != -0x5A5A5A5B).any():
+            raise CpuError(-1, "gci_bam_mismatch_write wrote behind its events")
+        return out.view(IVL_DTYPE).reshape(-1)[:n], [int(c) for c in counts]
+
+    def mismatch_sites(self, mismatch: np.ndarray, depth: np.ndarray, min_reads: int, frac_ppm: int, windows: Sequence[Tuple[int, int]] = (),
+                       cap: Optional[int] = None) -> np.ndarray:
+        """device.Engine.mismatch_sites's twin -> MISMATCH_SITE_DTYPE [n].  cap: the room offered to the write call."""
+        nw = len(windows)
+        w = (_Window * max(nw, 1))()
+        for i, (a, b) in enumerate(windows):
+            w[i].begin, w[i].end = int(a), int(b)
+        n = ctypes.c_uint64(0)
+        head = (self.ctx, _p(mismatch), _p(depth), int(min_reads), int(frac_ppm), w, nw)
+        self._chk(self.lib.gci_mismatch_sites_size(*head, ctypes.byref(n)), "gci_mismatch_sites_size")
+        total = int(n.value)
+        room = total if cap is None else int(cap)
+        out = np.full((max(room, total) + 1, 5), -0x5A5A5A5B, dtype=np.int32)
+        self.last_out = out
+        self._chk(self.lib.gci_mismatch_sites_write(*head, _p(out), room), "gci_mismatch_sites_write")
+        if (out[total:] != -0x5A5A5A5B).any():
+            raise CpuError(-1, "gci_mismatch_sites_write wrote behind its sites")
+        return out.view(MISMATCH_SITE_DTYPE).reshape(-1)[:total]
 
     def track_add(self, acc: np.ndarray, add: np.ndarray) -> np.ndarray:
         self._chk(self.lib.gci_track_add(self.ctx, _p(acc), _p(add)), "gci_track_add")

@@ -89,6 +89,22 @@ struct gci_ctx {
     const void* isites_depth = nullptr;
     int32_t isites_min_reads = 0;
     uint32_t isites_windows = 0;
+    // mismatch_sites.py: the events the last gci_bam_mismatch_size found, in record and position order, and the sites the last
+    // gci_mismatch_sites_size found, with what each call measured
+    std::vector<gci_ivl> mm_events;
+    uint64_t mm_status = ~0ull;
+    bool mm_valid = false;
+    uint32_t mm_n_rec = 0;
+    uint64_t mm_n_bytes = 0;
+    const void* mm_stream = nullptr;
+    const void* mm_off = nullptr;
+    const void* mm_codes = nullptr;
+    std::vector<gci_mismatch_site> msites;
+    bool msites_valid = false;
+    const void* msites_track = nullptr;
+    const void* msites_depth = nullptr;
+    int32_t msites_min_reads = 0, msites_frac = 0;
+    uint32_t msites_windows = 0;
 };
 
 namespace {
@@ -723,6 +739,7 @@ int gci_layout_set(gci_ctx* ctx, int32_t n_contigs, const int64_t* h_lengths)
     ctx->bg_track = nullptr; ctx->bg_text_run0 = nullptr;
     ctx->clip_valid = false; ctx->sites_valid = false;
     ctx->indel_valid = false; ctx->isites_valid = false;
+    ctx->mm_valid = false; ctx->msites_valid = false;
     return GCI_OK;
 }
 int64_t gci_layout_total(gci_ctx* ctx) { return ctx ? ctx->total : 0; }
@@ -1388,6 +1405,192 @@ int gci_indel_sites_write(gci_ctx* ctx, const int32_t* del, const int32_t* ins, 
     if (!ctx->isites.empty() && !out) return GCI_E_INVALID;
     if (cap < ctx->isites.size()) return GCI_E_CAPACITY;
     std::copy(ctx->isites.begin(), ctx->isites.end(), out);
+    return GCI_OK;
+}
+
+/* ---- mismatch_sites.py: bases where the reads carry another base than the assembly (k_mismatch.hip's twins, from the text of
+ * include/gci_hip.h: a byte, a record, a base, an element at a time) ---- */
+int gci_fasta_codes(gci_ctx* ctx, const uint8_t* text, uint64_t n_bytes, const int64_t* body, uint32_t n_records, const int64_t* dst,
+                    const uint64_t* tile_kept0, uint8_t* codes)
+{
+    if (!ctx || !codes || (n_bytes && (!text || !tile_kept0)) || (n_records && (!body || !dst))) return GCI_E_INVALID;
+    const int lst = need_layout(ctx);
+    if (lst) return lst;
+    if (((uintptr_t)text) & 15u) return GCI_E_INVALID;
+    static const char iupac[] = "=ACMGRSVTWYHKDBN";
+    for (uint32_t r = 0; r < n_records; r++) {
+        if (dst[r] < 0) continue;
+        const uint64_t a = (uint64_t)std::max<int64_t>(body[2 * r], 0), b = std::min<uint64_t>((uint64_t)std::max<int64_t>(body[2 * r + 1], 0), n_bytes);
+        uint64_t e = (uint64_t)dst[r];
+        for (uint64_t i = a; i < b; i++) {
+            uint8_t c = text[i];
+            if (c == '\n' || c == '\r' || c == ' ') continue;
+            if (c >= 'a' && c <= 'z') c = (uint8_t)(c - 'a' + 'A');
+            if (c == 'U') c = 'T';
+            uint8_t code = 15;
+            for (int k = 1; k < 16; k++) if (c == (uint8_t)iupac[k]) code = (uint8_t)k;
+            if (e < (uint64_t)ctx->total) codes[e] = code;
+            e++;
+        }
+    }
+    return GCI_OK;
+}
+
+int gci_bam_mismatch_size(gci_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, const uint64_t* rec_off, uint32_t n_rec, int has_seq, const int32_t* ref_sel,
+                          int32_t n_ref, uint32_t excl_flags, int min_mapq, const uint8_t* codes, uint64_t* h_counts, uint64_t* status)
+{
+    if (!ctx || !h_counts || !status || !codes || n_ref < 0 || has_seq != 1 || (n_rec && (!bam || !rec_off || !ref_sel))) return GCI_E_INVALID;
+    const int lst = need_layout(ctx);
+    if (lst) return lst;
+    ctx->mm_valid = false;
+    ctx->mm_events.clear();
+    uint64_t st = ~0ull, counted = 0, compared = 0;
+    for (uint32_t i = 0; i < n_rec; i++) {
+        const uint64_t off = rec_off[i];
+        const uint64_t word = ((uint64_t)i << 8) | (uint64_t)(uint8_t)(-GCI_E_MALFORMED);
+        if (off > n_bytes || n_bytes - off < 36) { st = std::min(st, word); continue; }
+        const uint8_t* p = bam + off;
+        const int32_t block_size = (int32_t)rd32(p), ref_id = (int32_t)rd32(p + 4), pos = (int32_t)rd32(p + 8);
+        const uint32_t l_read_name = p[12], n_cigar = rd16(p + 16), flag = rd16(p + 18);
+        const int mapq = p[13];
+        const int32_t l_seq = (int32_t)rd32(p + 20);
+        const uint64_t rec_end = off + 4 + (uint64_t)(uint32_t)block_size;
+        const uint64_t cig_off = off + 36 + l_read_name;
+        const uint64_t aux_off = cig_off + 4ull * n_cigar + (((uint64_t)(uint32_t)l_seq + 1) >> 1) + (uint64_t)(uint32_t)l_seq;
+        if (block_size < 32 || rec_end > n_bytes || l_seq < 0 || aux_off > rec_end) { st = std::min(st, word); continue; }
+        if ((flag & excl_flags) || mapq < min_mapq || ref_id < 0 || ref_id >= n_ref || pos < 0 || ref_sel[ref_id] < 0) continue;      // skipped
+        counted++;
+        const uint8_t* ops = bam + cig_off;
+        const uint8_t* seq = ops + 4ull * n_cigar;                              // behind the in-record words, also in the CG case
+        uint64_t n = n_cigar;
+        if (n > 0 && (rd32(ops) & 0xFu) == 4u && (rd32(ops) >> 4) == (uint32_t)l_seq) {
+            const uint8_t* end = bam + rec_end;
+            for (const uint8_t* q = bam + aux_off; q + 3 <= end;) {
+                const int64_t sz = aux_value_size(q + 3, end, q[2]);
+                if (sz < 0 || q + 3 + sz > end) break;
+                if (q[0] == 'C' && q[1] == 'G') {
+                    if (q[2] == 'B' && (q[3] == 'I' || q[3] == 'i')) {
+                        const uint32_t cg_len = rd32(q + 4);
+                        if (cg_len >= n_cigar && cg_len < (1u << 29)) { ops = q + 8; n = cg_len; }
+                    }
+                    break;
+                }
+                q += 3 + sz;
+            }
+        }
+        // first pass: codes 9 - 15 and the query length
+        bool bad = false;
+        uint64_t qlen = 0;
+        for (uint64_t k = 0; k < n; k++) {
+            const uint32_t w = rd32(ops + 4 * k), op = w & 0xFu;
+            if (op >= 9u) bad = true;
+            if (op == 0u || op == 1u || op == 4u || op == 7u || op == 8u) qlen += w >> 4;          // M I S = X
+        }
+        if (l_seq > 0 && qlen != (uint64_t)l_seq) bad = true;
+        if (bad) st = std::min(st, word);
+        if (l_seq == 0 || qlen != (uint64_t)l_seq) continue;                    // nothing of it is compared
+        const int32_t contig = ref_sel[ref_id];
+        const uint64_t L = contig < ctx->n_contigs ? std::min<uint64_t>((uint64_t)ctx->len[(size_t)contig], 0x7FFFFFFEull) : 0;
+        const uint8_t* ref = L ? codes + ctx->off[(size_t)contig] : codes;
+        uint64_t at = (uint64_t)pos, q = 0;
+        for (uint64_t k = 0; k < n && at < L; k++) {
+            const uint32_t w = rd32(ops + 4 * k), op = w & 0xFu;
+            const uint64_t len = w >> 4;
+            if (op == 0u || op == 7u || op == 8u) {
+                for (uint64_t j = 0; j < len && at + j < L; j++) {
+                    const uint32_t sb = seq[(q + j) >> 1], nib = ((q + j) & 1u) ? (sb & 15u) : (sb >> 4), rc = ref[at + j];
+                    const bool rb = rc == 1 || rc == 2 || rc == 4 || rc == 8, qb = nib == 1 || nib == 2 || nib == 4 || nib == 8;
+                    if (!rb || !qb) continue;
+                    compared++;
+                    if (rc != nib) ctx->mm_events.push_back(gci_ivl{contig, (int32_t)(at + j), (int32_t)(at + j), 0});
+                }
+            }
+            if (op == 0u || op == 2u || op == 3u || op == 7u || op == 8u) at += len;              // M D N = X
+            if (op == 0u || op == 1u || op == 4u || op == 7u || op == 8u) q += len;               // M I S = X
+        }
+    }
+    ctx->mm_status = st;
+    ctx->mm_valid = true; ctx->mm_n_rec = n_rec; ctx->mm_n_bytes = n_bytes; ctx->mm_stream = bam; ctx->mm_off = rec_off; ctx->mm_codes = codes;
+    h_counts[0] = counted; h_counts[1] = ctx->mm_events.size(); h_counts[2] = compared;
+    *status = st;
+    return GCI_OK;
+}
+
+int gci_bam_mismatch_write(gci_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, const uint64_t* rec_off, uint32_t n_rec, int has_seq, const uint8_t* codes,
+                           gci_ivl* out, uint64_t cap, uint64_t* status)
+{
+    if (!ctx || !status || !codes || has_seq != 1 || (n_rec && (!bam || !rec_off))) return GCI_E_INVALID;
+    const int lst = need_layout(ctx);
+    if (lst) return lst;
+    if (!ctx->mm_valid || ctx->mm_n_rec != n_rec || ctx->mm_n_bytes != n_bytes || bam != ctx->mm_stream || rec_off != ctx->mm_off || codes != ctx->mm_codes)
+        return GCI_E_INVALID;
+    const uint64_t total = ctx->mm_events.size();
+    if (total && !out) return GCI_E_INVALID;
+    if (cap < total) return GCI_E_CAPACITY;
+    std::copy(ctx->mm_events.begin(), ctx->mm_events.end(), out);
+    *status = ctx->mm_status;
+    return GCI_OK;
+}
+
+int gci_mismatch_sites_size(gci_ctx* ctx, const int32_t* mm, const int32_t* depth, int32_t min_reads, int32_t frac_ppm, const gci_window* h_windows,
+                            uint32_t n_windows, uint64_t* h_n_sites)
+{
+    if (!ctx || !mm || !depth || !h_n_sites || min_reads < 1 || frac_ppm < 0 || frac_ppm > 1000000 || (n_windows && !h_windows)) return GCI_E_INVALID;
+    const int lst = need_layout(ctx);
+    if (lst) return lst;
+    if ((((uintptr_t)mm) | ((uintptr_t)depth)) & 15u) return GCI_E_INVALID;
+    ctx->msites_valid = false;
+    *h_n_sites = 0;
+    std::vector<gci_window> ws;
+    if (n_windows == 0) {
+        for (int32_t c = 0; c < ctx->n_contigs; c++) ws.push_back(gci_window{ctx->off[(size_t)c], ctx->off[(size_t)c] + ctx->len[(size_t)c]});
+    } else {
+        int64_t at = 0;
+        for (uint32_t i = 0; i < n_windows; i++) {
+            gci_window w = h_windows[i];
+            w.begin = std::max<int64_t>(w.begin, 0);
+            w.end = std::max(std::min(w.end, ctx->total), w.begin);
+            if (w.begin < at) return GCI_E_INVALID;                        // not sorted and disjoint
+            at = w.end;
+            ws.push_back(w);
+        }
+    }
+    ctx->msites.clear();
+    for (const gci_window& w : ws) {
+        bool open = false;                                                  // a run never crosses from one window into the next
+        for (int64_t p = w.begin; p < w.end; p++) {
+            const int32_t c = (int32_t)(std::upper_bound(ctx->off.begin(), ctx->off.end(), p) - ctx->off.begin()) - 1;
+            const int64_t pos = p - ctx->off[(size_t)c];
+            const bool hot = pos < ctx->len[(size_t)c] && mm[p] >= min_reads && (int64_t)mm[p] * 1000000ll >= (int64_t)frac_ppm * (int64_t)depth[p];
+            if (open && (!hot || pos == 0)) open = false;                   // ... nor from one contig into the next
+            if (!hot) continue;
+            if (!open) {
+                ctx->msites.push_back(gci_mismatch_site{c, (int32_t)pos, (int32_t)pos, mm[p], depth[p]});
+                open = true;
+            }
+            gci_mismatch_site& s = ctx->msites.back();
+            s.end = (int32_t)pos + 1;
+            if (mm[p] > s.mismatch) { s.mismatch = mm[p]; s.depth = depth[p]; }   // the first base that reaches the maximum
+        }
+    }
+    ctx->msites_valid = true; ctx->msites_track = mm; ctx->msites_depth = depth;
+    ctx->msites_min_reads = min_reads; ctx->msites_frac = frac_ppm; ctx->msites_windows = n_windows;
+    *h_n_sites = ctx->msites.size();
+    return GCI_OK;
+}
+
+int gci_mismatch_sites_write(gci_ctx* ctx, const int32_t* mm, const int32_t* depth, int32_t min_reads, int32_t frac_ppm, const gci_window* h_windows,
+                             uint32_t n_windows, gci_mismatch_site* out, uint64_t cap)
+{
+    if (!ctx || !mm || !depth || min_reads < 1 || (n_windows && !h_windows)) return GCI_E_INVALID;
+    const int lst = need_layout(ctx);
+    if (lst) return lst;
+    if (!ctx->msites_valid || mm != ctx->msites_track || depth != ctx->msites_depth || min_reads != ctx->msites_min_reads || frac_ppm != ctx->msites_frac ||
+        n_windows != ctx->msites_windows)
+        return GCI_E_INVALID;
+    if (!ctx->msites.empty() && !out) return GCI_E_INVALID;
+    if (cap < ctx->msites.size()) return GCI_E_CAPACITY;
+    std::copy(ctx->msites.begin(), ctx->msites.end(), out);
     return GCI_OK;
 }
 

@@ -1,8 +1,9 @@
 // gci_cover_chunks.hpp -- the CIGAR of a BAM stream as CHUNKS of at most GCI_COVER_CHUNK_OPS operations, one wave each: what the
 // kernels that walk whole CIGARs share (k_cover.hip: the covered bases; k_fate.hip: the base totals of the record filter's two
-// quotients).  A lane per record says where the record's operations lie and how many chunks they make (CoverRec), an exclusive scan
-// of the chunk counts numbers the chunks, and a wave finds its record (cv_rec_of_chunk), its piece of the operation array
-// (cv_chunk_of) and its operation words, 64 a round (cv_op_word).
+// quotients; k_indels.hip, k_mismatch.hip: the events of a walk, with cv_parse_counted as their one record parse).  A lane per
+// record says where the record's operations lie and how many chunks they make (CoverRec), an exclusive scan of the chunk counts
+// numbers the chunks, and a wave finds its record (cv_rec_of_chunk), its piece of the operation array (cv_chunk_of) and its
+// operation words, 64 a round (cv_op_word).
 //
 // CIGAR words lie at any byte phase of the stream: a lane loads the naturally aligned dword its operation begins in, takes the next
 // one from its neighbour lane and re-aligns the two in registers (v_alignbyte), as k_cigar_chunks and pg_src_dword do.
@@ -49,6 +50,71 @@ __device__ __forceinline__ int64_t cv_aux_size(const uint8_t* p, const uint8_t* 
     }
     default: return -1;
     }
+}
+
+// where a record's SEQ lies: behind its in-record CIGAR words, also when the operations come from a CG array (k_mismatch.hip)
+struct CvSeq {
+    uint64_t seq_off;
+    uint32_t l_seq;
+    uint32_t pad;
+};
+
+// One lane per record, what k_indel_parse and k_mm_parse share: bounds, core fields, the skip rule of gci_bam_cover_size, where the
+// operations lie (own CIGAR or the first CG:B,I / B,i array behind a <l_seq>S<n>N placeholder) and how many chunks they make.
+// contig >= 0: the record is counted, with or without operations.  A record out of bounds is reported and makes no chunk.
+__device__ __forceinline__ CoverRec cv_parse_counted(const uint8_t* __restrict__ bam, uint64_t n_bytes, uint64_t off, uint32_t i, int has_seq,
+                                                     const int32_t* __restrict__ ref_sel, int32_t n_ref, uint32_t excl_flags, int min_mapq,
+                                                     unsigned long long* __restrict__ status, uint32_t& chunks, CvSeq& sq)
+{
+    CoverRec r;
+    r.ops_off = 0; r.n_ops = 0; r.contig = -1; r.pos = 0; r.pad = 0;
+    sq.seq_off = 0; sq.l_seq = 0; sq.pad = 0;
+    chunks = 0;
+    if (off > n_bytes || n_bytes - off < 36) {
+        cv_report(status, i, GCI_E_MALFORMED);
+    } else {
+        const uint8_t* p = bam + off;
+        const int32_t block_size = (int32_t)cv_rd32(p), ref_id = (int32_t)cv_rd32(p + 4), pos = (int32_t)cv_rd32(p + 8);
+        const uint32_t l_read_name = p[12];
+        const int mapq = p[13];
+        const uint32_t n_cigar = cv_rd16(p + 16), flag = cv_rd16(p + 18);
+        const int32_t l_seq = (int32_t)cv_rd32(p + 20);
+        const uint64_t rec_end = off + 4 + (uint64_t)(uint32_t)block_size;
+        const uint64_t cig_off = off + 36 + l_read_name;
+        const uint64_t aux_off = cig_off + 4ull * n_cigar + (has_seq ? (((uint64_t)(uint32_t)l_seq + 1) >> 1) + (uint64_t)(uint32_t)l_seq : 0ull);
+        if (block_size < 32 || rec_end > n_bytes || l_seq < 0 || aux_off > rec_end) {
+            cv_report(status, i, GCI_E_MALFORMED);
+        } else if (!(flag & excl_flags) && mapq >= min_mapq && ref_id >= 0 && ref_id < n_ref && pos >= 0 && ref_sel[ref_id] >= 0) {
+            r.contig = ref_sel[ref_id];                // (>= 0: the record is counted, with or without operations)
+            r.pos = pos;
+            r.ops_off = cig_off;
+            r.n_ops = n_cigar;
+            sq.seq_off = cig_off + 4ull * n_cigar;     // (with has_seq its (l_seq + 1) / 2 bytes end at or before aux_off <= rec_end)
+            sq.l_seq = (uint32_t)l_seq;
+            // <l_seq>S in front: the operations are the first CG:B,I (or B,i) array, as k_cover_parse walks to it; without a usable one
+            // the placeholder's own S and N stay
+            if (n_cigar > 0) {
+                const uint32_t op0 = cv_rd32(bam + cig_off);
+                if ((op0 & 0xFu) == 4u && (op0 >> 4) == (uint32_t)l_seq) {
+                    const uint8_t* end = bam + rec_end;
+                    for (const uint8_t* q = bam + aux_off; q + 3 <= end;) {
+                        const int64_t sz = cv_aux_size(q + 3, end, q[2]);
+                        if (sz < 0 || q + 3 + sz > end) break;
+                        if (q[0] == 'C' && q[1] == 'G') {
+                            if (q[2] == 'B' && (q[3] == 'I' || q[3] == 'i')) {
+                                const uint32_t cg_len = cv_rd32(q + 4);
+                                if (cg_len >= n_cigar && cg_len < (1u << 29)) { r.ops_off = (uint64_t)(q + 8 - bam); r.n_ops = cg_len; }
+                            }
+                            break;
+                        }
+                        q += 3 + sz;
+                    }
+                }
+            }
+            chunks = (r.n_ops + CV_OPS - 1) / CV_OPS;    // (every operation word lies inside the record: aux_off <= rec_end, q + 3 + sz <= end)
+        }
+    }
+    return r;
 }
 
 // the record of chunk c: the largest i with chunk0[i] <= c (records without chunks share their value with the record behind them)

@@ -180,6 +180,21 @@ struct gci_ctx {
     const void* indel_sites_depth = nullptr;
     int32_t indel_sites_min_reads = 0;
     uint32_t indel_sites_windows = 0;
+    // k_mismatch.hip: the records' ranks of gci_fasta_codes; what gci_bam_mismatch_size keeps for gci_bam_mismatch_write -- per record
+    // (parse, SEQ, chunk counts, counted) and per chunk (base sums, the two lengths, mismatches, pairs and their scans) --, and what
+    // gci_mismatch_sites_size keeps for gci_mismatch_sites_write
+    DevBuf mm_fasta, mm_rec, mm_chunk, mm_tiles;
+    bool mm_valid = false;
+    uint32_t mm_n_rec = 0;
+    uint64_t mm_n_bytes = 0, mm_n_chunks = 0, mm_n_mm = 0;
+    const void* mm_stream = nullptr;
+    const void* mm_off = nullptr;
+    const void* mm_codes = nullptr;
+    uint64_t mm_sites_epoch = 0, mm_sites_total = 0;          // (epoch 0: no size call yet)
+    const void* mm_sites_track = nullptr;
+    const void* mm_sites_depth = nullptr;
+    int32_t mm_sites_min_reads = 0, mm_sites_frac = 0;
+    uint32_t mm_sites_windows = 0;
     void* h_pinned = nullptr;               // staging for small uploads
     size_t h_pinned_cap = 0;
     // optional per-kernel HIP-event timing (gci_profile_*)

@@ -25,6 +25,7 @@
 //   k_indel_site_finish   one wave per site: walks forward from the start, 64 elements a round, to the first element that is not hot
 //                         or the end of the window or contig; the maxima of the three tracks; the depth track is read here only
 #include "gci_cigar_sums.hpp"
+#include "gci_site_tiles.hpp"
 
 struct IndelRecScratch {                 // carved out of ctx->indel_rec
     unsigned long long* status;
@@ -100,52 +101,9 @@ __global__ __launch_bounds__(BLOCK) void k_indel_parse(const uint8_t* __restrict
 {
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n_rec) return;
-    CoverRec r;
-    r.ops_off = 0; r.n_ops = 0; r.contig = -1; r.pos = 0; r.pad = 0;
-    uint32_t chunks = 0;
-    const uint64_t off = rec_off[i];
-    if (off > n_bytes || n_bytes - off < 36) {
-        cv_report(status, i, GCI_E_MALFORMED);
-    } else {
-        const uint8_t* p = bam + off;
-        const int32_t block_size = (int32_t)cv_rd32(p), ref_id = (int32_t)cv_rd32(p + 4), pos = (int32_t)cv_rd32(p + 8);
-        const uint32_t l_read_name = p[12];
-        const int mapq = p[13];
-        const uint32_t n_cigar = cv_rd16(p + 16), flag = cv_rd16(p + 18);
-        const int32_t l_seq = (int32_t)cv_rd32(p + 20);
-        const uint64_t rec_end = off + 4 + (uint64_t)(uint32_t)block_size;
-        const uint64_t cig_off = off + 36 + l_read_name;
-        const uint64_t aux_off = cig_off + 4ull * n_cigar + (has_seq ? (((uint64_t)(uint32_t)l_seq + 1) >> 1) + (uint64_t)(uint32_t)l_seq : 0ull);
-        if (block_size < 32 || rec_end > n_bytes || l_seq < 0 || aux_off > rec_end) {
-            cv_report(status, i, GCI_E_MALFORMED);
-        } else if (!(flag & excl_flags) && mapq >= min_mapq && ref_id >= 0 && ref_id < n_ref && pos >= 0 && ref_sel[ref_id] >= 0) {
-            r.contig = ref_sel[ref_id];                // (>= 0: the record is counted, with or without operations)
-            r.pos = pos;
-            r.ops_off = cig_off;
-            r.n_ops = n_cigar;
-            // <l_seq>S in front: the operations are the first CG:B,I (or B,i) array, as k_cover_parse walks to it; without a usable one
-            // the placeholder's own S and N stay, which hold no event
-            if (n_cigar > 0) {
-                const uint32_t op0 = cv_rd32(bam + cig_off);
-                if ((op0 & 0xFu) == 4u && (op0 >> 4) == (uint32_t)l_seq) {
-                    const uint8_t* end = bam + rec_end;
-                    for (const uint8_t* q = bam + aux_off; q + 3 <= end;) {
-                        const int64_t sz = cv_aux_size(q + 3, end, q[2]);
-                        if (sz < 0 || q + 3 + sz > end) break;
-                        if (q[0] == 'C' && q[1] == 'G') {
-                            if (q[2] == 'B' && (q[3] == 'I' || q[3] == 'i')) {
-                                const uint32_t cg_len = cv_rd32(q + 4);
-                                if (cg_len >= n_cigar && cg_len < (1u << 29)) { r.ops_off = (uint64_t)(q + 8 - bam); r.n_ops = cg_len; }
-                            }
-                            break;
-                        }
-                        q += 3 + sz;
-                    }
-                }
-            }
-            chunks = (r.n_ops + CV_OPS - 1) / CV_OPS;    // (every operation word lies inside the record: aux_off <= rec_end, q + 3 + sz <= end)
-        }
-    }
+    CvSeq q;
+    uint32_t chunks;
+    const CoverRec r = cv_parse_counted(bam, n_bytes, rec_off[i], i, has_seq, ref_sel, n_ref, excl_flags, min_mapq, status, chunks, q);
     recs[i] = r;
     nch[i] = chunks;
 }
@@ -344,34 +302,9 @@ extern "C" int gci_bam_indel_write(gci_ctx* ctx, const uint8_t* d_stream, uint64
 }
 
 // ---- the track side ---------------------------------------------------------------------------------------------------------------
-struct IndelTile {
-    int64_t p0;                          // the tile's first element (a multiple of TILE)
-    int64_t lo, hi;                      // the elements of the tile that are inside the window AND inside their contig
-    int64_t run_lo, run_hi;              // ... of the whole track: where a run of this tile may begin and must end
-    int64_t contig_off;
-    int32_t contig;
-};
-
-__device__ __forceinline__ IndelTile indel_tile_of(const gci_window* __restrict__ win, const int64_t* __restrict__ win_tile_first, int32_t n_win,
-                                                   int64_t wt, const int64_t* __restrict__ off, const int64_t* __restrict__ len,
-                                                   const int64_t* __restrict__ tile_first, int32_t n_contigs)
-{
-    IndelTile x;
-    const int32_t w = contig_of_tile(win_tile_first, n_win, wt);
-    const gci_window W = win[w];
-    x.p0 = (W.begin / TILE + (wt - win_tile_first[w])) * TILE;
-    x.contig = contig_of_tile(tile_first, n_contigs, x.p0 / TILE);
-    x.contig_off = off[x.contig];
-    x.run_lo = max(W.begin, x.contig_off);
-    x.run_hi = min(W.end, x.contig_off + len[x.contig]);
-    x.lo = max(x.p0, x.run_lo);
-    x.hi = min(x.p0 + TILE, x.run_hi);
-    return x;
-}
-
 // whether the element in front of q is hot AND of the same window and contig -- for the first element of a wave's stretch, which no
 // neighbour lane holds; q - 1 may lie in the tile in front
-__device__ __forceinline__ bool indel_prev_hot(const int32_t* __restrict__ del, const int32_t* __restrict__ ins, const IndelTile& x, int64_t q,
+__device__ __forceinline__ bool indel_prev_hot(const int32_t* __restrict__ del, const int32_t* __restrict__ ins, const SiteTile& x, int64_t q,
                                                int32_t min_reads)
 {
     if (q - 1 < x.run_lo || q - 1 >= x.run_hi) return false;
@@ -386,7 +319,7 @@ __global__ __launch_bounds__(BLOCK) void k_indel_sites_count(const int32_t* __re
 {
     __shared__ uint32_t part[BLOCK / 64];
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const IndelTile x = indel_tile_of(win, win_tile_first, n_win, blockIdx.x, off, len, tile_first, n_contigs);
+    const SiteTile x = site_tile_of(win, win_tile_first, n_win, blockIdx.x, off, len, tile_first, n_contigs);
     uint32_t n = 0;
 #pragma unroll
     for (int j = 0; j < 4; j++) {
@@ -422,7 +355,7 @@ __global__ __launch_bounds__(BLOCK) void k_indel_sites_write(const int32_t* __re
     __shared__ uint32_t wtot[BLOCK / 64];
     if (tile_cnt[blockIdx.x] == 0) return;             // (the whole workgroup)
     const int t = threadIdx.x, lane = t & 63;
-    const IndelTile x = indel_tile_of(win, win_tile_first, n_win, blockIdx.x, off, len, tile_first, n_contigs);
+    const SiteTile x = site_tile_of(win, win_tile_first, n_win, blockIdx.x, off, len, tile_first, n_contigs);
     const int64_t p = x.p0 + (int64_t)t * 16;          // a thread's 16 consecutive elements: ascending order is thread order
     uint32_t hot = 0;
 #pragma unroll

@@ -1,0 +1,691 @@
+// k_mismatch.hip -- mismatch_sites.py: bases where the reads carry another base than the assembly.  gci_fasta_codes turns the FASTA
+// bytes into one 4-bit code per base in the track layout; gci_bam_mismatch_size / _write walk every counted record's CIGAR with a
+// reference AND a query position, compare the SEQ nibble with the assembly's code under M / = / X and turn every mismatch into an
+// EVENT of one base for the depth build; gci_mismatch_sites_size / _write list the RUNS of bases where the built track is hot
+// against the depth track (include/gci_hip.h states all three).
+//
+// The FASTA side.  Tiles of 4096 bytes, a lane 16 consecutive bytes (gci_text_tiles.hpp); a sequence byte is gci_fasta_n_scan's.
+//   k_fasta_rec_rank  one lane per record: the sequence bytes of the file in front of its body -- the scanned count of its tile plus
+//                     the sequence bytes of that tile in front of the body
+//   k_fasta_codes     one workgroup per tile: a workgroup scan of the lanes' sequence bytes ranks every byte in the file, minus its
+//                     record's rank that is its position, and d_dst[record] + position is the one byte it stores
+//
+// The record side.  Input and chunks as k_indels.hip (gci_cover_chunks.hpp, gci_cigar_sums.hpp).
+//   k_mm_parse    one lane per record: cv_parse_counted, and where SEQ lies and how long it is
+//   k_cigar_sums  one wave per chunk
+//   k_mm_lens     one lane per chunk: its reference length M + D + N and its query length S + M + I -- scanned, the two carries
+//   k_mm_count    one wave per chunk, 64 operations a round: wave scans of the reference, query and match lengths place every
+//                 operation on both axes; the round's MATCH BASES are then dealt to the lanes by base, MM_BASES consecutive ones a
+//                 lane, 64 * MM_BASES a step, and a lane finds the operation of its first base by a search over the 64 scanned match
+//                 lengths in LDS -- a record of 15-base operations fills the wave as one of 15,000-base operations does
+//   k_mm_finish   one lane per record: codes 9 - 15 and S + M + I != l_seq into the status word, whether the record is counted
+//   k_mm_write    the same walk; a lane's slot is its chunk's offset + the mismatches of earlier steps + those of the lanes below it
+//                 (ballots and popcounts), so events come in (record, reference position) order
+// A record whose S + M + I is not l_seq is never walked: no SEQ byte beyond (l_seq + 1) / 2 is ever read.  The only global atomic
+// is the status word's atomicMin.
+//
+// The track side.  Windows and tiles as k_indels.hip (gci_site_tiles.hpp); hot = mismatch >= min_reads and
+// mismatch * 1000000 >= frac_ppm * depth in 64 bits; the depth track is read in every pass.
+#include "gci_cigar_sums.hpp"
+#include "gci_site_tiles.hpp"
+#include "gci_text_tiles.hpp"
+
+#ifndef MM_BASES
+#define MM_BASES 4                       // consecutive match bases a lane takes in one step (1, 4 and 8 measured)
+#endif
+
+// ---- the FASTA side ---------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool mm_fasta_dropped(uint8_t c) { return c == '\n' || c == '\r' || c == ' '; }
+
+// BAM's 4-bit code ("=ACMGRSVTWYHKDBN") of a FASTA byte, case-insensitive; U is T; anything that is no IUPAC letter is 15
+__device__ __forceinline__ uint8_t mm_fasta_code(uint8_t c)
+{
+    const uint32_t l = c | 0x20u;
+    if (l < 'a' || l > 'z') return 15;
+    const uint32_t k = c & 0x1Fu;                      // A = 1 .. Z = 26
+    const unsigned long long tab = k < 16u ? 0xFF3FCFFB4FFD2E1Full : 0xFFFFFFAF978865FFull;
+    return (uint8_t)((tab >> (4u * (k & 15u))) & 15u);
+}
+
+// the record whose body holds byte i, or -1 (a title line, in front of the first record): steps back from the candidate
+__device__ __forceinline__ int64_t mm_record_of(const int64_t* __restrict__ body, int64_t cand, uint64_t i)
+{
+    while (cand >= 0 && (uint64_t)body[2 * cand] > i) cand--;
+    if (cand < 0 || i >= (uint64_t)body[2 * cand + 1]) return -1;
+    return cand;
+}
+
+__global__ __launch_bounds__(BLOCK) void k_fasta_rec_rank(const uint8_t* __restrict__ text, uint64_t n_bytes, const int64_t* __restrict__ body,
+                                                          uint32_t n_records, const unsigned long long* __restrict__ tile_kept0,
+                                                          unsigned long long* __restrict__ rec_rank)
+{
+    const uint32_t r = blockIdx.x * BLOCK + threadIdx.x;
+    if (r >= n_records) return;
+    uint64_t b = (uint64_t)(body[2 * r] < 0 ? 0 : body[2 * r]);
+    if (b > n_bytes) b = n_bytes;
+    const uint64_t tile0 = b / TEXT_TILE * TEXT_TILE;
+    unsigned long long rank = tile_kept0[b / TEXT_TILE];                 // (tiles + 1 entries: b == n_bytes may be the end of the last tile)
+    for (int64_t q = (int64_t)r - 1; q >= 0 && (uint64_t)body[2 * q + 1] > tile0; q--) {
+        const uint64_t lo = (uint64_t)body[2 * q] > tile0 ? (uint64_t)body[2 * q] : tile0;
+        const uint64_t hi = (uint64_t)body[2 * q + 1] < b ? (uint64_t)body[2 * q + 1] : b;
+        for (uint64_t i = lo; i < hi; i++) rank += mm_fasta_dropped(text[i]) ? 0u : 1u;
+    }
+    rec_rank[r] = rank;
+}
+
+__global__ __launch_bounds__(TEXT_BLOCK) void k_fasta_codes(const uint8_t* __restrict__ text, uint64_t n_bytes, const int64_t* __restrict__ body,
+                                                            uint32_t n_records, const int64_t* __restrict__ dst,
+                                                            const unsigned long long* __restrict__ tile_kept0,
+                                                            const unsigned long long* __restrict__ rec_rank, uint8_t* __restrict__ codes,
+                                                            int64_t total)
+{
+    __shared__ uint32_t wtot[TEXT_BLOCK / 64];
+    const int t = threadIdx.x;
+    const uint64_t tile0 = (uint64_t)blockIdx.x * TEXT_TILE, at = tile0 + 16u * t;
+    // the last record whose body begins at or before this lane's last byte (bodies are sorted and disjoint)
+    uint32_t lo = 0, hi = n_records;
+    while (lo < hi) { const uint32_t mid = (lo + hi) >> 1; if ((uint64_t)body[2 * mid] < at + 16) lo = mid + 1; else hi = mid; }
+    const int64_t cand = (int64_t)lo - 1;
+    const uint4 v = load16(text, n_bytes, (int64_t)at);
+    union { uint4 v; uint8_t b[16]; } u;
+    u.v = v;
+    uint32_t keep = 0;
+    int64_t rec[16];
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+        rec[k] = at + k < n_bytes ? mm_record_of(body, cand, at + k) : -1;
+        keep |= (rec[k] >= 0 && !mm_fasta_dropped(u.b[k])) ? (1u << k) : 0u;
+    }
+    uint32_t all;
+    const uint32_t pre = block_exclusive<uint32_t, TEXT_BLOCK / 64>((uint32_t)__builtin_popcount(keep), wtot, all);
+    unsigned long long g = tile_kept0[blockIdx.x] + pre;                 // the rank in the file of this lane's next sequence byte
+#pragma unroll
+    for (int k = 0; k < 16; k++) {
+        if (!((keep >> k) & 1u)) continue;
+        const int64_t d = dst[rec[k]];
+        if (d >= 0) {
+            const unsigned long long e = (unsigned long long)d + (g - rec_rank[rec[k]]);
+            if (e < (unsigned long long)total) codes[e] = mm_fasta_code(u.b[k]);
+        }
+        g++;
+    }
+}
+
+extern "C" int gci_fasta_codes(gci_ctx* ctx, const uint8_t* d_text, uint64_t n_bytes, const int64_t* d_body, uint32_t n_records, const int64_t* d_dst,
+                               const uint64_t* d_tile_kept0, uint8_t* d_codes)
+{
+    if (!ctx || !d_codes || (n_bytes && (!d_text || !d_tile_kept0)) || (n_records && (!d_body || !d_dst))) return GCI_E_INVALID;
+    if (!ctx->n_contigs) return GCI_E_NO_LAYOUT;
+    if (((uintptr_t)d_text) & 15u) return GCI_E_INVALID;
+    if (!n_bytes || !n_records) return GCI_OK;
+    const int64_t tiles = text_tiles(n_bytes, false);
+    if (tiles < 0) return GCI_E_INVALID;
+    GCI_TRY(gci_ensure(ctx, ctx->mm_fasta, 8 * (size_t)n_records));
+    unsigned long long* rank = (unsigned long long*)ctx->mm_fasta.p;
+    hipLaunchKernelGGL(k_fasta_rec_rank, dim3((n_records + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, ctx->stream, d_text, n_bytes, d_body, n_records,
+                       (const unsigned long long*)d_tile_kept0, rank);
+    LAUNCHCHK("k_fasta_rec_rank");
+    hipLaunchKernelGGL(k_fasta_codes, dim3((uint32_t)tiles), dim3(TEXT_BLOCK), 0, ctx->stream, d_text, n_bytes, d_body, n_records, d_dst,
+                       (const unsigned long long*)d_tile_kept0, rank, d_codes, ctx->total);
+    LAUNCHCHK("k_fasta_codes");
+    return GCI_OK;
+}
+
+// ---- the record side ----------------------------------------------------------------------------------------------------------------
+struct MmRecScratch {                    // carved out of ctx->mm_rec
+    unsigned long long* status;
+    unsigned long long* chunk0;          // n_rec + 1: exclusive scan of the chunk counts
+    unsigned long long* cnt0;            // n_rec + 1: exclusive scan of `counted`
+    CoverRec* recs;
+    CvSeq* seqs;
+    unsigned long long* blk;
+    uint32_t* nch;
+    uint32_t* counted;
+};
+
+struct MmChunkScratch {                  // carved out of ctx->mm_chunk
+    CigarSums* sums;
+    unsigned long long* ref;             // reference length of a chunk
+    unsigned long long* qry;             // query length of a chunk
+    unsigned long long* cmp;             // pairs compared in a chunk
+    unsigned long long* ref0;            // n_chunks + 1 each: the exclusive scans
+    unsigned long long* qry0;
+    unsigned long long* cmp0;
+    unsigned long long* mm0;
+    unsigned long long* blk;
+    uint32_t* n_mm;                      // mismatches of a chunk
+};
+
+static inline size_t mm_blocks(uint64_t n) { return (size_t)((n + TILE - 1) / TILE); }
+
+static inline size_t mm_rec_bytes(uint32_t n_rec)
+{
+    const size_t n = n_rec;
+    return 16 + 2 * 8 * (n + 1) + (sizeof(CoverRec) + sizeof(CvSeq)) * n + 8 * (mm_blocks(n) + 2) + 2 * 4 * n;
+}
+
+static inline MmRecScratch mm_rec_scratch(gci_ctx* ctx, uint32_t n_rec)
+{
+    const size_t n = n_rec;
+    MmRecScratch s;
+    uint8_t* p = (uint8_t*)ctx->mm_rec.p;
+    s.status = (unsigned long long*)p; p += 16;
+    s.chunk0 = (unsigned long long*)p; p += 8 * (n + 1);
+    s.cnt0 = (unsigned long long*)p; p += 8 * (n + 1);
+    s.recs = (CoverRec*)p; p += sizeof(CoverRec) * n;
+    s.seqs = (CvSeq*)p; p += sizeof(CvSeq) * n;
+    s.blk = (unsigned long long*)p; p += 8 * (mm_blocks(n) + 2);
+    s.nch = (uint32_t*)p; p += 4 * n;
+    s.counted = (uint32_t*)p;
+    return s;
+}
+
+static inline size_t mm_chunk_bytes(uint64_t n_chunks)
+{
+    const size_t n = (size_t)n_chunks;
+    return sizeof(CigarSums) * n + 3 * 8 * n + 4 * 8 * (n + 1) + 8 * (mm_blocks(n) + 2) + 4 * n;
+}
+
+static inline MmChunkScratch mm_chunk_scratch(gci_ctx* ctx, uint64_t n_chunks)
+{
+    const size_t n = (size_t)n_chunks;
+    MmChunkScratch s;
+    uint8_t* p = (uint8_t*)ctx->mm_chunk.p;
+    s.sums = (CigarSums*)p; p += sizeof(CigarSums) * n;
+    s.ref = (unsigned long long*)p; p += 8 * n;
+    s.qry = (unsigned long long*)p; p += 8 * n;
+    s.cmp = (unsigned long long*)p; p += 8 * n;
+    s.ref0 = (unsigned long long*)p; p += 8 * (n + 1);
+    s.qry0 = (unsigned long long*)p; p += 8 * (n + 1);
+    s.cmp0 = (unsigned long long*)p; p += 8 * (n + 1);
+    s.mm0 = (unsigned long long*)p; p += 8 * (n + 1);
+    s.blk = (unsigned long long*)p; p += 8 * (mm_blocks(n) + 2);
+    s.n_mm = (uint32_t*)p;
+    return s;
+}
+
+__global__ __launch_bounds__(BLOCK) void k_mm_parse(const uint8_t* __restrict__ bam, uint64_t n_bytes, const uint64_t* __restrict__ rec_off,
+                                                    uint32_t n_rec, const int32_t* __restrict__ ref_sel, int32_t n_ref, uint32_t excl_flags,
+                                                    int min_mapq, CoverRec* __restrict__ recs, CvSeq* __restrict__ seqs, uint32_t* __restrict__ nch,
+                                                    unsigned long long* __restrict__ status)
+{
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n_rec) return;
+    CvSeq q;
+    uint32_t chunks;
+    const CoverRec r = cv_parse_counted(bam, n_bytes, rec_off[i], i, 1, ref_sel, n_ref, excl_flags, min_mapq, status, chunks, q);
+    recs[i] = r;
+    seqs[i] = q;
+    nch[i] = chunks;
+}
+
+__global__ __launch_bounds__(BLOCK) void k_mm_lens(const CigarSums* __restrict__ sums, unsigned long long n_chunks,
+                                                   unsigned long long* __restrict__ chunk_ref, unsigned long long* __restrict__ chunk_qry)
+{
+    const unsigned long long ch = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x;
+    if (ch >= n_chunks) return;
+    const CigarSums s = sums[ch];
+    chunk_ref[ch] = s.M + s.D + s.N;                   // (every total is below 2^57)
+    chunk_qry[ch] = s.S + s.M + s.I;
+}
+
+__device__ __forceinline__ unsigned long long mm_below(int lane) { return (1ull << lane) - 1ull; }
+
+// LDS written by the lanes of ONE wave is read by its other lanes: no workgroup barrier (the waves of a workgroup walk chunks of
+// different lengths), the wave's own LDS operations complete in order
+__device__ __forceinline__ void mm_wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+struct MmWalkArgs {
+    const uint8_t* bam;
+    uint64_t n_bytes;
+    const CoverRec* recs;
+    const CvSeq* seqs;
+    const unsigned long long* chunk0;
+    uint32_t n_rec;
+    unsigned long long n_chunks;
+    const unsigned long long* ref0;
+    const unsigned long long* qry0;
+    const int64_t* contig_len;
+    const int64_t* contig_off;
+    int32_t n_contigs;
+    const uint8_t* codes;
+};
+
+template <bool WRITE>
+__device__ __forceinline__ void mm_walk(const MmWalkArgs& A, uint32_t* __restrict__ chunk_mm, unsigned long long* __restrict__ chunk_cmp,
+                                        const unsigned long long* __restrict__ chunk_mm0, unsigned long long total, gci_ivl* __restrict__ out)
+{
+    // of the round's 64 operations: the inclusive scan of the match lengths, and where each begins on the reference and in the read
+    __shared__ unsigned long long s_inc[BLOCK / 64][64], s_ref[BLOCK / 64][64], s_qry[BLOCK / 64][64];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const unsigned long long ch = (unsigned long long)blockIdx.x * (BLOCK / 64) + w;
+    if (ch >= A.n_chunks) return;                      // (the whole wave)
+    const uint32_t rec = cv_rec_of_chunk(A.chunk0, A.n_rec, ch);
+    const CoverRec r = A.recs[rec];
+    const CvSeq sq = A.seqs[rec];
+    const unsigned long long ch_first = A.chunk0[rec], ch_last = A.chunk0[rec + 1];
+    uint32_t mms = 0;
+    unsigned long long cmps = 0;
+    // SEQ `*`, or a record whose operations do not add up to l_seq (k_mm_finish reports it): nothing is compared, no SEQ byte is read
+    const bool walk = sq.l_seq != 0 && A.qry0[ch_last] - A.qry0[ch_first] == (unsigned long long)sq.l_seq;
+    if (walk) {
+        const CvChunk c = cv_chunk_of(A.bam, r, (uint32_t)(ch - ch_first));
+        // positions in 64 bits: pos + the reference lengths in front may pass 2^31; compared with L before they index anything
+        unsigned long long at = (unsigned long long)(uint32_t)r.pos + (A.ref0[ch] - A.ref0[ch_first]);
+        unsigned long long qat = A.qry0[ch] - A.qry0[ch_first];
+        const int64_t len = r.contig < A.n_contigs ? A.contig_len[r.contig] : 0;       // (a d_ref_sel beyond the layout: no base of it is inside)
+        const unsigned long long L = (unsigned long long)(len < 0x7FFFFFFEll ? (len < 0 ? 0 : len) : 0x7FFFFFFEll);
+        const uint8_t* __restrict__ ref = A.codes + (L ? A.contig_off[r.contig] : 0);
+        const uint8_t* __restrict__ seq = A.bam + sq.seq_off;
+        unsigned long long o_mm = WRITE ? chunk_mm0[ch] : 0ull;                         // where the chunk's next mismatch goes
+        for (uint32_t k0 = 0; k0 < c.n && at < L; k0 += 64) {                           // (behind the contig's end nothing is compared)
+            const uint32_t k = k0 + lane;
+            const bool valid = k < c.n;
+            const uint32_t v = cv_op_word(A.bam, A.n_bytes, c, k, lane);
+            const uint32_t op = v & 0xFu, n = v >> 4;
+            const unsigned long long ref_len = (valid && ((0x18Du >> op) & 1u)) ? n : 0u;   // M D N = X
+            const unsigned long long qry_len = (valid && ((0x193u >> op) & 1u)) ? n : 0u;   // M I S = X
+            const unsigned long long m_len = (valid && ((0x181u >> op) & 1u)) ? n : 0u;     // M = X
+            const unsigned long long inc_r = wave_inclusive<unsigned long long>(ref_len, lane);
+            const unsigned long long inc_q = wave_inclusive<unsigned long long>(qry_len, lane);
+            const unsigned long long inc_m = wave_inclusive<unsigned long long>(m_len, lane);
+            mm_wave_sync();                            // (the reads of the round in front are done)
+            s_inc[w][lane] = inc_m;
+            s_ref[w][lane] = at + inc_r - ref_len;
+            s_qry[w][lane] = qat + inc_q - qry_len;
+            mm_wave_sync();
+            const unsigned long long T = __shfl(inc_m, 63, 64);          // the round's match bases, dealt MM_BASES to a lane
+            for (unsigned long long b0 = 0; b0 < T; b0 += 64 * MM_BASES) {
+                const unsigned long long j0 = b0 + (unsigned long long)lane * MM_BASES;
+                uint32_t o = 0;                        // the operation of base j0: the entries of s_inc at or below it
+                if (j0 < T) {
+#pragma unroll
+                    for (uint32_t step = 32; step >= 1; step >>= 1) if (s_inc[w][o + step - 1] <= j0) o += step;
+                }
+                uint32_t cmp = 0, mis = 0;
+                unsigned long long p_first = ~0ull;
+#pragma unroll
+                for (int b = 0; b < MM_BASES; b++) {
+                    const unsigned long long j = j0 + b;
+                    if (j >= T) break;
+                    while (s_inc[w][o] <= j) o++;      // (j < T = s_inc[63]: o stays below 64; operations without match bases are passed)
+                    const unsigned long long in_op = j - (o ? s_inc[w][o - 1] : 0ull);
+                    const unsigned long long p = s_ref[w][o] + in_op, q = s_qry[w][o] + in_op;
+                    if (b == 0) p_first = p;
+                    if (p < L && q < (unsigned long long)sq.l_seq) {
+                        const uint32_t rc = ref[p], sb = seq[q >> 1];
+                        const uint32_t nib = (q & 1ull) ? (sb & 15u) : (sb >> 4);             // the high nibble is the even q
+                        const bool both = ((0x116u >> rc) & 1u) && ((0x116u >> nib) & 1u);    // both one of 1 2 4 8 (rc, nib < 16)
+                        cmp |= both ? (1u << b) : 0u;
+                        mis |= (both && rc != nib) ? (1u << b) : 0u;
+                    }
+                }
+                if (WRITE) {
+                    // base order is lane order, then the order inside the lane: the lanes below, then the lane's own lower bits
+                    unsigned long long slot = o_mm;
+                    uint32_t step_total = 0;
+#pragma unroll
+                    for (int b = 0; b < MM_BASES; b++) {
+                        const unsigned long long m = __ballot((mis >> b) & 1u);
+                        slot += (unsigned long long)__builtin_popcountll(m & mm_below(lane));
+                        step_total += (uint32_t)__builtin_popcountll(m);
+                    }
+                    uint32_t bits = mis;
+                    while (bits) {
+                        const int b = __builtin_ctz(bits);
+                        bits &= bits - 1u;
+                        const unsigned long long j = j0 + b;
+                        uint32_t oo = 0;
+#pragma unroll
+                        for (uint32_t step = 32; step >= 1; step >>= 1) if (s_inc[w][oo + step - 1] <= j) oo += step;
+                        const unsigned long long p = s_ref[w][oo] + (j - (oo ? s_inc[w][oo - 1] : 0ull));
+                        gci_ivl e;
+                        e.contig = r.contig; e.start = (int32_t)p; e.end = (int32_t)p; e.pad = 0;
+                        if (slot < total) out[slot] = e;
+                        slot++;
+                    }
+                    o_mm += step_total;
+                } else {
+                    mms += (uint32_t)__builtin_popcount(mis);
+                    cmps += (unsigned long long)__builtin_popcount(cmp);
+                }
+                if (__shfl(p_first, 0, 64) >= L) break;                  // (positions ascend with the base index: the rest is outside)
+            }
+            at += __shfl(inc_r, 63, 64);
+            qat += __shfl(inc_q, 63, 64);
+        }
+    }
+    if (!WRITE) {
+        mms = wave_sum<uint32_t>(mms);
+        cmps = wave_sum<unsigned long long>(cmps);
+        if (lane == 0) { chunk_mm[ch] = mms; chunk_cmp[ch] = cmps; }
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_mm_count(MmWalkArgs A, uint32_t* __restrict__ chunk_mm, unsigned long long* __restrict__ chunk_cmp)
+{
+    mm_walk<false>(A, chunk_mm, chunk_cmp, nullptr, 0, nullptr);
+}
+
+__global__ __launch_bounds__(BLOCK) void k_mm_write(MmWalkArgs A, const unsigned long long* __restrict__ chunk_mm0, unsigned long long total,
+                                                    gci_ivl* __restrict__ out)
+{
+    mm_walk<true>(A, nullptr, nullptr, chunk_mm0, total, out);
+}
+
+__global__ __launch_bounds__(BLOCK) void k_mm_finish(uint32_t n_rec, const CoverRec* __restrict__ recs, const CvSeq* __restrict__ seqs,
+                                                     const unsigned long long* __restrict__ chunk0, const CigarSums* __restrict__ sums,
+                                                     const unsigned long long* __restrict__ qry0, uint32_t* __restrict__ counted,
+                                                     unsigned long long* __restrict__ status)
+{
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n_rec) return;
+    uint32_t c = 0;
+    if (recs[i].contig >= 0) {
+        c = 1;
+        unsigned long long bad = 0;
+        const unsigned long long first = chunk0[i], last = chunk0[i + 1];
+        for (unsigned long long ch = first; ch < last; ch++) bad |= sums[ch].bad;
+        const unsigned long long q = last > first ? qry0[last] - qry0[first] : 0ull;
+        if (seqs[i].l_seq != 0 && q != (unsigned long long)seqs[i].l_seq) bad = 1;
+        if (bad) cv_report(status, i, GCI_E_MALFORMED);
+    }
+    counted[i] = c;
+}
+
+static inline dim3 mm_wave_grid(unsigned long long n) { return dim3((uint32_t)((n + BLOCK / 64 - 1) / (BLOCK / 64))); }
+
+static inline MmWalkArgs mm_walk_args(gci_ctx* ctx, const uint8_t* d_stream, uint64_t n_bytes, uint32_t n_rec, unsigned long long n_chunks,
+                                      const MmRecScratch& R, const MmChunkScratch& C, const uint8_t* d_codes)
+{
+    MmWalkArgs A;
+    A.bam = d_stream; A.n_bytes = n_bytes; A.recs = R.recs; A.seqs = R.seqs; A.chunk0 = R.chunk0; A.n_rec = n_rec; A.n_chunks = n_chunks;
+    A.ref0 = C.ref0; A.qry0 = C.qry0; A.contig_len = (const int64_t*)ctx->d_len.p; A.contig_off = (const int64_t*)ctx->d_off.p;
+    A.n_contigs = ctx->n_contigs; A.codes = d_codes;
+    return A;
+}
+
+extern "C" int gci_bam_mismatch_size(gci_ctx* ctx, const uint8_t* d_stream, uint64_t n_bytes, const uint64_t* d_rec_off, uint32_t n_rec, int has_seq,
+                                     const int32_t* d_ref_sel, int32_t n_ref, uint32_t excl_flags, int min_mapq, const uint8_t* d_codes,
+                                     uint64_t* h_counts, uint64_t* d_status)
+{
+    if (!ctx || !h_counts || !d_status || !d_codes || n_ref < 0 || has_seq != 1 || (n_rec && (!d_stream || !d_rec_off || !d_ref_sel)))
+        return GCI_E_INVALID;
+    if (!ctx->n_contigs) return GCI_E_NO_LAYOUT;
+    ctx->mm_valid = false;
+    h_counts[0] = h_counts[1] = h_counts[2] = 0;
+    GCI_TRY(gci_ensure(ctx, ctx->mm_rec, mm_rec_bytes(n_rec)));
+    const MmRecScratch R = mm_rec_scratch(ctx, n_rec);
+    HIPCHK(hipMemsetAsync(R.status, 0xFF, 8, ctx->stream));
+    unsigned long long n_chunks = 0, n_mm = 0, n_cmp = 0, n_counted = 0;
+    if (n_rec) {
+        const uint32_t groups = (n_rec + BLOCK - 1) / BLOCK;
+        hipLaunchKernelGGL(k_mm_parse, dim3(groups), dim3(BLOCK), 0, ctx->stream, d_stream, n_bytes, d_rec_off, n_rec, d_ref_sel, n_ref, excl_flags,
+                           min_mapq, R.recs, R.seqs, R.nch, R.status);
+        LAUNCHCHK("k_mm_parse");
+        GCI_TRY((device_exclusive_scan<uint32_t, unsigned long long>(ctx, R.nch, R.chunk0, R.blk, (int64_t)n_rec, true)));
+        HIPCHK(hipMemcpyAsync(&n_chunks, R.chunk0 + n_rec, 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        if (n_chunks > 0x7FFFFFFFull) return GCI_E_INVALID;                  // (2^42 operations in one call)
+        const CigarSums* sums = nullptr;
+        const unsigned long long* qry0 = nullptr;
+        if (n_chunks) {
+            GCI_TRY(gci_ensure(ctx, ctx->mm_chunk, mm_chunk_bytes(n_chunks)));
+            const MmChunkScratch C = mm_chunk_scratch(ctx, n_chunks);
+            sums = C.sums; qry0 = C.qry0;
+            hipLaunchKernelGGL(k_cigar_sums, cigar_sums_grid(n_chunks), dim3(BLOCK), 0, ctx->stream, d_stream, n_bytes, R.recs, R.chunk0, n_rec, n_chunks,
+                               C.sums);
+            LAUNCHCHK("k_cigar_sums");
+            hipLaunchKernelGGL(k_mm_lens, dim3((uint32_t)((n_chunks + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, ctx->stream, C.sums, n_chunks, C.ref, C.qry);
+            LAUNCHCHK("k_mm_lens");
+            GCI_TRY((device_exclusive_scan<unsigned long long, unsigned long long>(ctx, C.ref, C.ref0, C.blk, (int64_t)n_chunks, true)));
+            GCI_TRY((device_exclusive_scan<unsigned long long, unsigned long long>(ctx, C.qry, C.qry0, C.blk, (int64_t)n_chunks, true)));
+            hipLaunchKernelGGL(k_mm_count, mm_wave_grid(n_chunks), dim3(BLOCK), 0, ctx->stream,
+                               mm_walk_args(ctx, d_stream, n_bytes, n_rec, n_chunks, R, C, d_codes), C.n_mm, C.cmp);
+            LAUNCHCHK("k_mm_count");
+            GCI_TRY((device_exclusive_scan<uint32_t, unsigned long long>(ctx, C.n_mm, C.mm0, C.blk, (int64_t)n_chunks, true)));
+            GCI_TRY((device_exclusive_scan<unsigned long long, unsigned long long>(ctx, C.cmp, C.cmp0, C.blk, (int64_t)n_chunks, true)));
+            HIPCHK(hipMemcpyAsync(&n_mm, C.mm0 + n_chunks, 8, hipMemcpyDeviceToHost, ctx->stream));
+            HIPCHK(hipMemcpyAsync(&n_cmp, C.cmp0 + n_chunks, 8, hipMemcpyDeviceToHost, ctx->stream));
+        }
+        hipLaunchKernelGGL(k_mm_finish, dim3(groups), dim3(BLOCK), 0, ctx->stream, n_rec, R.recs, R.seqs, R.chunk0, sums, qry0, R.counted, R.status);
+        LAUNCHCHK("k_mm_finish");
+        GCI_TRY((device_exclusive_scan<uint32_t, unsigned long long>(ctx, R.counted, R.cnt0, R.blk, (int64_t)n_rec, true)));
+        HIPCHK(hipMemcpyAsync(&n_counted, R.cnt0 + n_rec, 8, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIPCHK(hipMemcpyAsync(d_status, R.status, 8, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    ctx->mm_valid = true;
+    ctx->mm_n_rec = n_rec; ctx->mm_n_bytes = n_bytes; ctx->mm_n_chunks = n_chunks; ctx->mm_n_mm = n_mm;
+    ctx->mm_stream = d_stream; ctx->mm_off = d_rec_off; ctx->mm_codes = d_codes;
+    h_counts[0] = n_counted; h_counts[1] = n_mm; h_counts[2] = n_cmp;
+    return GCI_OK;
+}
+
+extern "C" int gci_bam_mismatch_write(gci_ctx* ctx, const uint8_t* d_stream, uint64_t n_bytes, const uint64_t* d_rec_off, uint32_t n_rec, int has_seq,
+                                      const uint8_t* d_codes, gci_ivl* d_out, uint64_t cap, uint64_t* d_status)
+{
+    if (!ctx || !d_status || !d_codes || has_seq != 1 || (n_rec && (!d_stream || !d_rec_off))) return GCI_E_INVALID;
+    if (!ctx->n_contigs) return GCI_E_NO_LAYOUT;
+    // not the input gci_bam_mismatch_size measured last on this context
+    if (!ctx->mm_valid || n_rec != ctx->mm_n_rec || n_bytes != ctx->mm_n_bytes || d_stream != ctx->mm_stream || d_rec_off != ctx->mm_off ||
+        d_codes != ctx->mm_codes)
+        return GCI_E_INVALID;
+    const unsigned long long total = ctx->mm_n_mm;
+    if (total && !d_out) return GCI_E_INVALID;
+    if (cap < total) return GCI_E_CAPACITY;
+    const MmRecScratch R = mm_rec_scratch(ctx, n_rec);
+    const unsigned long long n_chunks = ctx->mm_n_chunks;
+    if (n_chunks && total) {
+        const MmChunkScratch C = mm_chunk_scratch(ctx, n_chunks);
+        hipLaunchKernelGGL(k_mm_write, mm_wave_grid(n_chunks), dim3(BLOCK), 0, ctx->stream,
+                           mm_walk_args(ctx, d_stream, n_bytes, n_rec, n_chunks, R, C, d_codes), C.mm0, total, d_out);
+        LAUNCHCHK("k_mm_write");
+    }
+    HIPCHK(hipMemcpyAsync(d_status, R.status, 8, hipMemcpyDeviceToDevice, ctx->stream));
+    return GCI_OK;
+}
+
+// ---- the track side -----------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool mm_hot(int32_t mm, int32_t depth, int32_t min_reads, int64_t frac_ppm)
+{
+    return mm >= min_reads && (int64_t)mm * 1000000ll >= frac_ppm * (int64_t)depth;
+}
+
+// whether the element in front of q is hot AND of the same window and contig (q - 1 may lie in the tile in front)
+__device__ __forceinline__ bool mm_prev_hot(const int32_t* __restrict__ mm, const int32_t* __restrict__ depth, const SiteTile& x, int64_t q,
+                                            int32_t min_reads, int64_t frac_ppm)
+{
+    if (q - 1 < x.run_lo || q - 1 >= x.run_hi) return false;
+    return mm_hot(mm[q - 1], depth[q - 1], min_reads, frac_ppm);
+}
+
+// the hot elements among a thread's 16 consecutive ones at p (bit k: element p + k)
+__device__ __forceinline__ uint32_t mm_hot16(const int32_t* __restrict__ mm, const int32_t* __restrict__ depth, const SiteTile& x, int64_t p,
+                                             int32_t min_reads, int64_t frac_ppm)
+{
+    uint32_t hot = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const int4 a = *reinterpret_cast<const int4*>(mm + p + 4 * j), b = *reinterpret_cast<const int4*>(depth + p + 4 * j);
+        const int32_t m[4] = {a.x, a.y, a.z, a.w}, d[4] = {b.x, b.y, b.z, b.w};
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int64_t q = p + 4 * j + k;
+            hot |= (q >= x.lo && q < x.hi && mm_hot(m[k], d[k], min_reads, frac_ppm)) ? (1u << (4 * j + k)) : 0u;
+        }
+    }
+    return hot;
+}
+
+// one workgroup per window tile, a thread 16 consecutive elements: the run starts of the tile, counted (WRITE = false) or stored by rank
+template <bool WRITE>
+__device__ __forceinline__ void mm_sites_tile(const int32_t* __restrict__ mm, const int32_t* __restrict__ depth, const gci_window* __restrict__ win,
+                                              const int64_t* __restrict__ win_tile_first, int32_t n_win, const int64_t* __restrict__ off,
+                                              const int64_t* __restrict__ len, const int64_t* __restrict__ tile_first, int32_t n_contigs,
+                                              int32_t min_reads, int64_t frac_ppm, uint32_t* __restrict__ tile_cnt,
+                                              const unsigned long long* __restrict__ tile_off, gci_mismatch_site* __restrict__ out,
+                                              unsigned long long total)
+{
+    __shared__ uint32_t wtot[BLOCK / 64];
+    if (WRITE && tile_cnt[blockIdx.x] == 0) return;    // (the whole workgroup)
+    const int t = threadIdx.x, lane = t & 63;
+    const SiteTile x = site_tile_of(win, win_tile_first, n_win, blockIdx.x, off, len, tile_first, n_contigs);
+    const int64_t p = x.p0 + (int64_t)t * 16;          // ascending order is thread order
+    const uint32_t hot = mm_hot16(mm, depth, x, p, min_reads, frac_ppm);
+    uint32_t prev = (uint32_t)__shfl_up((int)(hot >> 15), 1, 64);
+    if (lane == 0) prev = mm_prev_hot(mm, depth, x, p, min_reads, frac_ppm) ? 1u : 0u;
+    uint32_t starts = hot & ~((hot << 1) | prev) & 0xFFFFu;
+    uint32_t all;
+    const uint32_t pre = block_exclusive<uint32_t, BLOCK / 64>((uint32_t)__builtin_popcount(starts), wtot, all);
+    if (!WRITE) {
+        if (t == 0) tile_cnt[blockIdx.x] = all;
+        return;
+    }
+    unsigned long long slot = tile_off[blockIdx.x] + pre;
+    while (starts) {                                   // (few: a genome has thousands of sites)
+        const int k = __builtin_ctz(starts);
+        starts &= starts - 1u;
+        gci_mismatch_site s;
+        s.contig = x.contig; s.start = (int32_t)(p + k - x.contig_off);
+        s.end = (int32_t)(x.run_hi - x.contig_off);    // where the run ends at the latest: k_mm_site_finish walks up to it
+        s.mismatch = 0; s.depth = 0;
+        if (slot < total) out[slot] = s;
+        slot++;
+    }
+}
+
+__global__ __launch_bounds__(BLOCK) void k_mm_sites_count(const int32_t* __restrict__ mm, const int32_t* __restrict__ depth,
+                                                          const gci_window* __restrict__ win, const int64_t* __restrict__ win_tile_first, int32_t n_win,
+                                                          const int64_t* __restrict__ off, const int64_t* __restrict__ len,
+                                                          const int64_t* __restrict__ tile_first, int32_t n_contigs, int32_t min_reads,
+                                                          int64_t frac_ppm, uint32_t* __restrict__ tile_cnt)
+{
+    mm_sites_tile<false>(mm, depth, win, win_tile_first, n_win, off, len, tile_first, n_contigs, min_reads, frac_ppm, tile_cnt, nullptr, nullptr, 0);
+}
+
+__global__ __launch_bounds__(BLOCK) void k_mm_sites_write(const int32_t* __restrict__ mm, const int32_t* __restrict__ depth,
+                                                          const gci_window* __restrict__ win, const int64_t* __restrict__ win_tile_first, int32_t n_win,
+                                                          const int64_t* __restrict__ off, const int64_t* __restrict__ len,
+                                                          const int64_t* __restrict__ tile_first, int32_t n_contigs, int32_t min_reads,
+                                                          int64_t frac_ppm, uint32_t* __restrict__ tile_cnt,
+                                                          const unsigned long long* __restrict__ tile_off, gci_mismatch_site* __restrict__ out,
+                                                          unsigned long long total)
+{
+    mm_sites_tile<true>(mm, depth, win, win_tile_first, n_win, off, len, tile_first, n_contigs, min_reads, frac_ppm, tile_cnt, tile_off, out, total);
+}
+
+// one wave per site: forward from the start, 64 elements a round, to the first element that is not hot or the end of the window or
+// contig; the largest mismatch count and the depth at the FIRST base that reaches it
+__global__ __launch_bounds__(BLOCK) void k_mm_site_finish(const int32_t* __restrict__ mm, const int32_t* __restrict__ depth,
+                                                          const int64_t* __restrict__ off, int32_t min_reads, int64_t frac_ppm,
+                                                          gci_mismatch_site* __restrict__ out, unsigned long long total)
+{
+    const int lane = threadIdx.x & 63;
+    const unsigned long long i = (unsigned long long)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6);
+    if (i >= total) return;                            // (the whole wave)
+    const gci_mismatch_site s = out[i];
+    const int64_t base = off[s.contig], lim = base + s.end, q0 = base + s.start;
+    int64_t q = q0;                                    // (hot, and below lim)
+    // (count << 32) | (0xFFFFFFFF - distance from the start): the largest key is the largest count at the smallest distance
+    unsigned long long best = 0;
+    for (;;) {
+        const int64_t e = q + lane;
+        const bool in = e < lim;
+        const int32_t m = in ? mm[e] : 0, d = in ? depth[e] : 0;
+        const unsigned long long cold = ~__ballot(in && mm_hot(m, d, min_reads, frac_ppm));
+        const int first = cold ? __builtin_ctzll(cold) : 64;                    // the run's elements of this round: the lanes below `first`
+        if (lane < first) {
+            const unsigned long long key = ((unsigned long long)(uint32_t)m << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)(e - q0));
+            best = key > best ? key : best;
+        }
+        q += first;
+        if (first < 64) break;
+    }
+#pragma unroll
+    for (int x = 32; x >= 1; x >>= 1) { const unsigned long long o = __shfl_xor(best, x, 64); best = o > best ? o : best; }
+    if (lane == 0) {
+        gci_mismatch_site r = s;
+        r.end = (int32_t)(q - base);
+        r.mismatch = (int32_t)(best >> 32);
+        r.depth = depth[q0 + (best ? (int64_t)(0xFFFFFFFFu - (uint32_t)best) : 0)];      // (best != 0: the start is hot)
+        out[i] = r;
+    }
+}
+
+struct MmTileScratch { uint32_t* cnt; unsigned long long* off; unsigned long long* blk; };
+
+static inline MmTileScratch mm_tile_scratch(gci_ctx* ctx, int64_t tiles)
+{
+    MmTileScratch s;
+    uint8_t* p = (uint8_t*)ctx->mm_tiles.p;
+    s.off = (unsigned long long*)p; p += 8 * ((size_t)tiles + 1);
+    s.blk = (unsigned long long*)p; p += 8 * (mm_blocks((uint64_t)tiles) + 2);
+    s.cnt = (uint32_t*)p;
+    return s;
+}
+
+extern "C" int gci_mismatch_sites_size(gci_ctx* ctx, const int32_t* d_mismatch, const int32_t* d_depth, int32_t min_reads, int32_t frac_ppm,
+                                       const gci_window* h_windows, uint32_t n_windows, uint64_t* h_n_sites)
+{
+    if (!ctx || !d_mismatch || !d_depth || !h_n_sites || min_reads < 1 || frac_ppm < 0 || frac_ppm > 1000000 || (n_windows && !h_windows))
+        return GCI_E_INVALID;
+    if (!ctx->n_contigs) return GCI_E_NO_LAYOUT;
+    if ((((uintptr_t)d_mismatch) | ((uintptr_t)d_depth)) & 15u) return GCI_E_INVALID;                        // whole tracks, as allocated
+    if (n_windows >= (1u << 31)) return GCI_E_INVALID;
+    std::vector<gci_window> ws;
+    if (!gci_site_windows(ctx, h_windows, n_windows, ws)) return GCI_E_INVALID;
+    ctx->mm_sites_epoch = 0;
+    *h_n_sites = 0;
+    GCI_TRY(gci_set_windows(ctx, ws.data(), (uint32_t)ws.size()));
+    ctx->win_flank = INT32_MIN;
+    const int64_t tiles = ctx->win_tiles;
+    if (tiles > 0x7FFFFFFFll) return GCI_E_INVALID;
+    unsigned long long total = 0;
+    if (tiles) {
+        GCI_TRY(gci_ensure(ctx, ctx->mm_tiles, 8 * ((size_t)tiles + 1) + 8 * (mm_blocks((uint64_t)tiles) + 2) + 4 * (size_t)tiles));
+        const MmTileScratch T = mm_tile_scratch(ctx, tiles);
+        hipLaunchKernelGGL(k_mm_sites_count, dim3((uint32_t)tiles), dim3(BLOCK), 0, ctx->stream, d_mismatch, d_depth, (const gci_window*)ctx->win.p,
+                           (const int64_t*)ctx->win_tile_first.p, (int32_t)ctx->win_n, (const int64_t*)ctx->d_off.p, (const int64_t*)ctx->d_len.p,
+                           (const int64_t*)ctx->d_tile_first.p, ctx->n_contigs, min_reads, (int64_t)frac_ppm, T.cnt);
+        LAUNCHCHK("k_mm_sites_count");
+        GCI_TRY((device_exclusive_scan<uint32_t, unsigned long long>(ctx, T.cnt, T.off, T.blk, tiles, true)));
+        HIPCHK(hipMemcpyAsync(&total, T.off + tiles, 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+    }
+    ctx->mm_sites_epoch = ctx->win_epoch; ctx->mm_sites_total = total;
+    ctx->mm_sites_track = d_mismatch; ctx->mm_sites_depth = d_depth;
+    ctx->mm_sites_min_reads = min_reads; ctx->mm_sites_frac = frac_ppm; ctx->mm_sites_windows = n_windows;
+    *h_n_sites = total;
+    return GCI_OK;
+}
+
+extern "C" int gci_mismatch_sites_write(gci_ctx* ctx, const int32_t* d_mismatch, const int32_t* d_depth, int32_t min_reads, int32_t frac_ppm,
+                                        const gci_window* h_windows, uint32_t n_windows, gci_mismatch_site* d_out, uint64_t cap)
+{
+    if (!ctx || !d_mismatch || !d_depth || min_reads < 1 || (n_windows && !h_windows)) return GCI_E_INVALID;
+    if (!ctx->n_contigs) return GCI_E_NO_LAYOUT;
+    // not what gci_mismatch_sites_size measured last on this context, or its windows are no longer the context's
+    if (!ctx->mm_sites_epoch || ctx->mm_sites_epoch != ctx->win_epoch || d_mismatch != ctx->mm_sites_track || d_depth != ctx->mm_sites_depth ||
+        min_reads != ctx->mm_sites_min_reads || frac_ppm != ctx->mm_sites_frac || n_windows != ctx->mm_sites_windows)
+        return GCI_E_INVALID;
+    const unsigned long long total = ctx->mm_sites_total;
+    if (total && !d_out) return GCI_E_INVALID;
+    if (cap < total) return GCI_E_CAPACITY;
+    const int64_t tiles = ctx->win_tiles;
+    if (!tiles || !total) return GCI_OK;
+    const MmTileScratch T = mm_tile_scratch(ctx, tiles);
+    hipLaunchKernelGGL(k_mm_sites_write, dim3((uint32_t)tiles), dim3(BLOCK), 0, ctx->stream, d_mismatch, d_depth, (const gci_window*)ctx->win.p,
+                       (const int64_t*)ctx->win_tile_first.p, (int32_t)ctx->win_n, (const int64_t*)ctx->d_off.p, (const int64_t*)ctx->d_len.p,
+                       (const int64_t*)ctx->d_tile_first.p, ctx->n_contigs, min_reads, (int64_t)frac_ppm, T.cnt, T.off, d_out, total);
+    LAUNCHCHK("k_mm_sites_write");
+    hipLaunchKernelGGL(k_mm_site_finish, mm_wave_grid(total), dim3(BLOCK), 0, ctx->stream, d_mismatch, d_depth, (const int64_t*)ctx->d_off.p, min_reads,
+                       (int64_t)frac_ppm, d_out, total);
+    LAUNCHCHK("k_mm_site_finish");
+    return GCI_OK;
+}

@@ -27,6 +27,7 @@ IVL_DTYPE = np.dtype([("contig", "<i4"), ("start", "<i4"), ("end", "<i4"), ("pad
 RUN_DTYPE = np.dtype([("start", "<u4"), ("depth", "<i4")])          # gci_depth_run
 SITE_DTYPE = np.dtype([("contig", "<i4"), ("pos", "<i4"), ("left", "<i4"), ("right", "<i4"), ("depth", "<i4"), ("pad", "<i4")])      # gci_clip_site
 INDEL_SITE_DTYPE = np.dtype([("contig", "<i4"), ("start", "<i4"), ("end", "<i4"), ("del", "<i4"), ("ins", "<i4"), ("depth", "<i4")])      # gci_indel_site
+MISMATCH_SITE_DTYPE = np.dtype([("contig", "<i4"), ("start", "<i4"), ("end", "<i4"), ("mismatch", "<i4"), ("depth", "<i4")])      # gci_mismatch_site
 
 _M64 = (1 << 64) - 1
 Buffer = Any                  # a device buffer of the engine's provider: hbm.Buf or Buffer
@@ -495,6 +496,72 @@ class Engine:
         out = self.T.empty((total, 6), self.T.int32, self.device)
         self._chk(self.lib.gci_indel_sites_write(*head, self._p(out), total), "gci_indel_sites_write")
         return np.ascontiguousarray(out.cpu().numpy()).view(INDEL_SITE_DTYPE).reshape(-1)[:total]
+
+    # ---- mismatch_sites.py: bases where the reads disagree with the assembly (include/gci_hip.h: gci_fasta_codes, gci_bam_mismatch_*,
+    # gci_mismatch_sites_*; k_mismatch.hip) ----
+    def fasta_codes(self, text: np.ndarray, bodies: np.ndarray, dst: np.ndarray, codes: Optional[Buffer] = None,
+                    before_codes=None) -> Tuple[Buffer, np.ndarray]:
+        """The assembly as one 4-bit code per base in the track layout -> (uint8 [layout total] on the device, the uint32 sequence-byte
+        count of every 4096-byte tile of the file).  text = the FASTA file's bytes, bodies = int64 [n_records, 2] byte ranges of the
+        record bodies, dst[r] = the flat element of record r's first base or -1 to leave it out.  codes: the array to write into
+        (default: a new one filled with 15); elements no base goes to keep what they held.  before_codes(tile counts): called between
+        the counting and the writing -- where a caller checks the records' lengths (formats/fasta.body_lengths) and may raise."""
+        n = int(text.shape[0])
+        d_text = self.upload_staged(text) if n >= (256 << 20) else self.to_device(text)
+        bodies = np.ascontiguousarray(bodies, dtype=np.int64).reshape(-1, 2)
+        d_body = self.to_device(bodies)
+        d_dst = self.to_device(np.ascontiguousarray(dst, dtype=np.int64))
+        tiles = (n + 4095) // 4096
+        kept = self.T.zeros(max(tiles, 1), self.T.int32, self.device)
+        self._chk(self.lib.gci_fasta_n_scan(self.ctx, self._p(d_text), n, self._p(d_body), int(bodies.shape[0]), self._p(kept), None, 0,
+                                            self._p(self._count)), "gci_fasta_n_scan")
+        kept0 = self.T.empty(tiles + 1, self.T.int64, self.device)
+        self._chk(self.lib.gci_dev_u32_scan_u64(self.device.index or 0, self._p(kept), tiles, self._p(kept0),
+                                                ctypes.c_void_p(self.stream.cuda_stream)), "gci_dev_u32_scan_u64")
+        h_kept = kept.cpu().numpy().view(np.uint32)[:tiles]
+        if before_codes is not None:
+            before_codes(h_kept)
+        if codes is None:
+            codes = self.T.empty(max(int(self.total), 1), self.T.uint8, self.device)
+            codes[:] = 15
+        self._chk(self.lib.gci_fasta_codes(self.ctx, self._p(d_text), n, self._p(d_body), int(bodies.shape[0]), self._p(d_dst), self._p(kept0),
+                                           self._p(codes)), "gci_fasta_codes")
+        return codes, h_kept
+
+    def bam_mismatch(self, d_stream: Buffer, d_rec_off: Buffer, has_seq: bool, d_ref_sel: Buffer, d_codes: Buffer, excl_flags: int = 0x704,
+                     min_mapq: int = 0, check: bool = True, rec_idx_base: int = 0) -> Tuple[Buffer, List[int]]:
+        """-> (the events, [records counted, mismatches, pairs compared]): intervals int32 [n, 4], (contig, p, p, 0) per base p of a
+        counted record of an inflated BAM stream (has_seq must hold) where the read's base and the assembly's code in d_codes are both
+        one of A, C, G, T and differ, in (record, reference position) order, for depth_build with flank 0."""
+        n = int(d_rec_off.shape[0])
+        counts = (ctypes.c_uint64 * 3)()
+        self._chk(self.lib.gci_bam_mismatch_size(self.ctx, self._p(d_stream), int(d_stream.shape[0]), self._p(d_rec_off), n, int(has_seq),
+                                                 self._p(d_ref_sel), int(d_ref_sel.shape[0]), int(excl_flags), int(min_mapq), self._p(d_codes), counts,
+                                                 self._p(self._status)), "gci_bam_mismatch_size")
+        if check:
+            self._raise_status(self._status.item(), "gci_bam_mismatch_size", rec_idx_base)
+        n_mm = int(counts[1])
+        out = self.T.empty((max(n_mm, 1), 4), self.T.int32, self.device)
+        self._chk(self.lib.gci_bam_mismatch_write(self.ctx, self._p(d_stream), int(d_stream.shape[0]), self._p(d_rec_off), n, int(has_seq),
+                                                  self._p(d_codes), self._p(out), n_mm, self._p(self._status)), "gci_bam_mismatch_write")
+        return out[:n_mm], [int(c) for c in counts]
+
+    def mismatch_sites(self, mismatch: Buffer, depth: Buffer, min_reads: int, frac_ppm: int,
+                       windows: Sequence[Tuple[int, int]] = ()) -> np.ndarray:
+        """-> MISMATCH_SITE_DTYPE [n]: the maximal runs of elements with mismatch >= min_reads and mismatch * 1000000 >= frac_ppm * depth
+        inside the sorted, disjoint [begin, end) windows of track elements (none: every contig), in ascending order: contig, start, end
+        (exclusive), the largest mismatch count of the run and the depth at the first base that reaches it."""
+        nw = len(windows)
+        arr = self._window_array(windows)
+        n = ctypes.c_uint64(0)
+        head = (self.ctx, self._p(mismatch), self._p(depth), int(min_reads), int(frac_ppm), arr, nw)
+        self._chk(self.lib.gci_mismatch_sites_size(*head, ctypes.byref(n)), "gci_mismatch_sites_size")
+        total = int(n.value)
+        if total == 0:
+            return np.zeros(0, dtype=MISMATCH_SITE_DTYPE)
+        out = self.T.empty((total, 5), self.T.int32, self.device)
+        self._chk(self.lib.gci_mismatch_sites_write(*head, self._p(out), total), "gci_mismatch_sites_write")
+        return np.ascontiguousarray(out.cpu().numpy()).view(MISMATCH_SITE_DTYPE).reshape(-1)[:total]
 
     def track_add(self, acc: Buffer, add: Buffer) -> Buffer:
         """acc += add over the layout."""

@@ -138,13 +138,27 @@ def encode_aux(tags: Sequence[Tuple[str, str, object]]) -> bytes:
     return b"".join(out)
 
 
+_SEQ_CODE = np.full(256, 15, dtype=np.uint8)
+for _k, _c in enumerate("=ACMGRSVTWYHKDBN"):
+    _SEQ_CODE[ord(_c)] = _SEQ_CODE[ord(_c.lower())] = _k
+
+
+def pack_seq(seq: bytes) -> bytes:
+    """ASCII bases -> BAM's packed SEQ: two 4-bit codes a byte, the first base in the high nibble."""
+    codes = _SEQ_CODE[np.frombuffer(seq, dtype=np.uint8)]
+    if codes.shape[0] & 1:
+        codes = np.concatenate((codes, np.zeros(1, dtype=np.uint8)))
+    return ((codes[0::2] << 4) | codes[1::2]).astype(np.uint8).tobytes()
+
+
 def encode_record(ref_id: int, pos: int, name: str, mapq: int, flag: int,
                   cigar: Sequence[Tuple[int, int]], l_seq: int, aux: bytes = b"",
                   seq_fill: int = 0x11, qual_fill: int = 0xFF,
                   n_cigar_field: Optional[int] = None, next_ref: int = -1, next_pos: int = -1,
-                  tlen: int = 0) -> bytes:
+                  tlen: int = 0, seq: Optional[bytes] = None) -> bytes:
     """One record incl. its block_size prefix.  ``cigar`` = [(op_code, length)].
-    ``l_seq`` 0 encodes SEQ '*'.  More than 65535 ops are stored the spec's way: a
+    ``l_seq`` 0 encodes SEQ '*'.  ``seq``: the read's bases as ASCII, ``l_seq`` of them (the high nibble
+    is the even base; letters outside "=ACMGRSVTWYHKDBN" become N); absent, every SEQ byte is ``seq_fill``.  More than 65535 ops are stored the spec's way: a
     ``<l_seq>S<ref_len>N`` placeholder plus a ``CG:B,I`` tag appended to ``aux``."""
     nb = name.encode() + b"\x00"
     if len(nb) > 255:
@@ -158,8 +172,13 @@ def encode_record(ref_id: int, pos: int, name: str, mapq: int, flag: int,
     end = pos + (rlen if rlen > 0 else 1)
     core = struct.pack("<iiBBHHHiiii", ref_id, pos, len(nb), mapq, reg2bin(max(pos, 0), max(end, 1)),
                        n_cig, flag, l_seq, next_ref, next_pos, tlen)
-    body = core + nb + struct.pack("<%dI" % len(ops), *ops) + bytes([seq_fill]) * ((l_seq + 1) // 2) + \
-        bytes([qual_fill]) * l_seq + aux
+    if seq is None:
+        packed = bytes([seq_fill]) * ((l_seq + 1) // 2)
+    else:
+        if len(seq) != l_seq:
+            raise BAMError("seq has %d bases, l_seq is %d" % (len(seq), l_seq))
+        packed = pack_seq(seq)
+    body = core + nb + struct.pack("<%dI" % len(ops), *ops) + packed + bytes([qual_fill]) * l_seq + aux
     return struct.pack("<i", len(body)) + body
 
 

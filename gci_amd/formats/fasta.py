@@ -202,6 +202,26 @@ def n_runs_device(engine, path: str, lengths: bool = False):
     return ids, runs
 
 
+def body_lengths(buf: np.ndarray, bodies: np.ndarray, kept: np.ndarray) -> List[int]:
+    """The sequence length of every record from the tile counts of gci_fasta_n_scan (`kept`: the sequence bytes of every 4096-byte
+    tile): the count in front of the body's end minus the one in front of its begin; only the two tiles the body's ends lie in
+    are looked at on the host."""
+    before_tile = np.concatenate(([0], np.cumsum(kept, dtype=np.int64)))
+
+    def coord(off: int, r: int) -> int:
+        lo = (off // 4096) * 4096
+        c = int(before_tile[off // 4096])
+        q = r
+        while q >= 0 and bodies[q, 1] > lo:
+            a, b = max(int(bodies[q, 0]), lo), min(int(bodies[q, 1]), off)
+            if b > a:
+                c += int(np.count_nonzero(~_DROP[buf[a:b]]))
+            q -= 1
+        return c
+
+    return [coord(int(e), r) - coord(int(b), r) for r, (b, e) in enumerate(bodies.tolist())]
+
+
 def write(path: str, records: List[Tuple[str, bytes]], width: int = 60) -> None:
     with open(path, "wb") as f:
         for rid, seq in records:

@@ -29,7 +29,7 @@ from typing import Dict, List, Optional, Sequence, Set, Tuple
 import numpy as np
 
 from . import hbm, hostio, phases, score
-from .device import Buffer, Engine, INDEL_SITE_DTYPE, JoinInput, REC_DTYPE, SITE_DTYPE, name_hash_np
+from .device import Buffer, Engine, INDEL_SITE_DTYPE, JoinInput, MISMATCH_SITE_DTYPE, REC_DTYPE, SITE_DTYPE, name_hash_np
 from . import _lib
 from ._lib import GciError, REC_HQ, REC_PASS
 from .formats import bam as bamfmt
@@ -913,6 +913,10 @@ def _drop_ahead(ahead) -> None:
     ahead[1].add_done_callback(done)
 
 
+class SeqNeeded(ValueError):
+    """bam_join_input(need_seq=True) with the `heads` ingest."""
+
+
 def _ingest_mode() -> str:                                      # (bam_join_input's `ingest`, where the caller does not say)
     return os.environ.get("GCI_BAM_INGEST", "gpu")
 
@@ -928,7 +932,7 @@ def _ref_sel(engine: Engine, hdr, targets: Sequence[str], own: Optional[Sequence
 
 
 def bam_join_input(engine: Engine, path: str, targets: Sequence[str], filt: Tuple[int, int, float, float],
-                   threads: int = 1, chunk_bytes: Optional[int] = None, ingest: Optional[str] = None) -> JoinInput:
+                   threads: int = 1, chunk_bytes: Optional[int] = None, ingest: Optional[str] = None, need_seq: bool = False) -> JoinInput:
     """K1 over one BAM file -> the file's join input (compact records + where their names are).
 
     ingest = "gpu" (default; GCI_BAM_INGEST overrides): the file's bytes are uploaded as they are and inflated on the
@@ -937,10 +941,14 @@ def bam_join_input(engine: Engine, path: str, targets: Sequence[str], filt: Tupl
     ingest = "heads": the native host pipeline (gci_bam_heads) inflates the file group by group and keeps every record
     without its SEQ / QUAL bytes; only that heads stream (about 400 B of a 27 KB HiFi record) is uploaded and filtered
     through its record pages; names stay addressable inside those (_ingest_heads).
-    ingest = "full" (or an explicit chunk_bytes): the whole stream, inflated on the host, goes to the device (_ingest_full)."""
+    ingest = "full" (or an explicit chunk_bytes): the whole stream, inflated on the host, goes to the device (_ingest_full).
+    need_seq: the visitor reads the records' SEQ bytes, which a heads stream does not hold: "heads" is refused (SeqNeeded), and a
+    "gpu" ingest that declines falls to "full"."""
     ingest = ingest or ("full" if chunk_bytes else _ingest_mode())
     if ingest not in ("heads", "full", "gpu"):
         raise ValueError("ingest must be 'heads', 'full' or 'gpu'")
+    if need_seq and ingest == "heads":
+        raise SeqNeeded("the reads' bases are needed and the `heads` ingest drops them: use GCI_BAM_INGEST=gpu or full")
     chunk_bytes = int(chunk_bytes or BAM_CHUNK_BYTES)
     nthreads = hostio.pick_threads(threads)
     ahead = _TABLES.pop(path, None)
@@ -955,7 +963,7 @@ def bam_join_input(engine: Engine, path: str, targets: Sequence[str], filt: Tupl
         if ji is not None:
             _drop_later(raw)                                  # (the unmapping, off this thread)
             return ji
-    if ingest != "full":
+    if ingest != "full" and not need_seq:
         ji = _ingest_heads(engine, raw, nthreads, ref_sel_for, filt)
     return ji if ji is not None else _ingest_full(engine, path, raw, nthreads, chunk_bytes, ref_sel_for, filt)
 
@@ -1348,7 +1356,8 @@ class _ClipVisitor(StreamVisitor):
     """_CoverVisitor with two more tracks: every piece goes through gci_bam_cover_* (the depth) and gci_bam_clip_* (the left and the
     right events), so a file is read once; three _IntervalCollectors with the flush and hand-over rules of _CoverVisitor."""
 
-    TRACKS = _CLIP_TRACKS                              # the two halves of the event call, then the depth
+    TRACKS = _CLIP_TRACKS                              # the parts of the event call (two halves here), then the depth
+    NEED_SEQ = False                                   # the event call reads SEQ: bam_join_input(need_seq=True)
     PHASE, CALL = "record clips", "gci_bam_clip_size"
 
     def __init__(self, main: Engine, opts: CoverOpts, min_bases: int, budget: int):
@@ -1366,7 +1375,7 @@ class _ClipVisitor(StreamVisitor):
     abort_file = begin_file
 
     def events(self, engine, d_stream, d_off, has_seq, ref_sel):
-        """-> (the first half, the second half, the three counts) of the piece."""
+        """-> (the parts of the piece, one per track in front of the depth, ..., the three counts)."""
         return engine.bam_clip(d_stream, d_off, has_seq, ref_sel, self.opts.excl, self.opts.min_mapq, self.min_bases)
 
     def visit(self, engine, d_stream, d_off, has_seq, ref_sel, rec_idx_base) -> None:
@@ -1381,13 +1390,13 @@ class _ClipVisitor(StreamVisitor):
             raise _file_record_error(engine, e, "gci_bam_cover_size", rec_idx_base) from None
         try:
             with phases.gpu(self.PHASE):
-                first, second, counts = self.events(engine, d_stream, d_off, has_seq, ref_sel)
+                *parts, counts = self.events(engine, d_stream, d_off, has_seq, ref_sel)
         except GciError as e:
             if e.rec < 0:
                 raise
             raise _file_record_error(engine, e, self.CALL, rec_idx_base) from None
         self.counts = [a + b for a, b in zip(self.counts, counts)]
-        for name, part in zip(self.TRACKS, (first, second, ivl)):
+        for name, part in zip(self.TRACKS, (*parts, ivl)):
             c = self.collectors[name]
             c.add(part)
             if c.n_ivl > self.budget:
@@ -1396,15 +1405,18 @@ class _ClipVisitor(StreamVisitor):
                 c.hand_over(self.main.stream)
 
     def file_done(self) -> Dict[str, Buffer]:
-        """The file's three tracks (the caller's engine and stream)."""
+        """The file's tracks by name (the caller's engine and stream)."""
         return {name: self.collectors[name].finish(self.main) for name in self.TRACKS}
 
 
 def _event_tracks(engine: Engine, bam_files: Sequence[str], chrs: Sequence[str], make_visitor, threads: int, wall: str,
-                  regions: Optional[Sequence[Tuple[str, int, int]]]):
-    """What bam_clip_sites and bam_indel_sites share: the layout of the first file's contigs (restricted by `chrs`), the TracksDoNotFit
-    check before anything is read, every file once through make_visitor(engine)'s three collectors, the files' tracks added up
-    -> (targets_length, the three summed tracks by name, counts per file, the visitor, the windows of `regions` in flat track elements
+                  regions: Optional[Sequence[Tuple[str, int, int]]], tracks: int = 3, bytes_per_base: int = 0):
+    """What bam_clip_sites, bam_indel_sites and bam_mismatch_sites share: the layout of the first file's contigs (restricted by `chrs`),
+    the TracksDoNotFit check before anything is read, make_visitor(engine) behind that check and in front of the first file, every
+    file once through the visitor's collectors (one per track), the files' tracks added up.  `tracks`: how many tracks the visitor
+    builds; `bytes_per_base`: what the run keeps per layout element next to them (the code array of bam_mismatch_sites), as the
+    check counts it
+    -> (targets_length, the summed tracks by name, counts per file, the visitor, the windows of `regions` in flat track elements
     -- None: `regions` holds no window of a selected contig)."""
     first = same_sq_table(bam_files)
     targets_length = _targets_of(first, list(chrs))
@@ -1412,11 +1424,12 @@ def _event_tracks(engine: Engine, bam_files: Sequence[str], chrs: Sequence[str],
     if not targets:
         raise ValueError("no contig selected")
     engine.set_layout([targets_length[t] for t in targets])
-    # three tracks, one more while intervals are built in parts -- and with several files a second set, the file's next to the sum of
-    # the files before it
-    n_tracks = 3 * (2 if len(bam_files) > 1 else 1) + 1
+    # the visitor's tracks, one more while intervals are built in parts -- and with several files a second set, the file's next to the
+    # sum of the files before it.  The FASTA text of reference_codes is not counted: it is on the device next to the code array only
+    # while no track exists yet and is about one byte per base, less than the tracks that follow it
+    n_tracks = tracks * (2 if len(bam_files) > 1 else 1) + 1
     track_bytes, free = 4 * int(engine.total), device_memory_free(engine)
-    if n_tracks * track_bytes > free:
+    if n_tracks * track_bytes + bytes_per_base * int(engine.total) > free:
         raise TracksDoNotFit(n_tracks, track_bytes, free)
     visitor = make_visitor(engine)
     totals: Dict[str, Buffer] = {}
@@ -1425,7 +1438,7 @@ def _event_tracks(engine: Engine, bam_files: Sequence[str], chrs: Sequence[str],
         visitor.begin_file()
         try:
             with phases.wall("%s[%s]" % (wall, os.path.basename(path))):
-                bam_join_input(engine, path, targets, visitor, threads)
+                bam_join_input(engine, path, targets, visitor, threads, need_seq=visitor.NEED_SEQ)
         except BaseException as e:
             visitor.abort_file()
             if isinstance(e, GciError):
@@ -1556,6 +1569,139 @@ def indel_summary_text(bam_files: Sequence[str], counts: Sequence[Sequence[int]]
     for k, (path, row) in enumerate(zip(bam_files, counts), 1):
         lines.append("%d\t%d\t%d\t%d\t%s" % (k, row[0], row[1], row[2], path))
     lines.append("total\t%d\t%d\t%d\t." % tuple(sum(int(row[j]) for row in counts) for j in range(3)))
+    lines.append("sites\t%d" % n_sites)
+    lines += ["%s\t%s" % (name, value) for name, value in options]
+    return "\n".join(lines) + "\n"
+
+
+# ==============================================================================================
+# mismatch_sites.py: bases where the reads disagree with the assembly
+# ==============================================================================================
+
+MISMATCH_MIN_READS = 3
+MISMATCH_MIN_FRAC = "0.5"                  # of the reads over the base: a choice, not a measurement
+_MISMATCH_TRACKS = ("mismatch", "depth")
+
+
+def parse_fraction_ppm(text: str) -> int:
+    """A decimal fraction between 0 and 1 with at most six digits behind the point -> parts per million, exactly (no float on the
+    way).  ValueError otherwise."""
+    import re
+    m = re.fullmatch(r"([0-9]+)(?:\.([0-9]{0,6}))?|\.([0-9]{1,6})", text.strip())
+    if not m:
+        raise ValueError("not a decimal fraction with at most six digits behind the point: `%s`" % text)
+    whole, frac = int(m.group(1) or 0), (m.group(2) or m.group(3) or "")
+    ppm = whole * 1000000 + int(frac.ljust(6, "0") or 0)
+    if ppm > 1000000:
+        raise ValueError("a fraction between 0 and 1 is needed: `%s`" % text)
+    return ppm
+
+
+class MismatchSites:
+    """What bam_mismatch_sites returns: mismatch / depth = the two DepthTracks (per base the counted records that carry another base
+    than the assembly there; the read-mapping depth), sites = device.MISMATCH_SITE_DTYPE [n] in contig order and then by position,
+    counts[k] = [records counted, mismatches, pairs compared] of file k, flushes as in ClipSites."""
+
+    def __init__(self, mismatch: DepthTracks, depth: DepthTracks, sites: np.ndarray, counts: List[List[int]], flushes: int):
+        self.mismatch, self.depth, self.sites, self.counts, self.flushes = mismatch, depth, sites, counts, flushes
+
+
+class ReferenceMismatch(ValueError):
+    """reference_codes: the FASTA file does not fit the @SQ table."""
+
+
+def reference_codes(engine: Engine, reference: str, targets_length: Dict[str, int]) -> Buffer:
+    """The assembly of `reference` as gci_fasta_codes lays it out for the engine's layout (the contigs of targets_length, in order).  The
+    FASTA ids are matched to the contigs by name: ReferenceMismatch (a ValueError) for an id that occurs twice, a contig the FASTA
+    does not hold, and a contig whose sequence is not as long as its @SQ LN -- the lengths come from the tile counts and are checked
+    before a code is written.  The FASTA text is on the device only inside this call."""
+    from .formats import fasta
+    buf, spans = fasta.indexed(reference)
+    index = {t: k for k, t in enumerate(targets_length)}
+    seen, dst = set(), []
+    for rid, _, _ in spans:
+        if rid in seen:
+            raise ReferenceMismatch(f"the id `{rid}` occurs twice in {reference}")
+        seen.add(rid)
+        dst.append(int(engine.offsets[index[rid]]) if rid in index else -1)
+    for t in targets_length:
+        if t not in seen:
+            raise ReferenceMismatch(f"contig `{t}` is not in {reference}")
+    bodies = np.array([(b, e) for _, b, e in spans], dtype=np.int64).reshape(-1, 2)
+
+    def check_lengths(kept: np.ndarray) -> None:           # (between the tile counts and the codes: what gci_fasta_codes leaves to its caller)
+        for (rid, _, _), n in zip(spans, fasta.body_lengths(buf, bodies, kept)):
+            if rid in index and n != int(targets_length[rid]):
+                raise ReferenceMismatch(f"contig `{rid}` has {n} bases in {reference} and LN:{int(targets_length[rid])} in the BAM header")
+
+    with phases.gpu("fasta codes"):
+        codes, _ = engine.fasta_codes(buf, bodies, np.asarray(dst, dtype=np.int64), before_codes=check_lengths)
+        engine.sync()                                      # (the walk engines read the codes in their own stream order)
+    return codes
+
+
+class _MismatchVisitor(_ClipVisitor):
+    """_ClipVisitor with gci_bam_mismatch_* as the event call: one event track next to the cover; the third count is the pairs compared."""
+
+    TRACKS = _MISMATCH_TRACKS
+    NEED_SEQ = True
+    PHASE, CALL = "record mismatches", "gci_bam_mismatch_size"
+
+    def __init__(self, main: Engine, opts: CoverOpts, codes: Buffer, budget: int):
+        super().__init__(main, opts, 1, budget)
+        self.codes = codes
+
+    def events(self, engine, d_stream, d_off, has_seq, ref_sel):
+        return engine.bam_mismatch(d_stream, d_off, has_seq, ref_sel, self.codes, self.opts.excl, self.opts.min_mapq)
+
+
+def bam_mismatch_sites(engine: Engine, reference: str, bam_files: Sequence[str], chrs: Sequence[str] = (), cover_opts: Optional[CoverOpts] = None,
+                       threads: int = 1, min_reads: int = MISMATCH_MIN_READS, min_frac: str = MISMATCH_MIN_FRAC,
+                       regions: Optional[Sequence[Tuple[str, int, int]]] = None, ivl_budget: Optional[int] = None) -> MismatchSites:
+    """The bases where the reads of `bam_files` carry another base than the assembly `reference` (include/gci_hip.h: gci_fasta_codes,
+    gci_bam_mismatch_size, gci_mismatch_sites_size): per base the counted records whose base there and the assembly's are both one of
+    A, C, G, T and differ, the read-mapping depth as bam_raw_depth counts it with the same options, and the runs of bases where the
+    mismatches reach `min_reads` and the share `min_frac` of the depth (a decimal text, or parts per million as an int).  Files,
+    contigs, regions and TracksDoNotFit as in bam_clip_sites; the assembly is checked against the @SQ table before a record is read
+    (reference_codes).  The reads' bases are needed: SeqNeeded with GCI_BAM_INGEST=heads."""
+    opts = cover_opts or CoverOpts()
+    frac_ppm = int(min_frac) if isinstance(min_frac, (int, np.integer)) else parse_fraction_ppm(str(min_frac))
+    if int(min_reads) < 1 or not 0 <= frac_ppm <= 1000000:
+        raise ValueError("min_reads is at least 1, min_frac between 0 and 1")
+    if _ingest_mode() == "heads":
+        raise SeqNeeded("the reads' bases are needed and the `heads` ingest drops them: use GCI_BAM_INGEST=gpu or full")
+    budget = COVER_IVL_BUDGET if ivl_budget is None else ivl_budget
+    first = same_sq_table(bam_files)
+
+    def make_visitor(e):
+        return _MismatchVisitor(e, opts, reference_codes(e, reference, _targets_of(first, list(chrs))), budget)
+
+    targets_length, totals, counts, visitor, windows = _event_tracks(engine, bam_files, chrs, make_visitor, threads, "bam_mismatch", regions,
+                                                                     tracks=2, bytes_per_base=1)
+    with phases.gpu("mismatch sites"):
+        if windows is None:
+            sites = np.zeros(0, dtype=MISMATCH_SITE_DTYPE)
+        else:
+            sites = engine.mismatch_sites(totals["mismatch"], totals["depth"], int(min_reads), frac_ppm, windows)
+    tracks = {name: DepthTracks(engine, targets_length, totals[name]) for name in _MISMATCH_TRACKS}
+    return MismatchSites(tracks["mismatch"], tracks["depth"], sites, counts, visitor.flushes)
+
+
+def mismatch_sites_bed(sites: np.ndarray, targets: Sequence[str]) -> str:
+    """`contig\\tstart\\tend\\tmismatch\\tdepth\\n` per site, no header line: a BED file bedgraph_cli.parse_regions reads."""
+    return "".join("%s\t%d\t%d\t%d\t%d\n" % (targets[c], a, b, m, d)
+                   for c, a, b, m, d in zip(*(sites[f].tolist() for f in ("contig", "start", "end", "mismatch", "depth"))))
+
+
+def mismatch_summary_text(bam_files: Sequence[str], counts: Sequence[Sequence[int]], n_sites: int, options: Sequence[Tuple[str, object]]) -> str:
+    """The text of {PREFIX}.mismatch.txt: per file and in total the records counted, the pairs compared, the mismatches and their
+    quotient; the sites; the options."""
+    def row(head, c, path):
+        return "%s\t%d\t%d\t%d\t%s\t%s" % (head, c[0], c[2], c[1], ("%.6f" % (c[1] / c[2])) if c[2] else "nan", path)
+    lines = ["#file\trecords\tcompared\tmismatches\trate\tpath"]
+    for k, (path, c) in enumerate(zip(bam_files, counts), 1):
+        lines.append(row(str(k), [int(x) for x in c], path))
+    lines.append(row("total", [sum(int(c[j]) for c in counts) for j in range(3)], "."))
     lines.append("sites\t%d" % n_sites)
     lines += ["%s\t%s" % (name, value) for name, value in options]
     return "\n".join(lines) + "\n"

@@ -359,13 +359,60 @@ _SEQ_NIBBLES = np.array([1, 2, 4, 8], dtype=np.uint8)                      # A C
 _SEQ_LUT = (_SEQ_NIBBLES[:, None] << 4 | _SEQ_NIBBLES[None, :]).reshape(16).astype(np.uint8)
 
 
+def random_reference(contigs: Sequence[Tuple[str, int]], seed: int = 0) -> Dict[str, np.ndarray]:
+    """{name: uint8 [length] of A / C / G / T}, uniformly random and seeded: an assembly for reads with real bases."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    return {name: _ACGT[rng.integers(0, 4, int(L), dtype=np.uint8)] for name, L in contigs}
+
+
+def write_fasta(path: str, reference: Dict[str, np.ndarray], width: int = 80) -> None:
+    with open(path, "wb") as f:
+        for name, seq in reference.items():
+            f.write(b">" + name.encode() + b" synthetic\n")
+            nfull = seq.shape[0] // width
+            if nfull:
+                body = np.empty((nfull, width + 1), dtype=np.uint8)
+                body[:, :width] = seq[:nfull * width].reshape(nfull, width)
+                body[:, width] = 10
+                f.write(body.tobytes())
+            if seq.shape[0] % width:
+                f.write(seq[nfull * width:].tobytes() + b"\n")
+
+
+_ACGT = np.frombuffer(b"ACGT", dtype=np.uint8)
+_ACGT_CODE = np.zeros(256, dtype=np.uint8)
+_ACGT_CODE[_ACGT] = (1, 2, 4, 8)
+
+
+def _read_codes(rs: ReadSet, g: int, reference: Dict[str, np.ndarray], rng: np.random.Generator, sub_rate: float) -> np.ndarray:
+    """The 4-bit codes of record g's l_seq bases: under M, = and X the reference's base, replaced by a random one with probability
+    sub_rate (and beyond the contig's end); random bases under I and S, and everywhere when the operations do not add up to l_seq."""
+    n = int(rs.l_seq[g])
+    letters = _ACGT[rng.integers(0, 4, n, dtype=np.uint8)]
+    ops = rs.cigar[rs.cigar_off[g]:rs.cigar_off[g + 1]]
+    op, ln = (ops & 0xF).astype(np.int64), (ops >> 4).astype(np.int64)
+    q_len = ln * np.isin(op, (OP_M, 1, OP_S, OP_EQ, OP_X))
+    r_len = ln * np.isin(op, (OP_M, OP_D, OP_N, OP_EQ, OP_X))
+    ref = reference.get(rs.contigs[int(rs.ref_id[g])][0]) if int(rs.ref_id[g]) >= 0 else None
+    if ref is not None and int(q_len.sum()) == n:
+        m = np.flatnonzero(np.isin(op, (OP_M, OP_EQ, OP_X)) & (ln > 0))
+        w = _within(ln[m])
+        at_q = np.repeat((np.cumsum(q_len) - q_len)[m], ln[m]) + w
+        at_r = np.repeat((int(rs.pos[g]) + np.cumsum(r_len) - r_len)[m], ln[m]) + w
+        keep = (at_r < ref.shape[0]) & (rng.random(at_r.shape[0]) >= sub_rate)
+        letters[at_q[keep]] = ref[at_r[keep]]
+    return _ACGT_CODE[letters]
+
+
 def to_bam_stream(rs: ReadSet, chunk: int = 1 << 18, header_text: Optional[str] = None, heads: bool = False,
-                  seq_qual: str = "const", seed: int = 0):
+                  seq_qual: str = "const", seed: int = 0, reference: Optional[Dict[str, np.ndarray]] = None, sub_rate: float = 0.0):
     """-> (inflated BAM stream uint8[n], record offsets uint64[R]).
 
     seq_qual = "const": SEQ / QUAL are 0xFF fill (the path never reads them; the file deflates 100:1).
     seq_qual = "random": uniformly random bases and HiFi-like qualities (`_hifi_qual_lut`), so that BGZF inflate costs
     what it costs on real data (bench.py's command-line timing).
+    seq_qual = "reference": the reads carry real bases -- under M, = and X those of `reference` (random_reference), each replaced by
+    a random base with probability `sub_rate`, seeded; QUAL stays 0xFF fill.
 
     heads=True: the heads stream of the same file (gci_bam_heads: every record without its SEQ / QUAL bytes,
     l_seq unchanged) -- what a genome-scale experiment can hold in memory.
@@ -405,6 +452,10 @@ def to_bam_stream(rs: ReadSet, chunk: int = 1 << 18, header_text: Optional[str] 
         out = np.full(int(offs[-1]), 0xFF, dtype=np.uint8)
     out[:hdr.shape[0]] = hdr
     span = np.maximum(rs.ref_span(), 1)
+    if seq_qual == "reference":
+        if reference is None:
+            raise ValueError('seq_qual="reference" needs the reference')
+        ref_rng = np.random.Generator(np.random.PCG64(seed))
 
     core = np.zeros(R, dtype=np.dtype([
         ("block_size", "<i4"), ("ref_id", "<i4"), ("pos", "<i4"), ("l_read_name", "u1"), ("mapq", "u1"),
@@ -453,6 +504,14 @@ def to_bam_stream(rs: ReadSet, chunk: int = 1 << 18, header_text: Optional[str] 
             for r in range(hi - lo):
                 if nb[r]:
                     out[p_seq[r]:p_seq[r] + nb[r]] = _SEQ_LUT[rng.integers(0, 16, int(nb[r]), dtype=np.uint8)]
+        if seq_qual == "reference" and not heads:
+            p_seq = p_cig + 4 * n_cig_field[sl]
+            for r in range(hi - lo):
+                if l_seq[lo + r]:
+                    codes = _read_codes(rs, lo + r, reference, ref_rng, sub_rate)
+                    if codes.shape[0] & 1:
+                        codes = np.concatenate((codes, np.zeros(1, dtype=np.uint8)))
+                    out[p_seq[r]:p_seq[r] + codes.shape[0] // 2] = (codes[0::2] << 4) | codes[1::2]
         # aux
         p_aux = p_cig + 4 * n_cig_field[sl] + seq_bytes[sl]
         last = rs.nm_last[sl]

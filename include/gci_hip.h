@@ -577,6 +577,74 @@ int gci_indel_sites_size(gci_ctx* ctx, const int32_t* d_del, const int32_t* d_in
 int gci_indel_sites_write(gci_ctx* ctx, const int32_t* d_del, const int32_t* d_ins, const int32_t* d_depth, int32_t min_reads,
                           const gci_window* h_windows, uint32_t n_windows, gci_indel_site* d_out, uint64_t cap);
 
+/* ---- mismatch_sites.py: bases where the reads carry another base than the assembly (k_mismatch.hip) -----------------------------------------
+ * gci_fasta_codes: the assembly as one code byte per base, indexed as the tracks are (contig offset + position).  Needs gci_layout_set.
+ *   input      d_text, n_bytes, d_body, n_records as gci_fasta_n_scan takes them (d_text 16-byte aligned, else GCI_E_INVALID), and
+ *              d_tile_kept0 = the exclusive scan of that call's d_tile_kept with the total behind it (tiles + 1 entries of uint64:
+ *              gci_dev_u32_scan_u64).  A sequence byte is gci_fasta_n_scan's: inside a record's body, not a line end, '\r' or blank.
+ *   d_dst[r]   int64: the flat element of d_codes where the first base of record r goes, -1 to leave the record out.  Base k of the
+ *              record goes to d_dst[r] + k; elements at or beyond gci_layout_total() are not written.  The caller has checked that
+ *              the record is as long as its contig: the call writes as many elements as the record has bases.
+ *   the code   of a byte: BAM's 4-bit encoding "=ACMGRSVTWYHKDBN" of the letter, case-insensitive: A = 1, C = 2, G = 4, T = 8, U / u
+ *              as T, the other IUPAC letters their BAM codes (N = 15); any other byte is 15.
+ *   d_codes    uint8, gci_layout_total() elements; every base is stored exactly once (its rank is the scanned tile count plus its
+ *              rank inside the 4096-byte tile); elements no base goes to keep what they held.  Asynchronous on the context's stream.
+ *
+ * gci_bam_mismatch_size / _write: the input of gci_bam_indel_size plus d_codes; has_seq must be 1 (else GCI_E_INVALID).  Per record:
+ *   counted    exactly when gci_bam_cover_size does not skip it with the same excl_flags (0x704 by default) and min_mapq.
+ *   operations the record's own, or the first CG:B,I / B,i array behind a <l_seq>S<n>N placeholder (the rule of gci_bam_indel_size).  SEQ
+ *              always lies behind the in-record CIGAR words, also in the CG case.
+ *   positions  the query position q starts at 0 and advances under M, =, X, I and S; the reference position p starts at pos and
+ *              advances under M, =, X, D and N, in 64 bits.  Under M, = and X query base q faces reference base p if p < L (the
+ *              contig's length, clamped as for gci_bam_indel_size; a d_ref_sel beyond the layout: 0).  The letter of the operation
+ *              does not matter: the bases decide.
+ *   codes      the read's is the SEQ nibble (the high nibble of byte q / 2 is the even q), the reference's is d_codes[offset + p].
+ *   compared   a facing pair whose two codes are each one of 1, 2, 4, 8.  A read nibble 0 ('='), N or another ambiguity code on
+ *              either side is never compared.
+ *   mismatch   a compared pair whose codes differ: one event gci_ivl{contig, p, p, 0}.
+ *   l_seq      == 0 (SEQ '*'): counted, nothing compared, no status.  l_seq > 0 and S + M + I over all operations != l_seq:
+ *              GCI_E_MALFORMED for that record, nothing of it is compared, no event, and no byte behind its SEQ is read.
+ *   *d_status  as gci_bam_indel_size reports it (smallest record index << 8 | -status): records out of bounds, operation codes 9 - 15
+ *              in a counted record (they move nothing), and the l_seq rule above.
+ *   h_counts   host, 3 entries: the records counted, the mismatch events, the pairs compared.  The size call synchronises.
+ * gci_bam_mismatch_write emits the events to d_out[0 .. h_counts[1]) in (record, reference position) order; ranks come from exclusive
+ * scans, ballots and popcounts, no atomics: two runs give the same bytes.  cap < h_counts[1]: GCI_E_CAPACITY, nothing is written.
+ * Another stream, n_bytes, offsets, n_rec or d_codes than the size call in front of it on this context measured: GCI_E_INVALID.
+ * gci_depth_build with flank 0 over the events gives the mismatch track: per base the counted records that carry another base there.
+ * Every mismatch lies on a base gci_bam_cover_size covers for the same record, so mismatch[b] <= depth[b] for the depth of the same
+ * options without count_del.
+ *
+ * gci_mismatch_sites_size / _write: the runs of hot elements of such a track against the depth track.
+ *   input      whole tracks of gci_layout_total() elements, 16-byte aligned (else GCI_E_INVALID); both are needed.
+ *   windows    as gci_indel_sites_size takes them.
+ *   hot        an element inside a window and inside its contig with mismatch >= min_reads and
+ *              mismatch * 1000000 >= frac_ppm * depth in 64-bit integers.  min_reads < 1, frac_ppm outside 0 .. 1000000: GCI_E_INVALID.
+ *   a site     a maximal run of consecutive hot elements of one contig inside one window, with the run rules of gci_indel_sites_size:
+ *              contig, start and end (exclusive) on the contig, mismatch = the maximum of the mismatch track over the run, depth =
+ *              the depth at the FIRST base of the run that reaches that maximum.  Sites come in ascending flat order.
+ *   write      the sites of the size call in front of it on this context (same tracks, min_reads, frac_ppm and n_windows, nothing
+ *              between the two that sets windows: else GCI_E_INVALID).  cap too small: GCI_E_CAPACITY, nothing is written.
+ * Both passes read both tracks, 16 bytes a lane; run starts are counted per tile, scanned and stored by rank; a wave per site walks
+ * the run.  No global atomics. */
+typedef struct gci_mismatch_site {
+    int32_t contig;
+    int32_t start;
+    int32_t end;
+    int32_t mismatch;
+    int32_t depth;
+} gci_mismatch_site;
+int gci_fasta_codes(gci_ctx* ctx, const uint8_t* d_text, uint64_t n_bytes, const int64_t* d_body, uint32_t n_records, const int64_t* d_dst,
+                    const uint64_t* d_tile_kept0, uint8_t* d_codes);
+int gci_bam_mismatch_size(gci_ctx* ctx, const uint8_t* d_stream, uint64_t n_bytes, const uint64_t* d_rec_off, uint32_t n_rec, int has_seq,
+                          const int32_t* d_ref_sel, int32_t n_ref, uint32_t excl_flags, int min_mapq, const uint8_t* d_codes, uint64_t* h_counts,
+                          uint64_t* d_status);
+int gci_bam_mismatch_write(gci_ctx* ctx, const uint8_t* d_stream, uint64_t n_bytes, const uint64_t* d_rec_off, uint32_t n_rec, int has_seq,
+                           const uint8_t* d_codes, gci_ivl* d_out, uint64_t cap, uint64_t* d_status);
+int gci_mismatch_sites_size(gci_ctx* ctx, const int32_t* d_mismatch, const int32_t* d_depth, int32_t min_reads, int32_t frac_ppm,
+                            const gci_window* h_windows, uint32_t n_windows, uint64_t* h_n_sites);
+int gci_mismatch_sites_write(gci_ctx* ctx, const int32_t* d_mismatch, const int32_t* d_depth, int32_t min_reads, int32_t frac_ppm,
+                             const gci_window* h_windows, uint32_t n_windows, gci_mismatch_site* d_out, uint64_t cap);
+
 /* Cross-rank name check for contig-sharded runs (exact).  gci_hash_bucket sorts the 64-bit name hashes of the
  * passing records into n_parts buckets by (hash >> 33) % n_parts; a bucket is part_cap + 1 uint64 words:
  * [0] = number of hashes the sender had for it (> part_cap: overflow), [1..] = the hashes.  After ONE all-to-all of
