@@ -82,8 +82,8 @@ extern "C" int gci_ctx_destroy(gci_ctx* ctx)
                       &ctx->win_tile_first, &ctx->text_lut, &ctx->long_items, &ctx->pg_scan, &ctx->pg_first, &ctx->pg_list, &ctx->route_tab, &ctx->deflate_nruns, &ctx->deflate_runs, &ctx->deflate_tab, &ctx->dgz_tiles, &ctx->build_nruns, &ctx->build_runs, &ctx->join_bucket, &ctx->tail_gaps, &ctx->tail_sums, &ctx->class_sums, &ctx->crc_tabs, &ctx->inflate_sym, &ctx->inflate_nsym, &ctx->inflate_wstatus, &ctx->inflate_lists, &ctx->inflate_prof, &ctx->inflate_next, &ctx->inflate_sym2, &ctx->inflate_lists2,
                       &ctx->bg_tile_cnt, &ctx->bg_tile_off, &ctx->bg_blk, &ctx->bg_wtab, &ctx->bg_blk_bytes, &ctx->bg_blk_off, &ctx->bg_blk2, &ctx->hist_chunk_first,
                       &ctx->cover_rec, &ctx->cover_chunk, &ctx->fate_rec, &ctx->fate_chunk, &ctx->reads_rec, &ctx->reads_chunk, &ctx->reads_names, &ctx->sweep_rec, &ctx->sweep_chunk,
-                      &ctx->clip_rec, &ctx->clip_chunk, &ctx->clip_tiles, &ctx->indel_rec, &ctx->indel_chunk, &ctx->indel_tiles,
-                      &ctx->mm_fasta, &ctx->mm_rec, &ctx->mm_chunk, &ctx->mm_tiles};
+                      &ctx->clip_rec, &ctx->clip_chunk, &ctx->indel_rec, &ctx->indel_chunk, &ctx->site_tiles,
+                      &ctx->mm_fasta, &ctx->mm_rec, &ctx->mm_chunk};
     for (DevBuf* b : bufs) if (b->p) (void)gci_dfree(b->p);
     for (DevBuf& b : ctx->paf_pool) if (b.p) (void)gci_dfree(b.p);
     if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);
@@ -211,9 +211,8 @@ extern "C" int gci_layout_set(gci_ctx* ctx, int32_t n, const int64_t* h_len)
     ctx->total = tiles * TILE;
     ctx->win_flank = INT32_MIN;
     ctx->bg_runs_epoch = 0; ctx->bg_text_run0 = nullptr;        // (k_bedgraph.hip: what the last count / size call measured is of another layout)
-    ctx->clip_valid = false; ctx->clip_sites_epoch = 0;         // (k_clips.hip: the same)
-    ctx->indel_valid = false; ctx->indel_sites_epoch = 0;       // (k_indels.hip: the same)
-    ctx->mm_valid = false; ctx->mm_sites_epoch = 0;             // (k_mismatch.hip: the same)
+    ctx->clip_valid = false; ctx->indel_valid = false; ctx->mm_valid = false;      // (k_clips.hip, k_indels.hip, k_mismatch.hip: the same)
+    ctx->site_memo.epoch = 0;                                   // (gci_site_tiles.hpp: the same)
     int r;
     if ((r = gci_ensure(ctx, ctx->d_len, n * 8))) return r;
     if ((r = gci_ensure(ctx, ctx->d_off, n * 8))) return r;

@@ -67,12 +67,13 @@ struct gci_ctx {
     const void* clip_stream = nullptr;
     const void* clip_off = nullptr;
     std::vector<gci_clip_site> sites;
-    bool sites_valid = false;
-    const void* sites_left = nullptr;
-    const void* sites_right = nullptr;
-    const void* sites_depth = nullptr;
-    int32_t sites_min_reads = 0;
-    uint32_t sites_windows = 0;
+    struct SiteAsk {                        // what a *_sites_size call measured: its _write call must ask the same
+        bool valid = false;
+        const void* track[3] = {nullptr, nullptr, nullptr};
+        int32_t min_reads = 0, frac = 0;
+        uint32_t n_windows = 0;
+    };
+    SiteAsk sites_ask;
     // indel_sites.py: the events the last gci_bam_indel_size found (deletions, then insertions, each in record and operation order)
     // and the sites the last gci_indel_sites_size found, with what each call measured
     std::vector<gci_ivl> indel_del, indel_ins;
@@ -83,12 +84,7 @@ struct gci_ctx {
     const void* indel_stream = nullptr;
     const void* indel_off = nullptr;
     std::vector<gci_indel_site> isites;
-    bool isites_valid = false;
-    const void* isites_del = nullptr;
-    const void* isites_ins = nullptr;
-    const void* isites_depth = nullptr;
-    int32_t isites_min_reads = 0;
-    uint32_t isites_windows = 0;
+    SiteAsk isites_ask;
     // mismatch_sites.py: the events the last gci_bam_mismatch_size found, in record and position order, and the sites the last
     // gci_mismatch_sites_size found, with what each call measured
     std::vector<gci_ivl> mm_events;
@@ -100,11 +96,7 @@ struct gci_ctx {
     const void* mm_off = nullptr;
     const void* mm_codes = nullptr;
     std::vector<gci_mismatch_site> msites;
-    bool msites_valid = false;
-    const void* msites_track = nullptr;
-    const void* msites_depth = nullptr;
-    int32_t msites_min_reads = 0, msites_frac = 0;
-    uint32_t msites_windows = 0;
+    SiteAsk msites_ask;
 };
 
 namespace {
@@ -271,12 +263,17 @@ int filter_record(const uint8_t* bam, uint64_t n_bytes, uint64_t off, const int3
     return GCI_OK;
 }
 
-// bam_depth.py, one record: bounds, the skip decision and where its operations lie (include/gci_hip.h: gci_bam_cover_size).
-// GCI_E_MALFORMED, or GCI_OK with r.contig < 0 for a skipped record.
+// bam_depth.py and the three site tools, one record: bounds, the skip decision and where its operations lie (include/gci_hip.h:
+// gci_bam_cover_size) -- the record's own, or the first CG:B,I / B,i array behind <l_seq>S (none usable: the record's own stay).
+// GCI_E_MALFORMED, or GCI_OK with r.contig < 0 for a skipped record.  sq: where SEQ lies (behind the in-record words, also in the CG
+// case) and l_seq.
+struct SeqAt { uint64_t seq_off; uint32_t l_seq; };
+
 int cover_parse(const uint8_t* bam, uint64_t n_bytes, uint64_t off, bool has_seq, const int32_t* ref_sel, int32_t n_ref, uint32_t excl_flags,
-                int min_mapq, gci_ctx::CoverRec& r)
+                int min_mapq, gci_ctx::CoverRec& r, SeqAt* sq = nullptr)
 {
     r.ops_off = 0; r.n_ops = 0; r.contig = -1; r.pos = 0;
+    if (sq) { sq->seq_off = 0; sq->l_seq = 0; }
     if (off > n_bytes || n_bytes - off < 36) return GCI_E_MALFORMED;
     const uint8_t* p = bam + off;
     const int32_t block_size = (int32_t)rd32(p), ref_id = (int32_t)rd32(p + 4), pos = (int32_t)rd32(p + 8);
@@ -290,6 +287,7 @@ int cover_parse(const uint8_t* bam, uint64_t n_bytes, uint64_t off, bool has_seq
     if (block_size < 32 || rec_end > n_bytes || l_seq < 0 || aux_off > rec_end) return GCI_E_MALFORMED;
     if ((flag & excl_flags) || mapq < min_mapq || ref_id < 0 || ref_id >= n_ref || pos < 0 || ref_sel[ref_id] < 0) return GCI_OK;
     r.contig = ref_sel[ref_id]; r.pos = pos; r.ops_off = cig_off; r.n_ops = n_cigar;
+    if (sq) { sq->seq_off = cig_off + 4ull * n_cigar; sq->l_seq = (uint32_t)l_seq; }
     if (n_cigar > 0) {                                                      // the CG:B,I placeholder, as filter_record restores it
         const uint32_t op0 = rd32(bam + cig_off);
         if ((op0 & 0xFu) == 4u && (op0 >> 4) == (uint32_t)l_seq) {
@@ -308,6 +306,45 @@ int cover_parse(const uint8_t* bam, uint64_t n_bytes, uint64_t off, bool has_seq
             }
         }
     }
+    return GCI_OK;
+}
+
+// the windows of a *_sites_size call: clamped to the track, none: every contig of the layout; false when not sorted and disjoint
+bool site_windows(const gci_ctx* ctx, const gci_window* h_windows, uint32_t n_windows, std::vector<gci_window>& ws)
+{
+    if (n_windows == 0) {
+        for (int32_t c = 0; c < ctx->n_contigs; c++) ws.push_back(gci_window{ctx->off[(size_t)c], ctx->off[(size_t)c] + ctx->len[(size_t)c]});
+        return true;
+    }
+    int64_t at = 0;
+    for (uint32_t i = 0; i < n_windows; i++) {
+        gci_window w = h_windows[i];
+        w.begin = std::max<int64_t>(w.begin, 0);
+        w.end = std::max(std::min(w.end, ctx->total), w.begin);
+        if (w.begin < at) return false;
+        at = w.end;
+        ws.push_back(w);
+    }
+    return true;
+}
+
+gci_ctx::SiteAsk site_ask(const void* a, const void* b, const void* c, int32_t min_reads, int32_t frac, uint32_t n_windows)
+{
+    gci_ctx::SiteAsk m;
+    m.valid = true; m.track[0] = a; m.track[1] = b; m.track[2] = c; m.min_reads = min_reads; m.frac = frac; m.n_windows = n_windows;
+    return m;
+}
+
+// a *_sites_write call: the sites its size call kept, when it asks what that call measured
+template <typename Site>
+int sites_write(const gci_ctx::SiteAsk& kept, const gci_ctx::SiteAsk& ask, const std::vector<Site>& sites, Site* out, uint64_t cap)
+{
+    if (!kept.valid || kept.track[0] != ask.track[0] || kept.track[1] != ask.track[1] || kept.track[2] != ask.track[2] ||
+        kept.min_reads != ask.min_reads || kept.frac != ask.frac || kept.n_windows != ask.n_windows)
+        return GCI_E_INVALID;
+    if (!sites.empty() && !out) return GCI_E_INVALID;
+    if (cap < sites.size()) return GCI_E_CAPACITY;
+    std::copy(sites.begin(), sites.end(), out);
     return GCI_OK;
 }
 
@@ -737,9 +774,9 @@ int gci_layout_set(gci_ctx* ctx, int32_t n_contigs, const int64_t* h_lengths)
     ctx->total = at > 0 ? at : GCI_TILE;
     ctx->n_contigs = n_contigs;
     ctx->bg_track = nullptr; ctx->bg_text_run0 = nullptr;
-    ctx->clip_valid = false; ctx->sites_valid = false;
-    ctx->indel_valid = false; ctx->isites_valid = false;
-    ctx->mm_valid = false; ctx->msites_valid = false;
+    ctx->clip_valid = false; ctx->sites_ask.valid = false;
+    ctx->indel_valid = false; ctx->isites_ask.valid = false;
+    ctx->mm_valid = false; ctx->msites_ask.valid = false;
     return GCI_OK;
 }
 int64_t gci_layout_total(gci_ctx* ctx) { return ctx ? ctx->total : 0; }
@@ -1125,38 +1162,16 @@ int gci_bam_clip_size(gci_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, const 
     uint64_t st = ~0ull, counted = 0;
     auto is_clip = [](uint32_t w) { return (w & 0xFu) == 4u || (w & 0xFu) == 5u; };       // S, H
     for (uint32_t i = 0; i < n_rec; i++) {
-        const uint64_t off = rec_off[i];
         const uint64_t word = ((uint64_t)i << 8) | (uint64_t)(uint8_t)(-GCI_E_MALFORMED);
-        if (off > n_bytes || n_bytes - off < 36) { st = std::min(st, word); continue; }
-        const uint8_t* p = bam + off;
-        const int32_t block_size = (int32_t)rd32(p), ref_id = (int32_t)rd32(p + 4), pos = (int32_t)rd32(p + 8);
-        const uint32_t l_read_name = p[12], n_cigar = rd16(p + 16), flag = rd16(p + 18);
-        const int mapq = p[13];
-        const int32_t l_seq = (int32_t)rd32(p + 20);
-        const uint64_t rec_end = off + 4 + (uint64_t)(uint32_t)block_size;
-        const uint64_t cig_off = off + 36 + l_read_name;
-        const uint64_t aux_off = cig_off + 4ull * n_cigar + (has_seq ? (((uint64_t)(uint32_t)l_seq + 1) >> 1) + (uint64_t)(uint32_t)l_seq : 0ull);
-        if (block_size < 32 || rec_end > n_bytes || l_seq < 0 || aux_off > rec_end) { st = std::min(st, word); continue; }
-        if ((flag & excl_flags) || mapq < min_mapq || ref_id < 0 || ref_id >= n_ref || pos < 0 || ref_sel[ref_id] < 0) continue;      // skipped
-        // the operations: the record's own, or the first CG:B,I / B,i array behind <l_seq>S (none usable: R counts as 0)
-        const uint8_t* ops = bam + cig_off;
-        uint64_t n = n_cigar;
-        if (n > 0 && (rd32(ops) & 0xFu) == 4u && (rd32(ops) >> 4) == (uint32_t)l_seq) {
-            n = 0;
-            const uint8_t* end = bam + rec_end;
-            for (const uint8_t* q = bam + aux_off; q + 3 <= end;) {
-                const int64_t sz = aux_value_size(q + 3, end, q[2]);
-                if (sz < 0 || q + 3 + sz > end) break;
-                if (q[0] == 'C' && q[1] == 'G') {
-                    if (q[2] == 'B' && (q[3] == 'I' || q[3] == 'i')) {
-                        const uint32_t cg_len = rd32(q + 4);
-                        if (cg_len >= n_cigar && cg_len < (1u << 29)) { ops = q + 8; n = cg_len; }
-                    }
-                    break;
-                }
-                q += 3 + sz;
-            }
-        }
+        gci_ctx::CoverRec r;
+        SeqAt sq;
+        if (cover_parse(bam, n_bytes, rec_off[i], has_seq != 0, ref_sel, n_ref, excl_flags, min_mapq, r, &sq) != GCI_OK) { st = std::min(st, word); continue; }
+        if (r.contig < 0) continue;                                         // skipped
+        // this tool's rule on top: <l_seq>S in front of the record's own operations -- the placeholder without a usable CG array -- is
+        // no clip: no operations, R counts as 0
+        const uint8_t* ops = bam + r.ops_off;
+        uint64_t n = r.n_ops;
+        if (n > 0 && r.ops_off + 4 * n == sq.seq_off && (rd32(ops) & 0xFu) == 4u && (rd32(ops) >> 4) == sq.l_seq) n = 0;
         uint64_t R = 0;
         bool bad = false;
         for (uint64_t k = 0; k < n; k++) {
@@ -1176,7 +1191,7 @@ int gci_bam_clip_size(gci_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, const 
             trail = rd32(ops + 4 * (n - 1)) >> 4;
             if (n > 1 && is_clip(rd32(ops + 4 * (n - 2)))) trail += rd32(ops + 4 * (n - 2)) >> 4;
         }
-        const int32_t contig = ref_sel[ref_id];
+        const int32_t contig = r.contig, pos = r.pos;
         const uint64_t L = contig < ctx->n_contigs ? (uint64_t)ctx->len[(size_t)contig] : 0;
         const uint64_t right = (uint64_t)pos + R - 1;
         if (lead >= (uint64_t)min_clip && (uint64_t)pos < L) ctx->clip_left.push_back(gci_ivl{contig, pos, pos, 0});
@@ -1212,22 +1227,10 @@ int gci_clip_sites_size(gci_ctx* ctx, const int32_t* left, const int32_t* right,
     const int lst = need_layout(ctx);
     if (lst) return lst;
     if ((((uintptr_t)left) | ((uintptr_t)right) | ((uintptr_t)depth)) & 15u) return GCI_E_INVALID;
-    ctx->sites_valid = false;
+    ctx->sites_ask.valid = false;
     *h_n_sites = 0;
     std::vector<gci_window> ws;
-    if (n_windows == 0) {
-        for (int32_t c = 0; c < ctx->n_contigs; c++) ws.push_back(gci_window{ctx->off[(size_t)c], ctx->off[(size_t)c] + ctx->len[(size_t)c]});
-    } else {
-        int64_t at = 0;
-        for (uint32_t i = 0; i < n_windows; i++) {
-            gci_window w = h_windows[i];
-            w.begin = std::max<int64_t>(w.begin, 0);
-            w.end = std::max(std::min(w.end, ctx->total), w.begin);
-            if (w.begin < at) return GCI_E_INVALID;                        // not sorted and disjoint
-            at = w.end;
-            ws.push_back(w);
-        }
-    }
+    if (!site_windows(ctx, h_windows, n_windows, ws)) return GCI_E_INVALID;   // not sorted and disjoint
     ctx->sites.clear();
     for (const gci_window& w : ws) {
         for (int64_t p = w.begin; p < w.end; p++) {
@@ -1238,8 +1241,7 @@ int gci_clip_sites_size(gci_ctx* ctx, const int32_t* left, const int32_t* right,
             ctx->sites.push_back(gci_clip_site{c, (int32_t)pos, left[p], right[p], depth ? depth[p] : 0, 0});
         }
     }
-    ctx->sites_valid = true; ctx->sites_left = left; ctx->sites_right = right; ctx->sites_depth = depth;
-    ctx->sites_min_reads = min_reads; ctx->sites_windows = n_windows;
+    ctx->sites_ask = site_ask(left, right, depth, min_reads, 0, n_windows);
     *h_n_sites = ctx->sites.size();
     return GCI_OK;
 }
@@ -1250,13 +1252,7 @@ int gci_clip_sites_write(gci_ctx* ctx, const int32_t* left, const int32_t* right
     if (!ctx || !left || !right || min_reads < 1 || (n_windows && !h_windows)) return GCI_E_INVALID;
     const int lst = need_layout(ctx);
     if (lst) return lst;
-    if (!ctx->sites_valid || left != ctx->sites_left || right != ctx->sites_right || depth != ctx->sites_depth || min_reads != ctx->sites_min_reads ||
-        n_windows != ctx->sites_windows)
-        return GCI_E_INVALID;
-    if (!ctx->sites.empty() && !out) return GCI_E_INVALID;
-    if (cap < ctx->sites.size()) return GCI_E_CAPACITY;
-    std::copy(ctx->sites.begin(), ctx->sites.end(), out);
-    return GCI_OK;
+    return sites_write(ctx->sites_ask, site_ask(left, right, depth, min_reads, 0, n_windows), ctx->sites, out, cap);
 }
 
 /* ---- indel_sites.py: long insertions and deletions in reads (k_indels.hip's twins, from the text of include/gci_hip.h: a record, an operation,
@@ -1271,39 +1267,15 @@ int gci_bam_indel_size(gci_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, const
     ctx->indel_del.clear(); ctx->indel_ins.clear();
     uint64_t st = ~0ull, counted = 0;
     for (uint32_t i = 0; i < n_rec; i++) {
-        const uint64_t off = rec_off[i];
         const uint64_t word = ((uint64_t)i << 8) | (uint64_t)(uint8_t)(-GCI_E_MALFORMED);
-        if (off > n_bytes || n_bytes - off < 36) { st = std::min(st, word); continue; }
-        const uint8_t* p = bam + off;
-        const int32_t block_size = (int32_t)rd32(p), ref_id = (int32_t)rd32(p + 4), pos = (int32_t)rd32(p + 8);
-        const uint32_t l_read_name = p[12], n_cigar = rd16(p + 16), flag = rd16(p + 18);
-        const int mapq = p[13];
-        const int32_t l_seq = (int32_t)rd32(p + 20);
-        const uint64_t rec_end = off + 4 + (uint64_t)(uint32_t)block_size;
-        const uint64_t cig_off = off + 36 + l_read_name;
-        const uint64_t aux_off = cig_off + 4ull * n_cigar + (has_seq ? (((uint64_t)(uint32_t)l_seq + 1) >> 1) + (uint64_t)(uint32_t)l_seq : 0ull);
-        if (block_size < 32 || rec_end > n_bytes || l_seq < 0 || aux_off > rec_end) { st = std::min(st, word); continue; }
-        if ((flag & excl_flags) || mapq < min_mapq || ref_id < 0 || ref_id >= n_ref || pos < 0 || ref_sel[ref_id] < 0) continue;      // skipped
+        gci_ctx::CoverRec r;
+        SeqAt sq;
+        if (cover_parse(bam, n_bytes, rec_off[i], has_seq != 0, ref_sel, n_ref, excl_flags, min_mapq, r, &sq) != GCI_OK) { st = std::min(st, word); continue; }
+        if (r.contig < 0) continue;                                         // skipped
         counted++;
-        // the operations: the record's own, or the first CG:B,I / B,i array behind <l_seq>S (none usable: the record's own stay)
-        const uint8_t* ops = bam + cig_off;
-        uint64_t n = n_cigar;
-        if (n > 0 && (rd32(ops) & 0xFu) == 4u && (rd32(ops) >> 4) == (uint32_t)l_seq) {
-            const uint8_t* end = bam + rec_end;
-            for (const uint8_t* q = bam + aux_off; q + 3 <= end;) {
-                const int64_t sz = aux_value_size(q + 3, end, q[2]);
-                if (sz < 0 || q + 3 + sz > end) break;
-                if (q[0] == 'C' && q[1] == 'G') {
-                    if (q[2] == 'B' && (q[3] == 'I' || q[3] == 'i')) {
-                        const uint32_t cg_len = rd32(q + 4);
-                        if (cg_len >= n_cigar && cg_len < (1u << 29)) { ops = q + 8; n = cg_len; }
-                    }
-                    break;
-                }
-                q += 3 + sz;
-            }
-        }
-        const int32_t contig = ref_sel[ref_id];
+        const uint8_t* ops = bam + r.ops_off;
+        const uint64_t n = r.n_ops;
+        const int32_t contig = r.contig, pos = r.pos;
         const uint64_t L = contig < ctx->n_contigs ? std::min<uint64_t>((uint64_t)ctx->len[(size_t)contig], 0x7FFFFFFEull) : 0;
         uint64_t at = (uint64_t)pos;
         bool bad = false;
@@ -1352,22 +1324,10 @@ int gci_indel_sites_size(gci_ctx* ctx, const int32_t* del, const int32_t* ins, c
     const int lst = need_layout(ctx);
     if (lst) return lst;
     if ((((uintptr_t)del) | ((uintptr_t)ins) | ((uintptr_t)depth)) & 15u) return GCI_E_INVALID;
-    ctx->isites_valid = false;
+    ctx->isites_ask.valid = false;
     *h_n_sites = 0;
     std::vector<gci_window> ws;
-    if (n_windows == 0) {
-        for (int32_t c = 0; c < ctx->n_contigs; c++) ws.push_back(gci_window{ctx->off[(size_t)c], ctx->off[(size_t)c] + ctx->len[(size_t)c]});
-    } else {
-        int64_t at = 0;
-        for (uint32_t i = 0; i < n_windows; i++) {
-            gci_window w = h_windows[i];
-            w.begin = std::max<int64_t>(w.begin, 0);
-            w.end = std::max(std::min(w.end, ctx->total), w.begin);
-            if (w.begin < at) return GCI_E_INVALID;                        // not sorted and disjoint
-            at = w.end;
-            ws.push_back(w);
-        }
-    }
+    if (!site_windows(ctx, h_windows, n_windows, ws)) return GCI_E_INVALID;   // not sorted and disjoint
     ctx->isites.clear();
     for (const gci_window& w : ws) {
         bool open = false;                                                  // a run never crosses from one window into the next
@@ -1387,8 +1347,7 @@ int gci_indel_sites_size(gci_ctx* ctx, const int32_t* del, const int32_t* ins, c
             if (depth) s.depth = std::max(s.depth, depth[p]);
         }
     }
-    ctx->isites_valid = true; ctx->isites_del = del; ctx->isites_ins = ins; ctx->isites_depth = depth;
-    ctx->isites_min_reads = min_reads; ctx->isites_windows = n_windows;
+    ctx->isites_ask = site_ask(del, ins, depth, min_reads, 0, n_windows);
     *h_n_sites = ctx->isites.size();
     return GCI_OK;
 }
@@ -1399,13 +1358,7 @@ int gci_indel_sites_write(gci_ctx* ctx, const int32_t* del, const int32_t* ins, 
     if (!ctx || !del || !ins || min_reads < 1 || (n_windows && !h_windows)) return GCI_E_INVALID;
     const int lst = need_layout(ctx);
     if (lst) return lst;
-    if (!ctx->isites_valid || del != ctx->isites_del || ins != ctx->isites_ins || depth != ctx->isites_depth || min_reads != ctx->isites_min_reads ||
-        n_windows != ctx->isites_windows)
-        return GCI_E_INVALID;
-    if (!ctx->isites.empty() && !out) return GCI_E_INVALID;
-    if (cap < ctx->isites.size()) return GCI_E_CAPACITY;
-    std::copy(ctx->isites.begin(), ctx->isites.end(), out);
-    return GCI_OK;
+    return sites_write(ctx->isites_ask, site_ask(del, ins, depth, min_reads, 0, n_windows), ctx->isites, out, cap);
 }
 
 /* ---- mismatch_sites.py: bases where the reads carry another base than the assembly (k_mismatch.hip's twins, from the text of
@@ -1446,38 +1399,16 @@ int gci_bam_mismatch_size(gci_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, co
     ctx->mm_events.clear();
     uint64_t st = ~0ull, counted = 0, compared = 0;
     for (uint32_t i = 0; i < n_rec; i++) {
-        const uint64_t off = rec_off[i];
         const uint64_t word = ((uint64_t)i << 8) | (uint64_t)(uint8_t)(-GCI_E_MALFORMED);
-        if (off > n_bytes || n_bytes - off < 36) { st = std::min(st, word); continue; }
-        const uint8_t* p = bam + off;
-        const int32_t block_size = (int32_t)rd32(p), ref_id = (int32_t)rd32(p + 4), pos = (int32_t)rd32(p + 8);
-        const uint32_t l_read_name = p[12], n_cigar = rd16(p + 16), flag = rd16(p + 18);
-        const int mapq = p[13];
-        const int32_t l_seq = (int32_t)rd32(p + 20);
-        const uint64_t rec_end = off + 4 + (uint64_t)(uint32_t)block_size;
-        const uint64_t cig_off = off + 36 + l_read_name;
-        const uint64_t aux_off = cig_off + 4ull * n_cigar + (((uint64_t)(uint32_t)l_seq + 1) >> 1) + (uint64_t)(uint32_t)l_seq;
-        if (block_size < 32 || rec_end > n_bytes || l_seq < 0 || aux_off > rec_end) { st = std::min(st, word); continue; }
-        if ((flag & excl_flags) || mapq < min_mapq || ref_id < 0 || ref_id >= n_ref || pos < 0 || ref_sel[ref_id] < 0) continue;      // skipped
+        gci_ctx::CoverRec r;
+        SeqAt sq;
+        if (cover_parse(bam, n_bytes, rec_off[i], true, ref_sel, n_ref, excl_flags, min_mapq, r, &sq) != GCI_OK) { st = std::min(st, word); continue; }
+        if (r.contig < 0) continue;                                         // skipped
         counted++;
-        const uint8_t* ops = bam + cig_off;
-        const uint8_t* seq = ops + 4ull * n_cigar;                              // behind the in-record words, also in the CG case
-        uint64_t n = n_cigar;
-        if (n > 0 && (rd32(ops) & 0xFu) == 4u && (rd32(ops) >> 4) == (uint32_t)l_seq) {
-            const uint8_t* end = bam + rec_end;
-            for (const uint8_t* q = bam + aux_off; q + 3 <= end;) {
-                const int64_t sz = aux_value_size(q + 3, end, q[2]);
-                if (sz < 0 || q + 3 + sz > end) break;
-                if (q[0] == 'C' && q[1] == 'G') {
-                    if (q[2] == 'B' && (q[3] == 'I' || q[3] == 'i')) {
-                        const uint32_t cg_len = rd32(q + 4);
-                        if (cg_len >= n_cigar && cg_len < (1u << 29)) { ops = q + 8; n = cg_len; }
-                    }
-                    break;
-                }
-                q += 3 + sz;
-            }
-        }
+        const uint8_t* ops = bam + r.ops_off;
+        const uint8_t* seq = bam + sq.seq_off;
+        const uint64_t n = r.n_ops;
+        const uint32_t l_seq = sq.l_seq;
         // first pass: codes 9 - 15 and the query length
         bool bad = false;
         uint64_t qlen = 0;
@@ -1489,7 +1420,7 @@ int gci_bam_mismatch_size(gci_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, co
         if (l_seq > 0 && qlen != (uint64_t)l_seq) bad = true;
         if (bad) st = std::min(st, word);
         if (l_seq == 0 || qlen != (uint64_t)l_seq) continue;                    // nothing of it is compared
-        const int32_t contig = ref_sel[ref_id];
+        const int32_t contig = r.contig, pos = r.pos;
         const uint64_t L = contig < ctx->n_contigs ? std::min<uint64_t>((uint64_t)ctx->len[(size_t)contig], 0x7FFFFFFEull) : 0;
         const uint8_t* ref = L ? codes + ctx->off[(size_t)contig] : codes;
         uint64_t at = (uint64_t)pos, q = 0;
@@ -1539,22 +1470,10 @@ int gci_mismatch_sites_size(gci_ctx* ctx, const int32_t* mm, const int32_t* dept
     const int lst = need_layout(ctx);
     if (lst) return lst;
     if ((((uintptr_t)mm) | ((uintptr_t)depth)) & 15u) return GCI_E_INVALID;
-    ctx->msites_valid = false;
+    ctx->msites_ask.valid = false;
     *h_n_sites = 0;
     std::vector<gci_window> ws;
-    if (n_windows == 0) {
-        for (int32_t c = 0; c < ctx->n_contigs; c++) ws.push_back(gci_window{ctx->off[(size_t)c], ctx->off[(size_t)c] + ctx->len[(size_t)c]});
-    } else {
-        int64_t at = 0;
-        for (uint32_t i = 0; i < n_windows; i++) {
-            gci_window w = h_windows[i];
-            w.begin = std::max<int64_t>(w.begin, 0);
-            w.end = std::max(std::min(w.end, ctx->total), w.begin);
-            if (w.begin < at) return GCI_E_INVALID;                        // not sorted and disjoint
-            at = w.end;
-            ws.push_back(w);
-        }
-    }
+    if (!site_windows(ctx, h_windows, n_windows, ws)) return GCI_E_INVALID;   // not sorted and disjoint
     ctx->msites.clear();
     for (const gci_window& w : ws) {
         bool open = false;                                                  // a run never crosses from one window into the next
@@ -1573,8 +1492,7 @@ int gci_mismatch_sites_size(gci_ctx* ctx, const int32_t* mm, const int32_t* dept
             if (mm[p] > s.mismatch) { s.mismatch = mm[p]; s.depth = depth[p]; }   // the first base that reaches the maximum
         }
     }
-    ctx->msites_valid = true; ctx->msites_track = mm; ctx->msites_depth = depth;
-    ctx->msites_min_reads = min_reads; ctx->msites_frac = frac_ppm; ctx->msites_windows = n_windows;
+    ctx->msites_ask = site_ask(mm, depth, nullptr, min_reads, frac_ppm, n_windows);
     *h_n_sites = ctx->msites.size();
     return GCI_OK;
 }
@@ -1585,13 +1503,7 @@ int gci_mismatch_sites_write(gci_ctx* ctx, const int32_t* mm, const int32_t* dep
     if (!ctx || !mm || !depth || min_reads < 1 || (n_windows && !h_windows)) return GCI_E_INVALID;
     const int lst = need_layout(ctx);
     if (lst) return lst;
-    if (!ctx->msites_valid || mm != ctx->msites_track || depth != ctx->msites_depth || min_reads != ctx->msites_min_reads || frac_ppm != ctx->msites_frac ||
-        n_windows != ctx->msites_windows)
-        return GCI_E_INVALID;
-    if (!ctx->msites.empty() && !out) return GCI_E_INVALID;
-    if (cap < ctx->msites.size()) return GCI_E_CAPACITY;
-    std::copy(ctx->msites.begin(), ctx->msites.end(), out);
-    return GCI_OK;
+    return sites_write(ctx->msites_ask, site_ask(mm, depth, nullptr, min_reads, frac_ppm, n_windows), ctx->msites, out, cap);
 }
 
 /* ---- filter_reads.py: the records of chosen classes over a set of regions as rows of text (k_reads.hip's twins: a record at a time) ---- */

@@ -1,6 +1,7 @@
 // gci_cover_chunks.hpp -- the CIGAR of a BAM stream as CHUNKS of at most GCI_COVER_CHUNK_OPS operations, one wave each: what the
 // kernels that walk whole CIGARs share (k_cover.hip: the covered bases; k_fate.hip: the base totals of the record filter's two
-// quotients; k_indels.hip, k_mismatch.hip: the events of a walk, with cv_parse_counted as their one record parse).  A lane per
+// quotients; k_clips.hip, k_indels.hip, k_mismatch.hip: the events of a record or of a walk), with cv_parse_counted as the one record
+// parse of k_cover.hip and those three, and RecFrame as the head of their per-record scratch.  A lane per
 // record says where the record's operations lie and how many chunks they make (CoverRec), an exclusive scan of the chunk counts
 // numbers the chunks, and a wave finds its record (cv_rec_of_chunk), its piece of the operation array (cv_chunk_of) and its
 // operation words, 64 a round (cv_op_word).
@@ -59,7 +60,8 @@ struct CvSeq {
     uint32_t pad;
 };
 
-// One lane per record, what k_indel_parse and k_mm_parse share: bounds, core fields, the skip rule of gci_bam_cover_size, where the
+// One lane per record, what k_cover_parse, k_clip_parse, k_indel_parse and k_mm_parse share: bounds, core fields, the skip rule of
+// gci_bam_cover_size, where the
 // operations lie (own CIGAR or the first CG:B,I / B,i array behind a <l_seq>S<n>N placeholder) and how many chunks they make.
 // contig >= 0: the record is counted, with or without operations.  A record out of bounds is reported and makes no chunk.
 __device__ __forceinline__ CoverRec cv_parse_counted(const uint8_t* __restrict__ bam, uint64_t n_bytes, uint64_t off, uint32_t i, int has_seq,
@@ -91,8 +93,9 @@ __device__ __forceinline__ CoverRec cv_parse_counted(const uint8_t* __restrict__
             r.n_ops = n_cigar;
             sq.seq_off = cig_off + 4ull * n_cigar;     // (with has_seq its (l_seq + 1) / 2 bytes end at or before aux_off <= rec_end)
             sq.l_seq = (uint32_t)l_seq;
-            // <l_seq>S in front: the operations are the first CG:B,I (or B,i) array, as k_cover_parse walks to it; without a usable one
-            // the placeholder's own S and N stay
+            // a CIGAR of more than 65535 operations lies in CG:B,I (or B,i) behind the placeholder <l_seq>S<n>N: the rule of
+            // formats/bam.py::decode_record and the record filter (the FIRST CG tag counts, bam_aux_get); without a usable one the
+            // placeholder's own S and N stay
             if (n_cigar > 0) {
                 const uint32_t op0 = cv_rd32(bam + cig_off);
                 if ((op0 & 0xFu) == 4u && (op0 >> 4) == (uint32_t)l_seq) {
@@ -115,6 +118,59 @@ __device__ __forceinline__ CoverRec cv_parse_counted(const uint8_t* __restrict__
         }
     }
     return r;
+}
+
+// The head of the per-record scratch of k_clips.hip, k_indels.hip and k_mismatch.hip, carved out of a DevBuf of rec_frame_bytes(n_rec)
+// + whatever the tool appends at `tail` (8-byte aligned).
+struct RecFrame {
+    unsigned long long* status;
+    unsigned long long* chunk0;          // n_rec + 1: exclusive scan of the chunk counts
+    unsigned long long* cnt0;            // n_rec + 1: exclusive scan of `counted`
+    CoverRec* recs;
+    unsigned long long* blk;
+    uint32_t* nch;
+    uint32_t* counted;
+    uint8_t* tail;
+};
+
+static inline size_t rec_frame_bytes(uint32_t n_rec)
+{
+    const size_t n = n_rec;
+    return 16 + 2 * 8 * (n + 1) + sizeof(CoverRec) * n + 8 * (scan_blocks(n) + 2) + 2 * 4 * n;
+}
+
+static inline RecFrame rec_frame(const DevBuf& buf, uint32_t n_rec)
+{
+    const size_t n = n_rec;
+    RecFrame s;
+    uint8_t* p = (uint8_t*)buf.p;
+    s.status = (unsigned long long*)p; p += 16;
+    s.chunk0 = (unsigned long long*)p; p += 8 * (n + 1);
+    s.cnt0 = (unsigned long long*)p; p += 8 * (n + 1);
+    s.recs = (CoverRec*)p; p += sizeof(CoverRec) * n;
+    s.blk = (unsigned long long*)p; p += 8 * (scan_blocks(n) + 2);
+    s.nch = (uint32_t*)p; p += 4 * n;
+    s.counted = (uint32_t*)p; p += 4 * n;
+    s.tail = p;
+    return s;
+}
+
+// what opens a *_size call over records: the scratch, and the status word at "nothing to report"
+static inline int rec_frame_open(gci_ctx* ctx, DevBuf& buf, size_t tail_bytes, uint32_t n_rec, RecFrame& F)
+{
+    GCI_TRY(gci_ensure(ctx, buf, rec_frame_bytes(n_rec) + tail_bytes));
+    F = rec_frame(buf, n_rec);
+    HIPCHK(hipMemsetAsync(F.status, 0xFF, 8, ctx->stream));
+    return GCI_OK;
+}
+
+// ... and what follows its parse: the chunks numbered, their count on the host (n_rec > 0)
+static inline int rec_frame_chunks(gci_ctx* ctx, const RecFrame& F, uint32_t n_rec, unsigned long long& n_chunks)
+{
+    GCI_TRY((device_exclusive_scan<uint32_t, unsigned long long>(ctx, F.nch, F.chunk0, F.blk, (int64_t)n_rec, true)));
+    HIPCHK(hipMemcpyAsync(&n_chunks, F.chunk0 + n_rec, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return n_chunks > 0x7FFFFFFFull ? GCI_E_INVALID : GCI_OK;                // (2^42 operations in one call)
 }
 
 // the record of chunk c: the largest i with chunk0[i] <= c (records without chunks share their value with the record behind them)

@@ -30,6 +30,20 @@ struct DevBuf {
     size_t cap = 0;
 };
 
+// block totals a device_exclusive_scan over n entries needs (its callers add 2), and the grid of a kernel that gives every one of n
+// items a wave
+static inline size_t scan_blocks(uint64_t n) { return (size_t)((n + TILE - 1) / TILE); }
+static inline dim3 wave_grid(unsigned long long n) { return dim3((uint32_t)((n + BLOCK / 64 - 1) / (BLOCK / 64))); }
+
+// gci_site_tiles.hpp: what the last *_sites_size call of any lister measured, for the *_sites_write call that follows it
+struct SiteMemo {
+    int lister = 0;                         // the Emit type's LISTER: 1 clips, 2 indels, 3 mismatch
+    uint64_t epoch = 0, total = 0;          // ctx->win_epoch of its windows (0: no size call yet), its sites
+    const void* track[3] = {nullptr, nullptr, nullptr};
+    int32_t min_reads = 0, frac = 0;
+    uint32_t n_windows = 0;
+};
+
 struct gci_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -151,50 +165,35 @@ struct gci_ctx {
     DevBuf sweep_rec, sweep_chunk;          // k_sweep.hip: per record (parse, NM, window, chunk counts and their scan) + the table, and per chunk (base sums)
     uint32_t sweep_grid_cap = 0;            // GCI_SWEEP_GRID=<n>: at most n workgroups for k_sweep_bin (testing; 0: what the device holds)
     // k_clips.hip: what gci_bam_clip_size keeps for gci_bam_clip_write -- per record (parse, end clips, events, ranks, right site) and
-    // per chunk (base sums) --, and what gci_clip_sites_size keeps for gci_clip_sites_write -- per window tile its sites and their scan
-    DevBuf clip_rec, clip_chunk, clip_tiles;
+    // per chunk (base sums)
+    DevBuf clip_rec, clip_chunk;
     bool clip_valid = false;
     uint32_t clip_n_rec = 0;
     uint64_t clip_n_left = 0, clip_n_right = 0;
     const void* clip_stream = nullptr;
     const void* clip_off = nullptr;
-    uint64_t clip_sites_epoch = 0, clip_sites_total = 0;      // (epoch 0: no size call yet)
-    const void* clip_sites_left = nullptr;
-    const void* clip_sites_right = nullptr;
-    const void* clip_sites_depth = nullptr;
-    int32_t clip_sites_min_reads = 0;
-    uint32_t clip_sites_windows = 0;
     // k_indels.hip: what gci_bam_indel_size keeps for gci_bam_indel_write -- per record (parse, chunk counts, counted) and per chunk
-    // (base sums, reference length, deletions, insertions and their scans) --, and what gci_indel_sites_size keeps for
-    // gci_indel_sites_write -- per window tile its run starts and their scan
-    DevBuf indel_rec, indel_chunk, indel_tiles;
+    // (base sums, reference length, deletions, insertions and their scans)
+    DevBuf indel_rec, indel_chunk;
     bool indel_valid = false;
     uint32_t indel_n_rec = 0;
     int indel_min_len = 0;
     uint64_t indel_n_bytes = 0, indel_n_chunks = 0, indel_n_del = 0, indel_n_ins = 0;
     const void* indel_stream = nullptr;
     const void* indel_off = nullptr;
-    uint64_t indel_sites_epoch = 0, indel_sites_total = 0;    // (epoch 0: no size call yet)
-    const void* indel_sites_del = nullptr;
-    const void* indel_sites_ins = nullptr;
-    const void* indel_sites_depth = nullptr;
-    int32_t indel_sites_min_reads = 0;
-    uint32_t indel_sites_windows = 0;
     // k_mismatch.hip: the records' ranks of gci_fasta_codes; what gci_bam_mismatch_size keeps for gci_bam_mismatch_write -- per record
-    // (parse, SEQ, chunk counts, counted) and per chunk (base sums, the two lengths, mismatches, pairs and their scans) --, and what
-    // gci_mismatch_sites_size keeps for gci_mismatch_sites_write
-    DevBuf mm_fasta, mm_rec, mm_chunk, mm_tiles;
+    // (parse, SEQ, chunk counts, counted) and per chunk (base sums, the two lengths, mismatches, pairs and their scans)
+    DevBuf mm_fasta, mm_rec, mm_chunk;
     bool mm_valid = false;
     uint32_t mm_n_rec = 0;
     uint64_t mm_n_bytes = 0, mm_n_chunks = 0, mm_n_mm = 0;
     const void* mm_stream = nullptr;
     const void* mm_off = nullptr;
     const void* mm_codes = nullptr;
-    uint64_t mm_sites_epoch = 0, mm_sites_total = 0;          // (epoch 0: no size call yet)
-    const void* mm_sites_track = nullptr;
-    const void* mm_sites_depth = nullptr;
-    int32_t mm_sites_min_reads = 0, mm_sites_frac = 0;
-    uint32_t mm_sites_windows = 0;
+    // gci_site_tiles.hpp: what gci_{clip,indel,mismatch}_sites_size keeps for the _write call -- per window tile its sites or run starts
+    // and their scan, and the one memo.  Every size call runs gci_set_windows, so what another lister left here is dead by then
+    DevBuf site_tiles;
+    SiteMemo site_memo;
     void* h_pinned = nullptr;               // staging for small uploads
     size_t h_pinned_cap = 0;
     // optional per-kernel HIP-event timing (gci_profile_*)
@@ -602,7 +601,7 @@ int gci_launch_contig_text_off(gci_ctx* ctx, const uint64_t* tile_off, uint64_t*
 // the windows of an issue scan, clamped to the track, with their tiles: ctx->win, win_tile_first (n_win + 1 entries), win_n, win_tiles
 int gci_set_windows(gci_ctx* ctx, const gci_window* h_win, uint32_t n_win);
 
-// the windows of a sites call (k_clips.hip, k_indels.hip) on the host: clamped as gci_set_windows clamps them, none: every contig of the
+// the windows of a sites call (gci_site_tiles.hpp: site_size) on the host: clamped as gci_set_windows clamps them, none: every contig of the
 // layout; false when they are not sorted and disjoint
 static inline bool gci_site_windows(const gci_ctx* ctx, const gci_window* h_windows, uint32_t n_windows, std::vector<gci_window>& ws)
 {

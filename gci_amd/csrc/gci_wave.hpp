@@ -47,6 +47,17 @@ __device__ __forceinline__ T wave_sum(T v)
     }
 }
 
+template <typename T>
+__device__ __forceinline__ T wave_max(T v)
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) { const T o = __shfl_xor(v, m, 64); v = o > v ? o : v; }
+    return v;
+}
+
+// the lanes below `lane`, as a ballot's mask
+__device__ __forceinline__ unsigned long long lanes_below(int lane) { return (1ull << lane) - 1ull; }
+
 // ---- workgroup exclusive scan -----------------------------------------------------------------------
 // Exclusive prefix of `v` over the NWAVES * 64 threads of a one-dimensional workgroup, and in `total` the sum over all of
 // them: a wave scan, the wave totals through LDS, then the totals of the waves in front.  All threads of the workgroup call it.

@@ -5,59 +5,39 @@
 //
 // The record side.  Input as for gci_bam_cover_size; the CIGAR work is k_reads.hip's: a CHUNK of at most GCI_COVER_CHUNK_OPS operations
 // is a wave's, never a record's (gci_cover_chunks.hpp, gci_cigar_sums.hpp).
-//   k_clip_parse    one lane per record: bounds, core fields, the skip rule, where the operations lie (own CIGAR or CG array) and how
-//                   many chunks they make; the at most four END operations are read here, directly: lead and trail
+//   k_clip_parse    one lane per record: cv_parse_counted (bounds, core fields, the skip rule, where the operations lie -- own CIGAR
+//                   or CG array -- and how many chunks they make), this file's rule for a placeholder without its array, and the at
+//                   most four END operations, read here, directly: lead and trail
 //   k_cigar_sums    one wave per chunk: the bases under M / = / X, D and N (R is their sum), codes 9 - 15; no atomics
 //   k_clip_decide   one lane per record: adds its chunks' sums, decides the two events and where the right one lies
 //   k_clip_write    one lane per record: its events to the rank an exclusive scan gave them -- left and right ranks packed into one
 //                   64-bit word, so one scan serves both -- : record order, no atomics
 // with the project's exclusive scan between them (chunks per record; events and counted records per record).
 //
-// The track side.  K8's windows and tiling (gci_set_windows, 4096-element tiles, int4 loads, elements outside [begin, end) or in the
-// padding behind a contig masked off).
-//   k_clip_sites_count   one workgroup per window tile: the left and right tracks, 16 bytes a lane, one count per tile
-//   k_clip_sites_write   one workgroup per window tile, gone at once when the tile's count is 0 (nearly every tile of a genome): a
-//                        thread takes 16 consecutive elements, a workgroup scan ranks them, the depth track is read here only
+// The track side.  gci_site_tiles.hpp's lister over the left and right tracks: the hot ELEMENTS (HotEither, RUNS = false), counted by
+// k_sites_count and written by k_sites_write; the depth track is read by ClipEmit only, where there is a site.
 #include "gci_cigar_sums.hpp"
+#include "gci_site_tiles.hpp"
 
-struct ClipScratch {                     // carved out of ctx->clip_rec
-    unsigned long long* status;
-    unsigned long long* chunk0;          // n_rec + 1: exclusive scan of the chunk counts
+struct ClipScratch : RecFrame {          // carved out of ctx->clip_rec: the frame, and behind it
     unsigned long long* ev;              // the events of a record: 1 = left, 1 << 32 = right
     unsigned long long* ev0;             // n_rec + 1: its exclusive scan -- left rank in the low word, right rank in the high one
-    unsigned long long* cnt0;            // n_rec + 1: exclusive scan of `counted`
-    CoverRec* recs;
-    unsigned long long* blk;
     uint2* ends;                         // lead, trail
     int32_t* rsite;                      // where the right event lies
-    uint32_t* nch;
-    uint32_t* counted;
 };
 
-static inline size_t cl_blocks(uint64_t n) { return (size_t)((n + TILE - 1) / TILE); }
+static inline size_t cl_tail_bytes(uint32_t n_rec) { return 8 * ((size_t)n_rec + 1) + (8 + 8 + 4) * (size_t)n_rec; }
 
-static inline size_t cl_rec_bytes(uint32_t n_rec)
-{
-    const size_t n = n_rec;
-    return 16 + 3 * 8 * (n + 1) + 8 * n + sizeof(CoverRec) * n + 8 * (cl_blocks(n) + 2) + 8 * n + 3 * 4 * n;
-}
-
-static inline ClipScratch cl_scratch(gci_ctx* ctx, uint32_t n_rec)
+static inline ClipScratch cl_scratch(const RecFrame& F, uint32_t n_rec)
 {
     const size_t n = n_rec;
     ClipScratch s;
-    uint8_t* p = (uint8_t*)ctx->clip_rec.p;
-    s.status = (unsigned long long*)p; p += 16;
-    s.chunk0 = (unsigned long long*)p; p += 8 * (n + 1);
+    static_cast<RecFrame&>(s) = F;
+    uint8_t* p = F.tail;
     s.ev0 = (unsigned long long*)p; p += 8 * (n + 1);
-    s.cnt0 = (unsigned long long*)p; p += 8 * (n + 1);
     s.ev = (unsigned long long*)p; p += 8 * n;
-    s.recs = (CoverRec*)p; p += sizeof(CoverRec) * n;
-    s.blk = (unsigned long long*)p; p += 8 * (cl_blocks(n) + 2);
     s.ends = (uint2*)p; p += 8 * n;
-    s.rsite = (int32_t*)p; p += 4 * n;
-    s.nch = (uint32_t*)p; p += 4 * n;
-    s.counted = (uint32_t*)p;
+    s.rsite = (int32_t*)p;
     return s;
 }
 
@@ -71,59 +51,26 @@ __global__ __launch_bounds__(BLOCK) void k_clip_parse(const uint8_t* __restrict_
 {
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n_rec) return;
-    CoverRec r;
-    r.ops_off = 0; r.n_ops = 0; r.contig = -1; r.pos = 0; r.pad = 0;
-    uint32_t chunks = 0, lead = 0, trail = 0;
-    const uint64_t off = rec_off[i];
-    if (off > n_bytes || n_bytes - off < 36) {
-        cv_report(status, i, GCI_E_MALFORMED);
-    } else {
-        const uint8_t* p = bam + off;
-        const int32_t block_size = (int32_t)cv_rd32(p), ref_id = (int32_t)cv_rd32(p + 4), pos = (int32_t)cv_rd32(p + 8);
-        const uint32_t l_read_name = p[12];
-        const int mapq = p[13];
-        const uint32_t n_cigar = cv_rd16(p + 16), flag = cv_rd16(p + 18);
-        const int32_t l_seq = (int32_t)cv_rd32(p + 20);
-        const uint64_t rec_end = off + 4 + (uint64_t)(uint32_t)block_size;
-        const uint64_t cig_off = off + 36 + l_read_name;
-        const uint64_t aux_off = cig_off + 4ull * n_cigar + (has_seq ? (((uint64_t)(uint32_t)l_seq + 1) >> 1) + (uint64_t)(uint32_t)l_seq : 0ull);
-        if (block_size < 32 || rec_end > n_bytes || l_seq < 0 || aux_off > rec_end) {
-            cv_report(status, i, GCI_E_MALFORMED);
-        } else if (!(flag & excl_flags) && mapq >= min_mapq && ref_id >= 0 && ref_id < n_ref && pos >= 0 && ref_sel[ref_id] >= 0 && n_cigar > 0) {
-            uint64_t ops_off = cig_off;
-            uint32_t n_ops = n_cigar;
-            // <l_seq>S in front: the operations are the first CG:B,I (or B,i) array, as k_cover_parse walks to it -- or, without a usable
-            // one, nothing: R counts as 0 and the record is skipped
-            const uint32_t op0 = cv_rd32(bam + cig_off);
-            if ((op0 & 0xFu) == 4u && (op0 >> 4) == (uint32_t)l_seq) {
-                n_ops = 0;
-                const uint8_t* end = bam + rec_end;
-                for (const uint8_t* q = bam + aux_off; q + 3 <= end;) {
-                    const int64_t sz = cv_aux_size(q + 3, end, q[2]);
-                    if (sz < 0 || q + 3 + sz > end) break;
-                    if (q[0] == 'C' && q[1] == 'G') {
-                        if (q[2] == 'B' && (q[3] == 'I' || q[3] == 'i')) {
-                            const uint32_t cg_len = cv_rd32(q + 4);
-                            if (cg_len >= n_cigar && cg_len < (1u << 29)) { ops_off = (uint64_t)(q + 8 - bam); n_ops = cg_len; }
-                        }
-                        break;
-                    }
-                    q += 3 + sz;
-                }
+    CvSeq sq;
+    uint32_t chunks, lead = 0, trail = 0;
+    CoverRec r = cv_parse_counted(bam, n_bytes, rec_off[i], i, has_seq, ref_sel, n_ref, excl_flags, min_mapq, status, chunks, sq);
+    if (r.n_ops > 0) {
+        const uint8_t* ops = bam + r.ops_off;          // (every operation word lies inside the record: cv_parse_counted)
+        const uint32_t a0 = cv_rd32(ops), z0 = cv_rd32(ops + 4ull * (r.n_ops - 1));
+        // This file's rule, NOT cover's and indels' (tests/clips_ref.py states it): <l_seq>S in front of the record's OWN operations
+        // -- a placeholder without a usable CG array; with one the operations lie behind SEQ -- is no clip of l_seq bases.  The record
+        // has no operations, R counts as 0 and it is not counted.
+        if (r.ops_off + 4ull * r.n_ops == sq.seq_off && (a0 & 0xFu) == 4u && (a0 >> 4) == sq.l_seq) {
+            r.n_ops = 0;
+            chunks = 0;
+        } else {
+            if (cl_is_clip(a0)) {
+                lead = a0 >> 4;
+                if (r.n_ops > 1) { const uint32_t a1 = cv_rd32(ops + 4); if (cl_is_clip(a1)) lead += a1 >> 4; }
             }
-            if (n_ops > 0) {                           // (every operation word lies inside the record: aux_off <= rec_end, q + 3 + sz <= end)
-                r.contig = ref_sel[ref_id]; r.pos = pos; r.ops_off = ops_off; r.n_ops = n_ops;
-                chunks = (n_ops + CV_OPS - 1) / CV_OPS;
-                const uint8_t* ops = bam + ops_off;
-                const uint32_t a0 = cv_rd32(ops), z0 = cv_rd32(ops + 4ull * (n_ops - 1));
-                if (cl_is_clip(a0)) {
-                    lead = a0 >> 4;
-                    if (n_ops > 1) { const uint32_t a1 = cv_rd32(ops + 4); if (cl_is_clip(a1)) lead += a1 >> 4; }
-                }
-                if (cl_is_clip(z0)) {
-                    trail = z0 >> 4;
-                    if (n_ops > 1) { const uint32_t z1 = cv_rd32(ops + 4ull * (n_ops - 2)); if (cl_is_clip(z1)) trail += z1 >> 4; }
-                }
+            if (cl_is_clip(z0)) {
+                trail = z0 >> 4;
+                if (r.n_ops > 1) { const uint32_t z1 = cv_rd32(ops + 4ull * (r.n_ops - 2)); if (cl_is_clip(z1)) trail += z1 >> 4; }
             }
         }
     }
@@ -203,19 +150,16 @@ extern "C" int gci_bam_clip_size(gci_ctx* ctx, const uint8_t* d_stream, uint64_t
     if (!ctx->n_contigs) return GCI_E_NO_LAYOUT;
     ctx->clip_valid = false;
     h_counts[0] = h_counts[1] = h_counts[2] = 0;
-    GCI_TRY(gci_ensure(ctx, ctx->clip_rec, cl_rec_bytes(n_rec)));
-    const ClipScratch R = cl_scratch(ctx, n_rec);
-    HIPCHK(hipMemsetAsync(R.status, 0xFF, 8, ctx->stream));
+    RecFrame F;
+    GCI_TRY(rec_frame_open(ctx, ctx->clip_rec, cl_tail_bytes(n_rec), n_rec, F));
+    const ClipScratch R = cl_scratch(F, n_rec);
     unsigned long long n_chunks = 0, n_ev = 0, n_counted = 0;
     if (n_rec) {
         const uint32_t groups = (n_rec + BLOCK - 1) / BLOCK;
         hipLaunchKernelGGL(k_clip_parse, dim3(groups), dim3(BLOCK), 0, ctx->stream, d_stream, n_bytes, d_rec_off, n_rec, has_seq, d_ref_sel, n_ref,
                            excl_flags, min_mapq, R.recs, R.nch, R.ends, R.status);
         LAUNCHCHK("k_clip_parse");
-        GCI_TRY((device_exclusive_scan<uint32_t, unsigned long long>(ctx, R.nch, R.chunk0, R.blk, (int64_t)n_rec, true)));
-        HIPCHK(hipMemcpyAsync(&n_chunks, R.chunk0 + n_rec, 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        if (n_chunks > 0x7FFFFFFFull) return GCI_E_INVALID;                  // (2^42 operations in one call)
+        GCI_TRY(rec_frame_chunks(ctx, R, n_rec, n_chunks));
         CigarSums* sums = nullptr;
         if (n_chunks) {
             GCI_TRY(gci_ensure(ctx, ctx->clip_chunk, sizeof(CigarSums) * (size_t)n_chunks));
@@ -252,7 +196,7 @@ extern "C" int gci_bam_clip_write(gci_ctx* ctx, const uint8_t* d_stream, uint64_
     const unsigned long long total = ctx->clip_n_left + ctx->clip_n_right;
     if (total && !d_out) return GCI_E_INVALID;
     if (cap < total) return GCI_E_CAPACITY;
-    const ClipScratch R = cl_scratch(ctx, n_rec);
+    const ClipScratch R = cl_scratch(rec_frame(ctx->clip_rec, n_rec), n_rec);
     if (n_rec && total) {
         hipLaunchKernelGGL(k_clip_write, dim3((n_rec + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, ctx->stream, n_rec, R.recs, R.ev, R.ev0, R.rsite,
                            (unsigned long long)ctx->clip_n_left, total, d_out);
@@ -263,105 +207,27 @@ extern "C" int gci_bam_clip_write(gci_ctx* ctx, const uint8_t* d_stream, uint64_
 }
 
 // ---- the track side ---------------------------------------------------------------------------------------------------------------
-struct ClipTile {
-    int64_t p0;                          // the tile's first element (a multiple of TILE)
-    int64_t lo, hi;                      // the elements of it that are inside the window AND inside their contig
-    int64_t contig_off;
-    int32_t contig;
+struct ClipEmit {
+    static constexpr int LISTER = 1;
+    static constexpr bool RUNS = false;
+    const int32_t* left;
+    const int32_t* right;
+    const int32_t* depth;
+    gci_clip_site* out;
+    __device__ __forceinline__ void operator()(unsigned long long slot, const SiteTile& x, int64_t q) const
+    {
+        gci_clip_site s;
+        s.contig = x.contig; s.pos = (int32_t)(q - x.contig_off);
+        s.left = left[q]; s.right = right[q]; s.depth = depth ? depth[q] : 0; s.pad = 0;
+        out[slot] = s;
+    }
 };
 
-__device__ __forceinline__ ClipTile clip_tile_of(const gci_window* __restrict__ win, const int64_t* __restrict__ win_tile_first, int32_t n_win,
-                                                 int64_t wt, const int64_t* __restrict__ off, const int64_t* __restrict__ len,
-                                                 const int64_t* __restrict__ tile_first, int32_t n_contigs)
+static inline SiteMemo cl_site_ask(const int32_t* d_left, const int32_t* d_right, const int32_t* d_depth, int32_t min_reads, uint32_t n_windows)
 {
-    ClipTile x;
-    const int32_t w = contig_of_tile(win_tile_first, n_win, wt);
-    const gci_window W = win[w];
-    x.p0 = (W.begin / TILE + (wt - win_tile_first[w])) * TILE;
-    x.contig = contig_of_tile(tile_first, n_contigs, x.p0 / TILE);
-    x.contig_off = off[x.contig];
-    x.lo = max(x.p0, W.begin);
-    x.hi = min(min(x.p0 + TILE, W.end), x.contig_off + len[x.contig]);
-    return x;
-}
-
-__global__ __launch_bounds__(BLOCK) void k_clip_sites_count(const int32_t* __restrict__ left, const int32_t* __restrict__ right,
-                                                            const gci_window* __restrict__ win, const int64_t* __restrict__ win_tile_first,
-                                                            int32_t n_win, const int64_t* __restrict__ off, const int64_t* __restrict__ len,
-                                                            const int64_t* __restrict__ tile_first, int32_t n_contigs, int32_t min_reads,
-                                                            uint32_t* __restrict__ tile_cnt)
-{
-    __shared__ uint32_t part[BLOCK / 64];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const ClipTile x = clip_tile_of(win, win_tile_first, n_win, blockIdx.x, off, len, tile_first, n_contigs);
-    uint32_t n = 0;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const int64_t p = x.p0 + (int64_t)(j * BLOCK + t) * 4;
-        const int4 a = *reinterpret_cast<const int4*>(left + p), b = *reinterpret_cast<const int4*>(right + p);
-        const int32_t l[4] = {a.x, a.y, a.z, a.w}, r[4] = {b.x, b.y, b.z, b.w};
-#pragma unroll
-        for (int k = 0; k < 4; k++) n += (p + k >= x.lo && p + k < x.hi && (l[k] >= min_reads || r[k] >= min_reads)) ? 1u : 0u;
-    }
-    n = wave_sum<uint32_t>(n);
-    if (lane == 0) part[wave] = n;
-    __syncthreads();
-    if (t == 0) {
-        uint32_t all = 0;
-#pragma unroll
-        for (int w = 0; w < BLOCK / 64; w++) all += part[w];
-        tile_cnt[blockIdx.x] = all;
-    }
-}
-
-__global__ __launch_bounds__(BLOCK) void k_clip_sites_write(const int32_t* __restrict__ left, const int32_t* __restrict__ right,
-                                                            const int32_t* __restrict__ depth, const gci_window* __restrict__ win,
-                                                            const int64_t* __restrict__ win_tile_first, int32_t n_win,
-                                                            const int64_t* __restrict__ off, const int64_t* __restrict__ len,
-                                                            const int64_t* __restrict__ tile_first, int32_t n_contigs, int32_t min_reads,
-                                                            const uint32_t* __restrict__ tile_cnt, const unsigned long long* __restrict__ tile_off,
-                                                            gci_clip_site* __restrict__ out, unsigned long long total)
-{
-    __shared__ uint32_t wtot[BLOCK / 64];
-    if (tile_cnt[blockIdx.x] == 0) return;             // (the whole workgroup)
-    const int t = threadIdx.x;
-    const ClipTile x = clip_tile_of(win, win_tile_first, n_win, blockIdx.x, off, len, tile_first, n_contigs);
-    const int64_t p = x.p0 + (int64_t)t * 16;          // a thread's 16 consecutive elements: ascending order is thread order
-    uint32_t flags = 0;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const int4 a = *reinterpret_cast<const int4*>(left + p + 4 * j), b = *reinterpret_cast<const int4*>(right + p + 4 * j);
-        const int32_t l[4] = {a.x, a.y, a.z, a.w}, r[4] = {b.x, b.y, b.z, b.w};
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int64_t q = p + 4 * j + k;
-            flags |= (q >= x.lo && q < x.hi && (l[k] >= min_reads || r[k] >= min_reads)) ? (1u << (4 * j + k)) : 0u;
-        }
-    }
-    uint32_t all;
-    const uint32_t pre = block_exclusive<uint32_t, BLOCK / 64>((uint32_t)__builtin_popcount(flags), wtot, all);
-    unsigned long long slot = tile_off[blockIdx.x] + pre;
-    while (flags) {                                    // (few: a genome has thousands of sites)
-        const int k = __builtin_ctz(flags);
-        flags &= flags - 1u;
-        gci_clip_site s;
-        s.contig = x.contig; s.pos = (int32_t)(p + k - x.contig_off);
-        s.left = left[p + k]; s.right = right[p + k]; s.depth = depth ? depth[p + k] : 0; s.pad = 0;
-        if (slot < total) out[slot] = s;
-        slot++;
-    }
-}
-
-struct ClipTileScratch { uint32_t* cnt; unsigned long long* off; unsigned long long* blk; };
-
-static inline ClipTileScratch cl_tile_scratch(gci_ctx* ctx, int64_t tiles)
-{
-    ClipTileScratch s;
-    uint8_t* p = (uint8_t*)ctx->clip_tiles.p;
-    s.off = (unsigned long long*)p; p += 8 * ((size_t)tiles + 1);
-    s.blk = (unsigned long long*)p; p += 8 * (cl_blocks((uint64_t)tiles) + 2);
-    s.cnt = (uint32_t*)p;
-    return s;
+    SiteMemo m;
+    m.track[0] = d_left; m.track[1] = d_right; m.track[2] = d_depth; m.min_reads = min_reads; m.n_windows = n_windows;
+    return m;
 }
 
 extern "C" int gci_clip_sites_size(gci_ctx* ctx, const int32_t* d_left, const int32_t* d_right, const int32_t* d_depth, int32_t min_reads,
@@ -370,32 +236,8 @@ extern "C" int gci_clip_sites_size(gci_ctx* ctx, const int32_t* d_left, const in
     if (!ctx || !d_left || !d_right || !h_n_sites || min_reads < 1 || (n_windows && !h_windows)) return GCI_E_INVALID;
     if (!ctx->n_contigs) return GCI_E_NO_LAYOUT;
     if ((((uintptr_t)d_left) | ((uintptr_t)d_right) | ((uintptr_t)d_depth)) & 15u) return GCI_E_INVALID;      // whole tracks, as allocated
-    if (n_windows >= (1u << 31)) return GCI_E_INVALID;
-    std::vector<gci_window> ws;
-    if (!gci_site_windows(ctx, h_windows, n_windows, ws)) return GCI_E_INVALID;
-    ctx->clip_sites_epoch = 0;
-    *h_n_sites = 0;
-    GCI_TRY(gci_set_windows(ctx, ws.data(), (uint32_t)ws.size()));
-    ctx->win_flank = INT32_MIN;
-    const int64_t tiles = ctx->win_tiles;
-    if (tiles > 0x7FFFFFFFll) return GCI_E_INVALID;
-    unsigned long long total = 0;
-    if (tiles) {
-        GCI_TRY(gci_ensure(ctx, ctx->clip_tiles, 8 * ((size_t)tiles + 1) + 8 * (cl_blocks((uint64_t)tiles) + 2) + 4 * (size_t)tiles));
-        const ClipTileScratch T = cl_tile_scratch(ctx, tiles);
-        hipLaunchKernelGGL(k_clip_sites_count, dim3((uint32_t)tiles), dim3(BLOCK), 0, ctx->stream, d_left, d_right, (const gci_window*)ctx->win.p,
-                           (const int64_t*)ctx->win_tile_first.p, (int32_t)ctx->win_n, (const int64_t*)ctx->d_off.p, (const int64_t*)ctx->d_len.p,
-                           (const int64_t*)ctx->d_tile_first.p, ctx->n_contigs, min_reads, T.cnt);
-        LAUNCHCHK("k_clip_sites_count");
-        GCI_TRY((device_exclusive_scan<uint32_t, unsigned long long>(ctx, T.cnt, T.off, T.blk, tiles, true)));
-        HIPCHK(hipMemcpyAsync(&total, T.off + tiles, 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-    }
-    ctx->clip_sites_epoch = ctx->win_epoch; ctx->clip_sites_total = total;
-    ctx->clip_sites_left = d_left; ctx->clip_sites_right = d_right; ctx->clip_sites_depth = d_depth;
-    ctx->clip_sites_min_reads = min_reads; ctx->clip_sites_windows = n_windows;
-    *h_n_sites = total;
-    return GCI_OK;
+    return site_size<ClipEmit>(ctx, HotEither{d_left, d_right, min_reads}, cl_site_ask(d_left, d_right, d_depth, min_reads, n_windows),
+                                       h_windows, h_n_sites, "k_sites_count (clips)");
 }
 
 extern "C" int gci_clip_sites_write(gci_ctx* ctx, const int32_t* d_left, const int32_t* d_right, const int32_t* d_depth, int32_t min_reads,
@@ -403,19 +245,6 @@ extern "C" int gci_clip_sites_write(gci_ctx* ctx, const int32_t* d_left, const i
 {
     if (!ctx || !d_left || !d_right || min_reads < 1 || (n_windows && !h_windows)) return GCI_E_INVALID;
     if (!ctx->n_contigs) return GCI_E_NO_LAYOUT;
-    // not what gci_clip_sites_size measured last on this context, or its windows are no longer the context's
-    if (!ctx->clip_sites_epoch || ctx->clip_sites_epoch != ctx->win_epoch || d_left != ctx->clip_sites_left || d_right != ctx->clip_sites_right ||
-        d_depth != ctx->clip_sites_depth || min_reads != ctx->clip_sites_min_reads || n_windows != ctx->clip_sites_windows)
-        return GCI_E_INVALID;
-    const unsigned long long total = ctx->clip_sites_total;
-    if (total && !d_out) return GCI_E_INVALID;
-    if (cap < total) return GCI_E_CAPACITY;
-    const int64_t tiles = ctx->win_tiles;
-    if (!tiles || !total) return GCI_OK;
-    const ClipTileScratch T = cl_tile_scratch(ctx, tiles);
-    hipLaunchKernelGGL(k_clip_sites_write, dim3((uint32_t)tiles), dim3(BLOCK), 0, ctx->stream, d_left, d_right, d_depth, (const gci_window*)ctx->win.p,
-                       (const int64_t*)ctx->win_tile_first.p, (int32_t)ctx->win_n, (const int64_t*)ctx->d_off.p, (const int64_t*)ctx->d_len.p,
-                       (const int64_t*)ctx->d_tile_first.p, ctx->n_contigs, min_reads, T.cnt, T.off, d_out, total);
-    LAUNCHCHK("k_clip_sites_write");
-    return GCI_OK;
+    return site_write(ctx, HotEither{d_left, d_right, min_reads}, cl_site_ask(d_left, d_right, d_depth, min_reads, n_windows),
+                                        ClipEmit{d_left, d_right, d_depth, d_out}, d_out, cap, "k_sites_write (clips)");
 }

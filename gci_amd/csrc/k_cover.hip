@@ -5,8 +5,9 @@
 //
 // Input as for gci_bam_filter: the inflated stream (or a heads stream) and the record offsets.  The unit of work is a CHUNK of at
 // most GCI_COVER_CHUNK_OPS CIGAR operations, never a record: an ONT record holds 10^3 - 10^5 operations.  Three steps:
-//   k_cover_parse   one lane per record: bounds, the skip decision (flag, MAPQ, refID, pos, contig), where the operations lie (the
-//                   record's own CIGAR, or the CG:B,I array behind a <l_seq>S<n>N placeholder) and how many chunks they make
+//   k_cover_parse   one lane per record: cv_parse_counted -- bounds, the skip decision (flag, MAPQ, refID, pos, contig), where the
+//                   operations lie (the record's own CIGAR, or the CG:B,I array behind a <l_seq>S<n>N placeholder) and how many
+//                   chunks they make --, then the class mask
 //   k_cover_count   one wave per chunk: the chunk's reference length, its intervals, operation codes 9 - 15
 //   k_cover_write   one wave per chunk: the same walk with positions (reference lengths scanned across the lanes, 64 operations a
 //                   round), one interval per maximal run of covering operations inside the chunk
@@ -33,11 +34,9 @@ struct CoverChunkScratch {         // carved out of ctx->cover_chunk
     uint32_t* cnt;
 };
 
-static inline size_t cv_blocks(uint64_t n) { return (size_t)((n + TILE - 1) / TILE); }
-
 static inline size_t cv_rec_bytes(uint32_t n_rec)
 {
-    return 16 + 8 * ((size_t)n_rec + 1) + sizeof(CoverRec) * (size_t)n_rec + 8 * (cv_blocks(n_rec) + 2) + 4 * (size_t)n_rec;
+    return 16 + 8 * ((size_t)n_rec + 1) + sizeof(CoverRec) * (size_t)n_rec + 8 * (scan_blocks(n_rec) + 2) + 4 * (size_t)n_rec;
 }
 
 static inline CoverRecScratch cv_rec_scratch(gci_ctx* ctx, uint32_t n_rec)
@@ -47,14 +46,14 @@ static inline CoverRecScratch cv_rec_scratch(gci_ctx* ctx, uint32_t n_rec)
     s.status = (unsigned long long*)p; p += 16;
     s.chunk0 = (unsigned long long*)p; p += 8 * ((size_t)n_rec + 1);
     s.recs = (CoverRec*)p; p += sizeof(CoverRec) * (size_t)n_rec;
-    s.blk = (unsigned long long*)p; p += 8 * (cv_blocks(n_rec) + 2);
+    s.blk = (unsigned long long*)p; p += 8 * (scan_blocks(n_rec) + 2);
     s.nch = (uint32_t*)p;
     return s;
 }
 
 static inline size_t cv_chunk_bytes(uint64_t n)
 {
-    return 8 * (size_t)n + 2 * 8 * ((size_t)n + 1) + 8 * (cv_blocks(n) + 2) + 4 * (size_t)n;
+    return 8 * (size_t)n + 2 * 8 * ((size_t)n + 1) + 8 * (scan_blocks(n) + 2) + 4 * (size_t)n;
 }
 
 static inline CoverChunkScratch cv_chunk_scratch(gci_ctx* ctx, uint64_t n)
@@ -64,7 +63,7 @@ static inline CoverChunkScratch cv_chunk_scratch(gci_ctx* ctx, uint64_t n)
     s.ref = (unsigned long long*)p; p += 8 * (size_t)n;
     s.ref0 = (unsigned long long*)p; p += 8 * ((size_t)n + 1);
     s.ivl0 = (unsigned long long*)p; p += 8 * ((size_t)n + 1);
-    s.blk = (unsigned long long*)p; p += 8 * (cv_blocks(n) + 2);
+    s.blk = (unsigned long long*)p; p += 8 * (scan_blocks(n) + 2);
     s.cnt = (uint32_t*)p;
     return s;
 }
@@ -78,52 +77,14 @@ __global__ __launch_bounds__(BLOCK) void k_cover_parse(const uint8_t* __restrict
 {
     const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n_rec) return;
-    CoverRec r;
-    r.ops_off = 0; r.n_ops = 0; r.contig = -1; r.pos = 0; r.pad = 0;
-    uint32_t chunks = 0;
-    const uint64_t off = rec_off[i];
-    if (off > n_bytes || n_bytes - off < 36) {
-        cv_report(status, i, GCI_E_MALFORMED);
-    } else {
-        const uint8_t* p = bam + off;
-        const int32_t block_size = (int32_t)cv_rd32(p), ref_id = (int32_t)cv_rd32(p + 4), pos = (int32_t)cv_rd32(p + 8);
-        const uint32_t l_read_name = p[12];
-        const int mapq = p[13];
-        const uint32_t n_cigar = cv_rd16(p + 16), flag = cv_rd16(p + 18);
-        const int32_t l_seq = (int32_t)cv_rd32(p + 20);
-        const uint64_t rec_end = off + 4 + (uint64_t)(uint32_t)block_size;
-        const uint64_t cig_off = off + 36 + l_read_name;
-        const uint64_t aux_off = cig_off + 4ull * n_cigar + (has_seq ? (((uint64_t)(uint32_t)l_seq + 1) >> 1) + (uint64_t)(uint32_t)l_seq : 0ull);
-        if (block_size < 32 || rec_end > n_bytes || l_seq < 0 || aux_off > rec_end) {
-            cv_report(status, i, GCI_E_MALFORMED);
-        } else if (!(flag & excl_flags) && mapq >= min_mapq && ref_id >= 0 && ref_id < n_ref && pos >= 0 && ref_sel[ref_id] >= 0 &&
-                   (!cls || (cls[i] < 32u && ((class_mask >> cls[i]) & 1u)))) {       // (gci_bam_cover_size_sel: only the classes of the mask)
-            r.contig = ref_sel[ref_id];
-            r.pos = pos;
-            r.ops_off = cig_off;
-            r.n_ops = n_cigar;
-            // a CIGAR of more than 65535 operations lies in CG:B,I (or B,i) behind the placeholder <l_seq>S<n>N: the rule of
-            // formats/bam.py::decode_record and the record filter (the FIRST CG tag counts, bam_aux_get)
-            if (n_cigar > 0) {
-                const uint32_t op0 = cv_rd32(bam + cig_off);
-                if ((op0 & 0xFu) == 4u && (op0 >> 4) == (uint32_t)l_seq) {
-                    const uint8_t* end = bam + rec_end;
-                    for (const uint8_t* q = bam + aux_off; q + 3 <= end;) {
-                        const int64_t sz = cv_aux_size(q + 3, end, q[2]);
-                        if (sz < 0 || q + 3 + sz > end) break;
-                        if (q[0] == 'C' && q[1] == 'G') {
-                            if (q[2] == 'B' && (q[3] == 'I' || q[3] == 'i')) {
-                                const uint32_t cg_len = cv_rd32(q + 4);
-                                if (cg_len >= n_cigar && cg_len < (1u << 29)) { r.ops_off = (uint64_t)(q + 8 - bam); r.n_ops = cg_len; }
-                            }
-                            break;
-                        }
-                        q += 3 + sz;
-                    }
-                }
-            }
-            chunks = (r.n_ops + CV_OPS - 1) / CV_OPS;
-        }
+    CvSeq q;
+    uint32_t chunks;
+    CoverRec r = cv_parse_counted(bam, n_bytes, rec_off[i], i, has_seq, ref_sel, n_ref, excl_flags, min_mapq, status, chunks, q);
+    // gci_bam_cover_size_sel: only the classes of the mask -- a record of another class is a skipped one (what it has to report as
+    // malformed it has reported)
+    if (r.contig >= 0 && cls && !(cls[i] < 32u && ((class_mask >> cls[i]) & 1u))) {
+        r.ops_off = 0; r.n_ops = 0; r.contig = -1; r.pos = 0;
+        chunks = 0;
     }
     recs[i] = r;
     nch[i] = chunks;
@@ -146,7 +107,6 @@ __device__ __forceinline__ CvClass cv_classify(uint32_t v, bool valid, int count
     return x;
 }
 
-__device__ __forceinline__ unsigned long long cv_below(int lane) { return (1ull << lane) - 1ull; }
 __device__ __forceinline__ int cv_top(unsigned long long m) { return 63 - __builtin_clzll(m); }     // m != 0
 // the lanes above lane t (t = 63: none)
 __device__ __forceinline__ unsigned long long cv_above(int t) { return t >= 63 ? 0ull : ~((2ull << t) - 1ull); }
@@ -172,7 +132,7 @@ __global__ __launch_bounds__(BLOCK) void k_cover_count(const uint8_t* __restrict
         bad |= x.bad;
         ref += x.ref_len;
         const unsigned long long covm = __ballot(x.cov), brkm = __ballot(x.brk), all = covm | brkm;
-        const unsigned long long below = all & cv_below(lane);
+        const unsigned long long below = all & lanes_below(lane);
         const bool prev_cov = below ? ((covm >> cv_top(below)) & 1ull) != 0 : open;
         cnt += (uint32_t)__builtin_popcountll(__ballot(x.brk && prev_cov));       // a run ends where D / N follows a covering operation
         if (all) open = ((covm >> cv_top(all)) & 1ull) != 0;
@@ -224,7 +184,7 @@ __global__ __launch_bounds__(BLOCK) void k_cover_write(const uint8_t* __restrict
         const unsigned long long inc = wave_inclusive<unsigned long long>((unsigned long long)x.ref_len, lane);
         const unsigned long long mine = at + inc - x.ref_len;                    // where this lane's operation begins on the reference
         const unsigned long long covm = __ballot(x.cov), brkm = __ballot(x.brk), all = covm | brkm;
-        const unsigned long long lowm = cv_below(lane), below = all & lowm;
+        const unsigned long long lowm = lanes_below(lane), below = all & lowm;
         const bool prev_cov = below ? ((covm >> cv_top(below)) & 1ull) != 0 : open;
         const bool close = x.brk && prev_cov;
         const unsigned long long closem = __ballot(close);
@@ -277,7 +237,7 @@ extern "C" int gci_bam_cover_size_sel(gci_ctx* ctx, const uint8_t* d_stream, uin
     if (n_chunks) {
         GCI_TRY(gci_ensure(ctx, ctx->cover_chunk, cv_chunk_bytes(n_chunks)));
         const CoverChunkScratch C = cv_chunk_scratch(ctx, n_chunks);
-        hipLaunchKernelGGL(k_cover_count, dim3((uint32_t)((n_chunks + BLOCK / 64 - 1) / (BLOCK / 64))), dim3(BLOCK), 0, ctx->stream, d_stream, n_bytes,
+        hipLaunchKernelGGL(k_cover_count, wave_grid(n_chunks), dim3(BLOCK), 0, ctx->stream, d_stream, n_bytes,
                            R.recs, R.chunk0, n_rec, n_chunks, count_del, C.ref, C.cnt, R.status);
         LAUNCHCHK("k_cover_count");
         GCI_TRY((device_exclusive_scan<unsigned long long, unsigned long long>(ctx, C.ref, C.ref0, C.blk, (int64_t)n_chunks, true)));
@@ -315,7 +275,7 @@ extern "C" int gci_bam_cover_write(gci_ctx* ctx, const uint8_t* d_stream, uint64
     const unsigned long long n_chunks = ctx->cover_n_chunks;
     if (n_chunks && ctx->cover_n_ivl) {
         const CoverChunkScratch C = cv_chunk_scratch(ctx, n_chunks);
-        hipLaunchKernelGGL(k_cover_write, dim3((uint32_t)((n_chunks + BLOCK / 64 - 1) / (BLOCK / 64))), dim3(BLOCK), 0, ctx->stream, d_stream, n_bytes,
+        hipLaunchKernelGGL(k_cover_write, wave_grid(n_chunks), dim3(BLOCK), 0, ctx->stream, d_stream, n_bytes,
                            R.recs, R.chunk0, n_rec, n_chunks, ctx->cover_count_del, C.ref0, C.ivl0, (const int64_t*)ctx->d_len.p, ctx->n_contigs, d_out,
                            (unsigned long long)ctx->cover_n_ivl);
         LAUNCHCHK("k_cover_write");

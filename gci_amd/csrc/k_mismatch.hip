@@ -13,19 +13,20 @@
 // The record side.  Input and chunks as k_indels.hip (gci_cover_chunks.hpp, gci_cigar_sums.hpp).
 //   k_mm_parse    one lane per record: cv_parse_counted, and where SEQ lies and how long it is
 //   k_cigar_sums  one wave per chunk
-//   k_mm_lens     one lane per chunk: its reference length M + D + N and its query length S + M + I -- scanned, the two carries
+//   k_chunk_lens  one lane per chunk: its reference length M + D + N and its query length S + M + I -- scanned, the two carries
 //   k_mm_count    one wave per chunk, 64 operations a round: wave scans of the reference, query and match lengths place every
 //                 operation on both axes; the round's MATCH BASES are then dealt to the lanes by base, MM_BASES consecutive ones a
 //                 lane, 64 * MM_BASES a step, and a lane finds the operation of its first base by a search over the 64 scanned match
 //                 lengths in LDS -- a record of 15-base operations fills the wave as one of 15,000-base operations does
-//   k_mm_finish   one lane per record: codes 9 - 15 and S + M + I != l_seq into the status word, whether the record is counted
+//   k_rec_finish  one lane per record: codes 9 - 15 and S + M + I != l_seq into the status word, whether the record is counted
 //   k_mm_write    the same walk; a lane's slot is its chunk's offset + the mismatches of earlier steps + those of the lanes below it
 //                 (ballots and popcounts), so events come in (record, reference position) order
 // A record whose S + M + I is not l_seq is never walked: no SEQ byte beyond (l_seq + 1) / 2 is ever read.  The only global atomic
 // is the status word's atomicMin.
 //
-// The track side.  Windows and tiles as k_indels.hip (gci_site_tiles.hpp); hot = mismatch >= min_reads and
-// mismatch * 1000000 >= frac_ppm * depth in 64 bits; the depth track is read in every pass.
+// The track side.  gci_site_tiles.hpp's lister, as k_indels.hip: the RUNS of hot elements, hot = mismatch >= min_reads and
+// mismatch * 1000000 >= frac_ppm * depth in 64 bits (HotMismatch); the depth track is read in every pass.  A site keeps the largest
+// mismatch count of its run and the depth at the FIRST base that reaches it (MmBest).
 #include "gci_cigar_sums.hpp"
 #include "gci_site_tiles.hpp"
 #include "gci_text_tiles.hpp"
@@ -132,16 +133,17 @@ extern "C" int gci_fasta_codes(gci_ctx* ctx, const uint8_t* d_text, uint64_t n_b
 }
 
 // ---- the record side ----------------------------------------------------------------------------------------------------------------
-struct MmRecScratch {                    // carved out of ctx->mm_rec
-    unsigned long long* status;
-    unsigned long long* chunk0;          // n_rec + 1: exclusive scan of the chunk counts
-    unsigned long long* cnt0;            // n_rec + 1: exclusive scan of `counted`
-    CoverRec* recs;
+struct MmRecScratch : RecFrame {         // carved out of ctx->mm_rec: the frame, and behind it
     CvSeq* seqs;
-    unsigned long long* blk;
-    uint32_t* nch;
-    uint32_t* counted;
 };
+
+static inline MmRecScratch mm_rec_scratch(const RecFrame& F)
+{
+    MmRecScratch s;
+    static_cast<RecFrame&>(s) = F;
+    s.seqs = (CvSeq*)F.tail;
+    return s;
+}
 
 struct MmChunkScratch {                  // carved out of ctx->mm_chunk
     CigarSums* sums;
@@ -156,34 +158,10 @@ struct MmChunkScratch {                  // carved out of ctx->mm_chunk
     uint32_t* n_mm;                      // mismatches of a chunk
 };
 
-static inline size_t mm_blocks(uint64_t n) { return (size_t)((n + TILE - 1) / TILE); }
-
-static inline size_t mm_rec_bytes(uint32_t n_rec)
-{
-    const size_t n = n_rec;
-    return 16 + 2 * 8 * (n + 1) + (sizeof(CoverRec) + sizeof(CvSeq)) * n + 8 * (mm_blocks(n) + 2) + 2 * 4 * n;
-}
-
-static inline MmRecScratch mm_rec_scratch(gci_ctx* ctx, uint32_t n_rec)
-{
-    const size_t n = n_rec;
-    MmRecScratch s;
-    uint8_t* p = (uint8_t*)ctx->mm_rec.p;
-    s.status = (unsigned long long*)p; p += 16;
-    s.chunk0 = (unsigned long long*)p; p += 8 * (n + 1);
-    s.cnt0 = (unsigned long long*)p; p += 8 * (n + 1);
-    s.recs = (CoverRec*)p; p += sizeof(CoverRec) * n;
-    s.seqs = (CvSeq*)p; p += sizeof(CvSeq) * n;
-    s.blk = (unsigned long long*)p; p += 8 * (mm_blocks(n) + 2);
-    s.nch = (uint32_t*)p; p += 4 * n;
-    s.counted = (uint32_t*)p;
-    return s;
-}
-
 static inline size_t mm_chunk_bytes(uint64_t n_chunks)
 {
     const size_t n = (size_t)n_chunks;
-    return sizeof(CigarSums) * n + 3 * 8 * n + 4 * 8 * (n + 1) + 8 * (mm_blocks(n) + 2) + 4 * n;
+    return sizeof(CigarSums) * n + 3 * 8 * n + 4 * 8 * (n + 1) + 8 * (scan_blocks(n) + 2) + 4 * n;
 }
 
 static inline MmChunkScratch mm_chunk_scratch(gci_ctx* ctx, uint64_t n_chunks)
@@ -199,7 +177,7 @@ static inline MmChunkScratch mm_chunk_scratch(gci_ctx* ctx, uint64_t n_chunks)
     s.qry0 = (unsigned long long*)p; p += 8 * (n + 1);
     s.cmp0 = (unsigned long long*)p; p += 8 * (n + 1);
     s.mm0 = (unsigned long long*)p; p += 8 * (n + 1);
-    s.blk = (unsigned long long*)p; p += 8 * (mm_blocks(n) + 2);
+    s.blk = (unsigned long long*)p; p += 8 * (scan_blocks(n) + 2);
     s.n_mm = (uint32_t*)p;
     return s;
 }
@@ -218,18 +196,6 @@ __global__ __launch_bounds__(BLOCK) void k_mm_parse(const uint8_t* __restrict__ 
     seqs[i] = q;
     nch[i] = chunks;
 }
-
-__global__ __launch_bounds__(BLOCK) void k_mm_lens(const CigarSums* __restrict__ sums, unsigned long long n_chunks,
-                                                   unsigned long long* __restrict__ chunk_ref, unsigned long long* __restrict__ chunk_qry)
-{
-    const unsigned long long ch = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x;
-    if (ch >= n_chunks) return;
-    const CigarSums s = sums[ch];
-    chunk_ref[ch] = s.M + s.D + s.N;                   // (every total is below 2^57)
-    chunk_qry[ch] = s.S + s.M + s.I;
-}
-
-__device__ __forceinline__ unsigned long long mm_below(int lane) { return (1ull << lane) - 1ull; }
 
 // LDS written by the lanes of ONE wave is read by its other lanes: no workgroup barrier (the waves of a workgroup walk chunks of
 // different lengths), the wave's own LDS operations complete in order
@@ -271,7 +237,7 @@ __device__ __forceinline__ void mm_walk(const MmWalkArgs& A, uint32_t* __restric
     const unsigned long long ch_first = A.chunk0[rec], ch_last = A.chunk0[rec + 1];
     uint32_t mms = 0;
     unsigned long long cmps = 0;
-    // SEQ `*`, or a record whose operations do not add up to l_seq (k_mm_finish reports it): nothing is compared, no SEQ byte is read
+    // SEQ `*`, or a record whose operations do not add up to l_seq (k_rec_finish reports it): nothing is compared, no SEQ byte is read
     const bool walk = sq.l_seq != 0 && A.qry0[ch_last] - A.qry0[ch_first] == (unsigned long long)sq.l_seq;
     if (walk) {
         const CvChunk c = cv_chunk_of(A.bam, r, (uint32_t)(ch - ch_first));
@@ -332,7 +298,7 @@ __device__ __forceinline__ void mm_walk(const MmWalkArgs& A, uint32_t* __restric
 #pragma unroll
                     for (int b = 0; b < MM_BASES; b++) {
                         const unsigned long long m = __ballot((mis >> b) & 1u);
-                        slot += (unsigned long long)__builtin_popcountll(m & mm_below(lane));
+                        slot += (unsigned long long)__builtin_popcountll(m & lanes_below(lane));
                         step_total += (uint32_t)__builtin_popcountll(m);
                     }
                     uint32_t bits = mis;
@@ -378,28 +344,6 @@ __global__ __launch_bounds__(BLOCK) void k_mm_write(MmWalkArgs A, const unsigned
     mm_walk<true>(A, nullptr, nullptr, chunk_mm0, total, out);
 }
 
-__global__ __launch_bounds__(BLOCK) void k_mm_finish(uint32_t n_rec, const CoverRec* __restrict__ recs, const CvSeq* __restrict__ seqs,
-                                                     const unsigned long long* __restrict__ chunk0, const CigarSums* __restrict__ sums,
-                                                     const unsigned long long* __restrict__ qry0, uint32_t* __restrict__ counted,
-                                                     unsigned long long* __restrict__ status)
-{
-    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= n_rec) return;
-    uint32_t c = 0;
-    if (recs[i].contig >= 0) {
-        c = 1;
-        unsigned long long bad = 0;
-        const unsigned long long first = chunk0[i], last = chunk0[i + 1];
-        for (unsigned long long ch = first; ch < last; ch++) bad |= sums[ch].bad;
-        const unsigned long long q = last > first ? qry0[last] - qry0[first] : 0ull;
-        if (seqs[i].l_seq != 0 && q != (unsigned long long)seqs[i].l_seq) bad = 1;
-        if (bad) cv_report(status, i, GCI_E_MALFORMED);
-    }
-    counted[i] = c;
-}
-
-static inline dim3 mm_wave_grid(unsigned long long n) { return dim3((uint32_t)((n + BLOCK / 64 - 1) / (BLOCK / 64))); }
-
 static inline MmWalkArgs mm_walk_args(gci_ctx* ctx, const uint8_t* d_stream, uint64_t n_bytes, uint32_t n_rec, unsigned long long n_chunks,
                                       const MmRecScratch& R, const MmChunkScratch& C, const uint8_t* d_codes)
 {
@@ -419,19 +363,16 @@ extern "C" int gci_bam_mismatch_size(gci_ctx* ctx, const uint8_t* d_stream, uint
     if (!ctx->n_contigs) return GCI_E_NO_LAYOUT;
     ctx->mm_valid = false;
     h_counts[0] = h_counts[1] = h_counts[2] = 0;
-    GCI_TRY(gci_ensure(ctx, ctx->mm_rec, mm_rec_bytes(n_rec)));
-    const MmRecScratch R = mm_rec_scratch(ctx, n_rec);
-    HIPCHK(hipMemsetAsync(R.status, 0xFF, 8, ctx->stream));
+    RecFrame F;
+    GCI_TRY(rec_frame_open(ctx, ctx->mm_rec, sizeof(CvSeq) * (size_t)n_rec, n_rec, F));
+    const MmRecScratch R = mm_rec_scratch(F);
     unsigned long long n_chunks = 0, n_mm = 0, n_cmp = 0, n_counted = 0;
     if (n_rec) {
         const uint32_t groups = (n_rec + BLOCK - 1) / BLOCK;
         hipLaunchKernelGGL(k_mm_parse, dim3(groups), dim3(BLOCK), 0, ctx->stream, d_stream, n_bytes, d_rec_off, n_rec, d_ref_sel, n_ref, excl_flags,
                            min_mapq, R.recs, R.seqs, R.nch, R.status);
         LAUNCHCHK("k_mm_parse");
-        GCI_TRY((device_exclusive_scan<uint32_t, unsigned long long>(ctx, R.nch, R.chunk0, R.blk, (int64_t)n_rec, true)));
-        HIPCHK(hipMemcpyAsync(&n_chunks, R.chunk0 + n_rec, 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        if (n_chunks > 0x7FFFFFFFull) return GCI_E_INVALID;                  // (2^42 operations in one call)
+        GCI_TRY(rec_frame_chunks(ctx, R, n_rec, n_chunks));
         const CigarSums* sums = nullptr;
         const unsigned long long* qry0 = nullptr;
         if (n_chunks) {
@@ -441,11 +382,11 @@ extern "C" int gci_bam_mismatch_size(gci_ctx* ctx, const uint8_t* d_stream, uint
             hipLaunchKernelGGL(k_cigar_sums, cigar_sums_grid(n_chunks), dim3(BLOCK), 0, ctx->stream, d_stream, n_bytes, R.recs, R.chunk0, n_rec, n_chunks,
                                C.sums);
             LAUNCHCHK("k_cigar_sums");
-            hipLaunchKernelGGL(k_mm_lens, dim3((uint32_t)((n_chunks + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, ctx->stream, C.sums, n_chunks, C.ref, C.qry);
-            LAUNCHCHK("k_mm_lens");
+            launch_chunk_lens(ctx, C.sums, n_chunks, C.ref, C.qry);
+            LAUNCHCHK("k_chunk_lens");
             GCI_TRY((device_exclusive_scan<unsigned long long, unsigned long long>(ctx, C.ref, C.ref0, C.blk, (int64_t)n_chunks, true)));
             GCI_TRY((device_exclusive_scan<unsigned long long, unsigned long long>(ctx, C.qry, C.qry0, C.blk, (int64_t)n_chunks, true)));
-            hipLaunchKernelGGL(k_mm_count, mm_wave_grid(n_chunks), dim3(BLOCK), 0, ctx->stream,
+            hipLaunchKernelGGL(k_mm_count, wave_grid(n_chunks), dim3(BLOCK), 0, ctx->stream,
                                mm_walk_args(ctx, d_stream, n_bytes, n_rec, n_chunks, R, C, d_codes), C.n_mm, C.cmp);
             LAUNCHCHK("k_mm_count");
             GCI_TRY((device_exclusive_scan<uint32_t, unsigned long long>(ctx, C.n_mm, C.mm0, C.blk, (int64_t)n_chunks, true)));
@@ -453,8 +394,8 @@ extern "C" int gci_bam_mismatch_size(gci_ctx* ctx, const uint8_t* d_stream, uint
             HIPCHK(hipMemcpyAsync(&n_mm, C.mm0 + n_chunks, 8, hipMemcpyDeviceToHost, ctx->stream));
             HIPCHK(hipMemcpyAsync(&n_cmp, C.cmp0 + n_chunks, 8, hipMemcpyDeviceToHost, ctx->stream));
         }
-        hipLaunchKernelGGL(k_mm_finish, dim3(groups), dim3(BLOCK), 0, ctx->stream, n_rec, R.recs, R.seqs, R.chunk0, sums, qry0, R.counted, R.status);
-        LAUNCHCHK("k_mm_finish");
+        launch_rec_finish(ctx, n_rec, R.recs, R.chunk0, sums, R.seqs, qry0, R.counted, R.status);
+        LAUNCHCHK("k_rec_finish");
         GCI_TRY((device_exclusive_scan<uint32_t, unsigned long long>(ctx, R.counted, R.cnt0, R.blk, (int64_t)n_rec, true)));
         HIPCHK(hipMemcpyAsync(&n_counted, R.cnt0 + n_rec, 8, hipMemcpyDeviceToHost, ctx->stream));
     }
@@ -479,11 +420,11 @@ extern "C" int gci_bam_mismatch_write(gci_ctx* ctx, const uint8_t* d_stream, uin
     const unsigned long long total = ctx->mm_n_mm;
     if (total && !d_out) return GCI_E_INVALID;
     if (cap < total) return GCI_E_CAPACITY;
-    const MmRecScratch R = mm_rec_scratch(ctx, n_rec);
+    const MmRecScratch R = mm_rec_scratch(rec_frame(ctx->mm_rec, n_rec));
     const unsigned long long n_chunks = ctx->mm_n_chunks;
     if (n_chunks && total) {
         const MmChunkScratch C = mm_chunk_scratch(ctx, n_chunks);
-        hipLaunchKernelGGL(k_mm_write, mm_wave_grid(n_chunks), dim3(BLOCK), 0, ctx->stream,
+        hipLaunchKernelGGL(k_mm_write, wave_grid(n_chunks), dim3(BLOCK), 0, ctx->stream,
                            mm_walk_args(ctx, d_stream, n_bytes, n_rec, n_chunks, R, C, d_codes), C.mm0, total, d_out);
         LAUNCHCHK("k_mm_write");
     }
@@ -492,142 +433,44 @@ extern "C" int gci_bam_mismatch_write(gci_ctx* ctx, const uint8_t* d_stream, uin
 }
 
 // ---- the track side -----------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool mm_hot(int32_t mm, int32_t depth, int32_t min_reads, int64_t frac_ppm)
-{
-    return mm >= min_reads && (int64_t)mm * 1000000ll >= frac_ppm * (int64_t)depth;
-}
-
-// whether the element in front of q is hot AND of the same window and contig (q - 1 may lie in the tile in front)
-__device__ __forceinline__ bool mm_prev_hot(const int32_t* __restrict__ mm, const int32_t* __restrict__ depth, const SiteTile& x, int64_t q,
-                                            int32_t min_reads, int64_t frac_ppm)
-{
-    if (q - 1 < x.run_lo || q - 1 >= x.run_hi) return false;
-    return mm_hot(mm[q - 1], depth[q - 1], min_reads, frac_ppm);
-}
-
-// the hot elements among a thread's 16 consecutive ones at p (bit k: element p + k)
-__device__ __forceinline__ uint32_t mm_hot16(const int32_t* __restrict__ mm, const int32_t* __restrict__ depth, const SiteTile& x, int64_t p,
-                                             int32_t min_reads, int64_t frac_ppm)
-{
-    uint32_t hot = 0;
-#pragma unroll
-    for (int j = 0; j < 4; j++) {
-        const int4 a = *reinterpret_cast<const int4*>(mm + p + 4 * j), b = *reinterpret_cast<const int4*>(depth + p + 4 * j);
-        const int32_t m[4] = {a.x, a.y, a.z, a.w}, d[4] = {b.x, b.y, b.z, b.w};
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const int64_t q = p + 4 * j + k;
-            hot |= (q >= x.lo && q < x.hi && mm_hot(m[k], d[k], min_reads, frac_ppm)) ? (1u << (4 * j + k)) : 0u;
-        }
-    }
-    return hot;
-}
-
-// one workgroup per window tile, a thread 16 consecutive elements: the run starts of the tile, counted (WRITE = false) or stored by rank
-template <bool WRITE>
-__device__ __forceinline__ void mm_sites_tile(const int32_t* __restrict__ mm, const int32_t* __restrict__ depth, const gci_window* __restrict__ win,
-                                              const int64_t* __restrict__ win_tile_first, int32_t n_win, const int64_t* __restrict__ off,
-                                              const int64_t* __restrict__ len, const int64_t* __restrict__ tile_first, int32_t n_contigs,
-                                              int32_t min_reads, int64_t frac_ppm, uint32_t* __restrict__ tile_cnt,
-                                              const unsigned long long* __restrict__ tile_off, gci_mismatch_site* __restrict__ out,
-                                              unsigned long long total)
-{
-    __shared__ uint32_t wtot[BLOCK / 64];
-    if (WRITE && tile_cnt[blockIdx.x] == 0) return;    // (the whole workgroup)
-    const int t = threadIdx.x, lane = t & 63;
-    const SiteTile x = site_tile_of(win, win_tile_first, n_win, blockIdx.x, off, len, tile_first, n_contigs);
-    const int64_t p = x.p0 + (int64_t)t * 16;          // ascending order is thread order
-    const uint32_t hot = mm_hot16(mm, depth, x, p, min_reads, frac_ppm);
-    uint32_t prev = (uint32_t)__shfl_up((int)(hot >> 15), 1, 64);
-    if (lane == 0) prev = mm_prev_hot(mm, depth, x, p, min_reads, frac_ppm) ? 1u : 0u;
-    uint32_t starts = hot & ~((hot << 1) | prev) & 0xFFFFu;
-    uint32_t all;
-    const uint32_t pre = block_exclusive<uint32_t, BLOCK / 64>((uint32_t)__builtin_popcount(starts), wtot, all);
-    if (!WRITE) {
-        if (t == 0) tile_cnt[blockIdx.x] = all;
-        return;
-    }
-    unsigned long long slot = tile_off[blockIdx.x] + pre;
-    while (starts) {                                   // (few: a genome has thousands of sites)
-        const int k = __builtin_ctz(starts);
-        starts &= starts - 1u;
+struct MmEmit {
+    static constexpr int LISTER = 3;
+    static constexpr bool RUNS = true;
+    gci_mismatch_site* out;
+    __device__ __forceinline__ void operator()(unsigned long long slot, const SiteTile& x, int64_t q) const
+    {
         gci_mismatch_site s;
-        s.contig = x.contig; s.start = (int32_t)(p + k - x.contig_off);
-        s.end = (int32_t)(x.run_hi - x.contig_off);    // where the run ends at the latest: k_mm_site_finish walks up to it
+        s.contig = x.contig; s.start = (int32_t)(q - x.contig_off);
+        s.end = (int32_t)(x.run_hi - x.contig_off);    // where the run ends at the latest: k_site_runs_finish walks up to it
         s.mismatch = 0; s.depth = 0;
-        if (slot < total) out[slot] = s;
-        slot++;
+        out[slot] = s;
     }
-}
+};
 
-__global__ __launch_bounds__(BLOCK) void k_mm_sites_count(const int32_t* __restrict__ mm, const int32_t* __restrict__ depth,
-                                                          const gci_window* __restrict__ win, const int64_t* __restrict__ win_tile_first, int32_t n_win,
-                                                          const int64_t* __restrict__ off, const int64_t* __restrict__ len,
-                                                          const int64_t* __restrict__ tile_first, int32_t n_contigs, int32_t min_reads,
-                                                          int64_t frac_ppm, uint32_t* __restrict__ tile_cnt)
-{
-    mm_sites_tile<false>(mm, depth, win, win_tile_first, n_win, off, len, tile_first, n_contigs, min_reads, frac_ppm, tile_cnt, nullptr, nullptr, 0);
-}
-
-__global__ __launch_bounds__(BLOCK) void k_mm_sites_write(const int32_t* __restrict__ mm, const int32_t* __restrict__ depth,
-                                                          const gci_window* __restrict__ win, const int64_t* __restrict__ win_tile_first, int32_t n_win,
-                                                          const int64_t* __restrict__ off, const int64_t* __restrict__ len,
-                                                          const int64_t* __restrict__ tile_first, int32_t n_contigs, int32_t min_reads,
-                                                          int64_t frac_ppm, uint32_t* __restrict__ tile_cnt,
-                                                          const unsigned long long* __restrict__ tile_off, gci_mismatch_site* __restrict__ out,
-                                                          unsigned long long total)
-{
-    mm_sites_tile<true>(mm, depth, win, win_tile_first, n_win, off, len, tile_first, n_contigs, min_reads, frac_ppm, tile_cnt, tile_off, out, total);
-}
-
-// one wave per site: forward from the start, 64 elements a round, to the first element that is not hot or the end of the window or
-// contig; the largest mismatch count and the depth at the FIRST base that reaches it
-__global__ __launch_bounds__(BLOCK) void k_mm_site_finish(const int32_t* __restrict__ mm, const int32_t* __restrict__ depth,
-                                                          const int64_t* __restrict__ off, int32_t min_reads, int64_t frac_ppm,
-                                                          gci_mismatch_site* __restrict__ out, unsigned long long total)
-{
-    const int lane = threadIdx.x & 63;
-    const unsigned long long i = (unsigned long long)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6);
-    if (i >= total) return;                            // (the whole wave)
-    const gci_mismatch_site s = out[i];
-    const int64_t base = off[s.contig], lim = base + s.end, q0 = base + s.start;
-    int64_t q = q0;                                    // (hot, and below lim)
-    // (count << 32) | (0xFFFFFFFF - distance from the start): the largest key is the largest count at the smallest distance
-    unsigned long long best = 0;
-    for (;;) {
-        const int64_t e = q + lane;
-        const bool in = e < lim;
-        const int32_t m = in ? mm[e] : 0, d = in ? depth[e] : 0;
-        const unsigned long long cold = ~__ballot(in && mm_hot(m, d, min_reads, frac_ppm));
-        const int first = cold ? __builtin_ctzll(cold) : 64;                    // the run's elements of this round: the lanes below `first`
-        if (lane < first) {
-            const unsigned long long key = ((unsigned long long)(uint32_t)m << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)(e - q0));
-            best = key > best ? key : best;
-        }
-        q += first;
-        if (first < 64) break;
+// of a run: the largest mismatch count and the depth at the FIRST base that reaches it -- the largest key
+// (count << 32) | (0xFFFFFFFF - distance from the start) is the largest count at the smallest distance
+struct MmBest {
+    const int32_t* depth;
+    typedef unsigned long long Acc;
+    __device__ __forceinline__ Acc init() const { return 0ull; }
+    __device__ __forceinline__ void take(Acc& best, int2 v, int64_t e, int64_t q0) const
+    {
+        const unsigned long long key = ((unsigned long long)(uint32_t)v.x << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)(e - q0));
+        best = key > best ? key : best;
     }
-#pragma unroll
-    for (int x = 32; x >= 1; x >>= 1) { const unsigned long long o = __shfl_xor(best, x, 64); best = o > best ? o : best; }
-    if (lane == 0) {
-        gci_mismatch_site r = s;
-        r.end = (int32_t)(q - base);
-        r.mismatch = (int32_t)(best >> 32);
-        r.depth = depth[q0 + (best ? (int64_t)(0xFFFFFFFFu - (uint32_t)best) : 0)];      // (best != 0: the start is hot)
-        out[i] = r;
+    __device__ __forceinline__ void wave(Acc& best) const { best = wave_max(best); }
+    __device__ __forceinline__ void store(gci_mismatch_site& s, const Acc& best, int64_t q0) const
+    {
+        s.mismatch = (int32_t)(best >> 32);
+        s.depth = depth[q0 + (best ? (int64_t)(0xFFFFFFFFu - (uint32_t)best) : 0)];      // (best != 0: the start is hot)
     }
-}
+};
 
-struct MmTileScratch { uint32_t* cnt; unsigned long long* off; unsigned long long* blk; };
-
-static inline MmTileScratch mm_tile_scratch(gci_ctx* ctx, int64_t tiles)
+static inline SiteMemo mm_site_ask(const int32_t* d_mismatch, const int32_t* d_depth, int32_t min_reads, int32_t frac_ppm, uint32_t n_windows)
 {
-    MmTileScratch s;
-    uint8_t* p = (uint8_t*)ctx->mm_tiles.p;
-    s.off = (unsigned long long*)p; p += 8 * ((size_t)tiles + 1);
-    s.blk = (unsigned long long*)p; p += 8 * (mm_blocks((uint64_t)tiles) + 2);
-    s.cnt = (uint32_t*)p;
-    return s;
+    SiteMemo m;
+    m.track[0] = d_mismatch; m.track[1] = d_depth; m.min_reads = min_reads; m.frac = frac_ppm; m.n_windows = n_windows;
+    return m;
 }
 
 extern "C" int gci_mismatch_sites_size(gci_ctx* ctx, const int32_t* d_mismatch, const int32_t* d_depth, int32_t min_reads, int32_t frac_ppm,
@@ -637,32 +480,9 @@ extern "C" int gci_mismatch_sites_size(gci_ctx* ctx, const int32_t* d_mismatch, 
         return GCI_E_INVALID;
     if (!ctx->n_contigs) return GCI_E_NO_LAYOUT;
     if ((((uintptr_t)d_mismatch) | ((uintptr_t)d_depth)) & 15u) return GCI_E_INVALID;                        // whole tracks, as allocated
-    if (n_windows >= (1u << 31)) return GCI_E_INVALID;
-    std::vector<gci_window> ws;
-    if (!gci_site_windows(ctx, h_windows, n_windows, ws)) return GCI_E_INVALID;
-    ctx->mm_sites_epoch = 0;
-    *h_n_sites = 0;
-    GCI_TRY(gci_set_windows(ctx, ws.data(), (uint32_t)ws.size()));
-    ctx->win_flank = INT32_MIN;
-    const int64_t tiles = ctx->win_tiles;
-    if (tiles > 0x7FFFFFFFll) return GCI_E_INVALID;
-    unsigned long long total = 0;
-    if (tiles) {
-        GCI_TRY(gci_ensure(ctx, ctx->mm_tiles, 8 * ((size_t)tiles + 1) + 8 * (mm_blocks((uint64_t)tiles) + 2) + 4 * (size_t)tiles));
-        const MmTileScratch T = mm_tile_scratch(ctx, tiles);
-        hipLaunchKernelGGL(k_mm_sites_count, dim3((uint32_t)tiles), dim3(BLOCK), 0, ctx->stream, d_mismatch, d_depth, (const gci_window*)ctx->win.p,
-                           (const int64_t*)ctx->win_tile_first.p, (int32_t)ctx->win_n, (const int64_t*)ctx->d_off.p, (const int64_t*)ctx->d_len.p,
-                           (const int64_t*)ctx->d_tile_first.p, ctx->n_contigs, min_reads, (int64_t)frac_ppm, T.cnt);
-        LAUNCHCHK("k_mm_sites_count");
-        GCI_TRY((device_exclusive_scan<uint32_t, unsigned long long>(ctx, T.cnt, T.off, T.blk, tiles, true)));
-        HIPCHK(hipMemcpyAsync(&total, T.off + tiles, 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-    }
-    ctx->mm_sites_epoch = ctx->win_epoch; ctx->mm_sites_total = total;
-    ctx->mm_sites_track = d_mismatch; ctx->mm_sites_depth = d_depth;
-    ctx->mm_sites_min_reads = min_reads; ctx->mm_sites_frac = frac_ppm; ctx->mm_sites_windows = n_windows;
-    *h_n_sites = total;
-    return GCI_OK;
+    return site_size<MmEmit>(ctx, HotMismatch{d_mismatch, d_depth, min_reads, (int64_t)frac_ppm},
+                                        mm_site_ask(d_mismatch, d_depth, min_reads, frac_ppm, n_windows), h_windows, h_n_sites,
+                                        "k_sites_count (mismatch)");
 }
 
 extern "C" int gci_mismatch_sites_write(gci_ctx* ctx, const int32_t* d_mismatch, const int32_t* d_depth, int32_t min_reads, int32_t frac_ppm,
@@ -670,22 +490,13 @@ extern "C" int gci_mismatch_sites_write(gci_ctx* ctx, const int32_t* d_mismatch,
 {
     if (!ctx || !d_mismatch || !d_depth || min_reads < 1 || (n_windows && !h_windows)) return GCI_E_INVALID;
     if (!ctx->n_contigs) return GCI_E_NO_LAYOUT;
-    // not what gci_mismatch_sites_size measured last on this context, or its windows are no longer the context's
-    if (!ctx->mm_sites_epoch || ctx->mm_sites_epoch != ctx->win_epoch || d_mismatch != ctx->mm_sites_track || d_depth != ctx->mm_sites_depth ||
-        min_reads != ctx->mm_sites_min_reads || frac_ppm != ctx->mm_sites_frac || n_windows != ctx->mm_sites_windows)
-        return GCI_E_INVALID;
-    const unsigned long long total = ctx->mm_sites_total;
-    if (total && !d_out) return GCI_E_INVALID;
-    if (cap < total) return GCI_E_CAPACITY;
-    const int64_t tiles = ctx->win_tiles;
-    if (!tiles || !total) return GCI_OK;
-    const MmTileScratch T = mm_tile_scratch(ctx, tiles);
-    hipLaunchKernelGGL(k_mm_sites_write, dim3((uint32_t)tiles), dim3(BLOCK), 0, ctx->stream, d_mismatch, d_depth, (const gci_window*)ctx->win.p,
-                       (const int64_t*)ctx->win_tile_first.p, (int32_t)ctx->win_n, (const int64_t*)ctx->d_off.p, (const int64_t*)ctx->d_len.p,
-                       (const int64_t*)ctx->d_tile_first.p, ctx->n_contigs, min_reads, (int64_t)frac_ppm, T.cnt, T.off, d_out, total);
-    LAUNCHCHK("k_mm_sites_write");
-    hipLaunchKernelGGL(k_mm_site_finish, mm_wave_grid(total), dim3(BLOCK), 0, ctx->stream, d_mismatch, d_depth, (const int64_t*)ctx->d_off.p, min_reads,
-                       (int64_t)frac_ppm, d_out, total);
-    LAUNCHCHK("k_mm_site_finish");
+    const HotMismatch hot{d_mismatch, d_depth, min_reads, (int64_t)frac_ppm};
+    GCI_TRY((site_write(ctx, hot, mm_site_ask(d_mismatch, d_depth, min_reads, frac_ppm, n_windows), MmEmit{d_out}, d_out, cap,
+                                           "k_sites_write (mismatch)")));
+    const unsigned long long total = ctx->site_memo.total;
+    if (!total) return GCI_OK;
+    hipLaunchKernelGGL((k_site_runs_finish<HotMismatch, MmBest, gci_mismatch_site>), wave_grid(total), dim3(BLOCK), 0, ctx->stream, hot,
+                       MmBest{d_depth}, (const int64_t*)ctx->d_off.p, d_out, total);
+    LAUNCHCHK("k_site_runs_finish (mismatch)");
     return GCI_OK;
 }

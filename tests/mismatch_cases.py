@@ -282,12 +282,13 @@ def want_codes(name):
 
 # ---- sites: tracks written by hand -----------------------------------------------------------------------------------------------------
 def _site_runs():
-    """Runs of 1, 64, 65 and 9000 elements, one across a tile edge; a run cut by a window edge and by two touching windows; a fraction
+    """Runs of 1, 64, 65 and 9000 elements, one across a tile edge, one from a wave's first lane (1024, in both thread mappings of the
+    lister) and one across that edge (2047 - 2048); a run cut by a window edge and by two touching windows; a fraction
     exactly at the threshold and one part per million beside it; the maximum reached twice: the depth of the first."""
     lengths = [20000]
     offs, total = R.layout(lengths)
     mism, depth = np.zeros(total, dtype=np.int32), np.full(total, 8, dtype=np.int32)
-    for a, n in ((100, 1), (300, 64), (500, 65), (4090, 10), (8192, 3)):
+    for a, n in ((100, 1), (300, 64), (500, 65), (1024, 64), (2047, 2), (4090, 10), (8192, 3)):
         mism[a:a + n] = 5
     mism[10000:19000] = 6
     mism[10500], depth[10500] = 9, 12
@@ -328,14 +329,14 @@ SITE_BUILDERS = {"runs": _site_runs, "contigs": _site_contigs, "random": _site_r
 SITE_NAMES = list(SITE_BUILDERS)
 SITES_EXPECTED = {
     # at 500000 ppm 3 / 6 and 500001 / 1000000 are hot, 499999 / 1000000 is not: the run is 1000 - 1002 (exclusive)
-    ("runs", 0): [(0, 100, 101, 5, 8), (0, 300, 364, 5, 8), (0, 500, 565, 5, 8), (0, 1000, 1002, 500001, 1000000), (0, 4090, 4100, 5, 8),
-                  (0, 8192, 8195, 5, 8), (0, 10000, 19000, 9, 12)],
+    ("runs", 0): [(0, 100, 101, 5, 8), (0, 300, 364, 5, 8), (0, 500, 565, 5, 8), (0, 1000, 1002, 500001, 1000000), (0, 1024, 1088, 5, 8),
+                  (0, 2047, 2049, 5, 8), (0, 4090, 4100, 5, 8), (0, 8192, 8195, 5, 8), (0, 10000, 19000, 9, 12)],
     # one part per million more: 3 / 6 is out, the run begins at 1001
-    ("runs", 1): [(0, 100, 101, 5, 8), (0, 300, 364, 5, 8), (0, 500, 565, 5, 8), (0, 1001, 1002, 500001, 1000000), (0, 4090, 4100, 5, 8),
-                  (0, 8192, 8195, 5, 8), (0, 10000, 19000, 9, 12)],
+    ("runs", 1): [(0, 100, 101, 5, 8), (0, 300, 364, 5, 8), (0, 500, 565, 5, 8), (0, 1001, 1002, 500001, 1000000), (0, 1024, 1088, 5, 8),
+                  (0, 2047, 2049, 5, 8), (0, 4090, 4100, 5, 8), (0, 8192, 8195, 5, 8), (0, 10000, 19000, 9, 12)],
     # one less: all three
-    ("runs", 2): [(0, 100, 101, 5, 8), (0, 300, 364, 5, 8), (0, 500, 565, 5, 8), (0, 1000, 1003, 500001, 1000000), (0, 4090, 4100, 5, 8),
-                  (0, 8192, 8195, 5, 8), (0, 10000, 19000, 9, 12)],
+    ("runs", 2): [(0, 100, 101, 5, 8), (0, 300, 364, 5, 8), (0, 500, 565, 5, 8), (0, 1000, 1003, 500001, 1000000), (0, 1024, 1088, 5, 8),
+                  (0, 2047, 2049, 5, 8), (0, 4090, 4100, 5, 8), (0, 8192, 8195, 5, 8), (0, 10000, 19000, 9, 12)],
     ("runs", 6): [(0, 4093, 4099, 5, 8)],
     ("runs", 7): [(0, 300, 330, 5, 8), (0, 330, 340, 5, 8), (0, 500, 565, 5, 8)],
     ("contigs", 0): [(0, 4090, 4096, 4, 8), (1, 0, 4, 4, 8), (1, 4990, 5000, 5, 8), (2, 95, 100, 4, 8), (3, 0, 1, 6, 8)],

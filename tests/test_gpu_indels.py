@@ -202,6 +202,26 @@ def test_argument_errors_of_the_site_calls(engine):
     assert lib.gci_indel_sites_write(engine.ctx, p(t["dele"]), p(t["ins"]), p(t["depth"]), 3, None, 0, p(out), 8192) == _lib.GCI_E_INVALID
 
 
+def test_a_size_call_of_another_lister_ends_what_the_clip_size_call_measured(engine):
+    """Every *_sites_size call sets the context's windows anew, so a write call that follows the size call of ANOTHER lister is refused
+    and the other lister's own write call gives its sites: what lets the three listers share one scratch and one memo."""
+    engine.set_layout([100])
+    a = np.zeros(int(engine.total), dtype=np.int32)
+    a[10:13], a[40] = [3, 4, 3], 5
+    t = engine.to_device(a)
+    p, lib = engine._p, engine.lib
+    n = ctypes.c_uint64(0)
+    head = (engine.ctx, p(t), p(t), None, 3, None, 0)
+    assert lib.gci_clip_sites_size(*head, ctypes.byref(n)) == 0 and n.value == 4
+    assert lib.gci_indel_sites_size(*head, ctypes.byref(n)) == 0 and n.value == 2
+    out = engine.to_device(np.full((4 + GUARD, 6), PATTERN, dtype=np.int32))
+    assert lib.gci_clip_sites_write(*head, p(out), 4) == _lib.GCI_E_INVALID
+    assert lib.gci_indel_sites_write(*head, p(out), 4) == 0
+    engine.sync()
+    host = np.ascontiguousarray(out.cpu().numpy()).reshape(-1, 6)
+    assert site_rows(host[:2].view(INDEL_SITE_DTYPE).reshape(-1)) == [(0, 10, 13, 4, 4, 0), (0, 40, 41, 5, 5, 0)] and (host[2:] == PATTERN).all()
+
+
 # ---- whole files -----------------------------------------------------------------------------------------------------------------------
 
 CONTIGS = (("ctgA", 300_000), ("ctgB", 200_000), ("ctgC", 6_000))          # no simulated read lies on ctgC: what is planted there is all there is

@@ -28,18 +28,11 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from site_scan import scan_alone  # noqa: E402
 
 CONTIGS = (("h1", 30_000_000), ("h2", 20_000_000))
-
-
-def _timed(engine, call) -> float:
-    T = engine.T
-    a, b = T.Event(enable_timing=True), T.Event(enable_timing=True)
-    a.record(engine.stream)
-    call()
-    b.record(engine.stream)
-    b.synchronize()
-    return a.elapsed_time(b)
 
 
 def _wall(engine, call) -> float:
@@ -107,13 +100,7 @@ def main(out: str = "", runs: int = 3, scale: float = 1.0, scan_mb: int = 1000) 
     size()
     write()
     engine.sync()
-    scan = {"size": [], "write": []}
-    for _ in range(max(runs, 5)):
-        scan["size"].append(round(_timed(engine, size), 4))
-        scan["write"].append(round(_timed(engine, write), 4))
-    read_bytes = 2 * 4 * int(engine.total)
-    res["scan"] = {"elements": int(engine.total), "sites": int(n.value), "ms": scan, "ms_min_median": {k: [min(v), round(statistics.median(v), 4)] for k, v in scan.items()},
-                   "size_pass_bytes": read_bytes, "size_pass_GB_per_s": round(read_bytes / (statistics.median(scan["size"]) * 1e-3) / 1e9, 1)}
+    res["scan"] = scan_alone(engine, runs, size, write, lambda: n.value, 2)
     if out:
         os.makedirs(out, exist_ok=True)
         with open(os.path.join(out, "clips_pass.json"), "w") as f:
