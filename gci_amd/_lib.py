@@ -162,6 +162,13 @@ EXPORTS = [
     ("gci_bam_mismatch_write", c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_int, c_void_p, c_void_p, c_uint64, c_void_p]),
     ("gci_mismatch_sites_size", c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, POINTER(Window), c_uint32, POINTER(c_uint64)]),
     ("gci_mismatch_sites_write", c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, POINTER(Window), c_uint32, c_void_p, c_uint64]),
+    ("gci_bam_allele_size", c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_int, c_void_p, c_int32, c_uint32, c_int, c_void_p, c_void_p,
+                                    c_void_p]),
+    ("gci_bam_allele_write", c_int, [c_void_p, c_void_p, c_uint64, c_void_p, c_uint32, c_int, c_void_p, c_void_p, c_uint64, c_void_p]),
+    ("gci_allele_sites_size", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, POINTER(Window), c_uint32,
+                                      POINTER(c_uint64)]),
+    ("gci_allele_sites_write", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, POINTER(Window), c_uint32,
+                                       c_void_p, c_uint64]),
     ("gci_depth_deflate_from_build", c_int, [c_void_p, c_void_p]),
     ("gci_depth_deflate_size", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p]),
     ("gci_depth_deflate_write", c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_void_p, c_void_p, c_void_p,

@@ -29,6 +29,7 @@ RUN_DTYPE = np.dtype([("start", "<u4"), ("depth", "<i4")])          # gci_depth_
 SITE_DTYPE = np.dtype([("contig", "<i4"), ("pos", "<i4"), ("left", "<i4"), ("right", "<i4"), ("depth", "<i4"), ("pad", "<i4")])      # gci_clip_site
 INDEL_SITE_DTYPE = np.dtype([("contig", "<i4"), ("start", "<i4"), ("end", "<i4"), ("del", "<i4"), ("ins", "<i4"), ("depth", "<i4")])      # gci_indel_site
 MISMATCH_SITE_DTYPE = np.dtype([("contig", "<i4"), ("start", "<i4"), ("end", "<i4"), ("mismatch", "<i4"), ("depth", "<i4")])      # gci_mismatch_site
+ALLELE_SITE_DTYPE = np.dtype([("contig", "<i4"), ("pos", "<i4"), ("ref", "<i4"), ("alt", "<i4"), ("n", "<i4", (4,)), ("depth", "<i4")])      # gci_allele_site
 GCI_TILE = 4096
 
 
@@ -47,7 +48,8 @@ gci_depth_text_parse gci_sdepth_index gci_sdepth_parse gci_depth_gz_scan gci_dep
 gci_depth_runs_write gci_bedgraph_size gci_bedgraph_write gci_depth_hist gci_bam_cover_size gci_bam_cover_write gci_track_add
 gci_bam_fate gci_bam_cover_size_sel gci_name_join_fate gci_fate_refine gci_bam_reads_size gci_bam_reads_write gci_bam_sweep gci_bam_clip_size gci_bam_clip_write gci_clip_sites_size gci_clip_sites_write
 gci_bam_indel_size gci_bam_indel_write gci_indel_sites_size gci_indel_sites_write
-gci_fasta_codes gci_bam_mismatch_size gci_bam_mismatch_write gci_mismatch_sites_size gci_mismatch_sites_write""".split()
+gci_fasta_codes gci_bam_mismatch_size gci_bam_mismatch_write gci_mismatch_sites_size gci_mismatch_sites_write
+gci_bam_allele_size gci_bam_allele_write gci_allele_sites_size gci_allele_sites_write""".split()
 _PROTO = {name: (name, res, args) for name, res, args in _lib.EXPORTS}
 EXPORTS = [_PROTO[name] for name in _SEAMS] + [("gci_cpu_option", c_int, [c_void_p, c_char_p, c_int])]
 
@@ -414,6 +416,52 @@ class CpuEngine:
         if (out[total:] != -0x5A5A5A5B).any():
             raise CpuError(-1, "gci_mismatch_sites_write wrote behind its sites")
         return out.view(MISMATCH_SITE_DTYPE).reshape(-1)[:total]
+
+    # ---- allele_sites.py (the twins of k_mismatch.hip's allele calls)
+    def bam_allele(self, stream: np.ndarray, offs: np.ndarray, ref_sel: np.ndarray, codes: np.ndarray, has_seq: bool = True, excl_flags: int = 0x704,
+                   min_mapq: int = 0, check: bool = True, cap: Optional[int] = None, guard: int = 0):
+        """device.Engine.bam_allele's twin -> (the A, C, G, T events as IVL_DTYPE, [records counted, A, C, G, T events, pairs compared]).
+        cap, guard: as bam_indel takes them."""
+        stream = np.ascontiguousarray(stream, dtype=np.uint8)
+        offs = np.ascontiguousarray(offs, dtype=np.uint64)
+        ref_sel = np.ascontiguousarray(ref_sel, dtype=np.int32)
+        counts = np.zeros(6, dtype=np.uint64)
+        self.last_status = np.zeros(1, dtype=np.uint64)
+        self._chk(self.lib.gci_bam_allele_size(self.ctx, _p(stream), stream.shape[0], _p(offs), offs.shape[0], int(has_seq), _p(ref_sel),
+                                               ref_sel.shape[0], int(excl_flags), int(min_mapq), _p(codes), _p(counts), _p(self.last_status)),
+                  "gci_bam_allele_size")
+        if check:
+            self._status(self.last_status, "gci_bam_allele_size")
+        ends = np.cumsum([0] + [int(c) for c in counts[1:5]]).tolist()
+        n = ends[4]
+        room = n if cap is None else int(cap)
+        out = np.full((max(room, n) + guard + 1, 4), -0x5A5A5A5B, dtype=np.int32)
+        self.last_out = out
+        self._chk(self.lib.gci_bam_allele_write(self.ctx, _p(stream), stream.shape[0], _p(offs), offs.shape[0], int(has_seq), _p(codes), _p(out),
+                                                room, _p(self.last_status)), "gci_bam_allele_write")
+        if (out[n:] != -0x5A5A5A5B).any():
+            raise CpuError(-1, "gci_bam_allele_write wrote behind its events")
+        ivl = out.view(IVL_DTYPE).reshape(-1)
+        return (*(ivl[ends[k]:ends[k + 1]] for k in range(4)), [int(c) for c in counts])
+
+    def allele_sites(self, a: np.ndarray, c: np.ndarray, g: np.ndarray, t: np.ndarray, depth: np.ndarray, codes: np.ndarray, min_reads: int,
+                     frac_ppm: int, windows: Sequence[Tuple[int, int]] = (), cap: Optional[int] = None) -> np.ndarray:
+        """device.Engine.allele_sites's twin -> ALLELE_SITE_DTYPE [n].  cap: the room offered to the write call."""
+        nw = len(windows)
+        w = (_Window * max(nw, 1))()
+        for i, (lo, hi) in enumerate(windows):
+            w[i].begin, w[i].end = int(lo), int(hi)
+        n = ctypes.c_uint64(0)
+        head = (self.ctx, _p(a), _p(c), _p(g), _p(t), _p(depth), _p(codes), int(min_reads), int(frac_ppm), w, nw)
+        self._chk(self.lib.gci_allele_sites_size(*head, ctypes.byref(n)), "gci_allele_sites_size")
+        total = int(n.value)
+        room = total if cap is None else int(cap)
+        out = np.full((max(room, total) + 1, 9), -0x5A5A5A5B, dtype=np.int32)
+        self.last_out = out
+        self._chk(self.lib.gci_allele_sites_write(*head, _p(out), room), "gci_allele_sites_write")
+        if (out[total:] != -0x5A5A5A5B).any():
+            raise CpuError(-1, "gci_allele_sites_write wrote behind its sites")
+        return out.view(ALLELE_SITE_DTYPE).reshape(-1)[:total]
 
     def track_add(self, acc: np.ndarray, add: np.ndarray) -> np.ndarray:
         self._chk(self.lib.gci_track_add(self.ctx, _p(acc), _p(add)), "gci_track_add")

@@ -83,7 +83,7 @@ extern "C" int gci_ctx_destroy(gci_ctx* ctx)
                       &ctx->bg_tile_cnt, &ctx->bg_tile_off, &ctx->bg_blk, &ctx->bg_wtab, &ctx->bg_blk_bytes, &ctx->bg_blk_off, &ctx->bg_blk2, &ctx->hist_chunk_first,
                       &ctx->cover_rec, &ctx->cover_chunk, &ctx->fate_rec, &ctx->fate_chunk, &ctx->reads_rec, &ctx->reads_chunk, &ctx->reads_names, &ctx->sweep_rec, &ctx->sweep_chunk,
                       &ctx->clip_rec, &ctx->clip_chunk, &ctx->indel_rec, &ctx->indel_chunk, &ctx->site_tiles,
-                      &ctx->mm_fasta, &ctx->mm_rec, &ctx->mm_chunk};
+                      &ctx->mm_fasta, &ctx->mm_rec, &ctx->mm_chunk, &ctx->al_rec, &ctx->al_chunk};
     for (DevBuf* b : bufs) if (b->p) (void)gci_dfree(b->p);
     for (DevBuf& b : ctx->paf_pool) if (b.p) (void)gci_dfree(b.p);
     if (ctx->h_pinned) (void)hipHostFree(ctx->h_pinned);

@@ -69,7 +69,7 @@ struct gci_ctx {
     std::vector<gci_clip_site> sites;
     struct SiteAsk {                        // what a *_sites_size call measured: its _write call must ask the same
         bool valid = false;
-        const void* track[3] = {nullptr, nullptr, nullptr};
+        const void* track[6] = {};          // (gci_allele_sites_*: six arrays; the others leave the rest null)
         int32_t min_reads = 0, frac = 0;
         uint32_t n_windows = 0;
     };
@@ -97,6 +97,18 @@ struct gci_ctx {
     const void* mm_codes = nullptr;
     std::vector<gci_mismatch_site> msites;
     SiteAsk msites_ask;
+    // allele_sites.py: the events the last gci_bam_allele_size found, a list per read base (A, C, G, T), each in record and position
+    // order, and the sites the last gci_allele_sites_size found, with what each call measured
+    std::vector<gci_ivl> al_events[4];
+    uint64_t al_status = ~0ull;
+    bool al_valid = false;
+    uint32_t al_n_rec = 0;
+    uint64_t al_n_bytes = 0;
+    const void* al_stream = nullptr;
+    const void* al_off = nullptr;
+    const void* al_codes = nullptr;
+    std::vector<gci_allele_site> asites;
+    SiteAsk asites_ask;
 };
 
 namespace {
@@ -339,8 +351,8 @@ gci_ctx::SiteAsk site_ask(const void* a, const void* b, const void* c, int32_t m
 template <typename Site>
 int sites_write(const gci_ctx::SiteAsk& kept, const gci_ctx::SiteAsk& ask, const std::vector<Site>& sites, Site* out, uint64_t cap)
 {
-    if (!kept.valid || kept.track[0] != ask.track[0] || kept.track[1] != ask.track[1] || kept.track[2] != ask.track[2] ||
-        kept.min_reads != ask.min_reads || kept.frac != ask.frac || kept.n_windows != ask.n_windows)
+    if (!kept.valid || !std::equal(kept.track, kept.track + 6, ask.track) || kept.min_reads != ask.min_reads || kept.frac != ask.frac ||
+        kept.n_windows != ask.n_windows)
         return GCI_E_INVALID;
     if (!sites.empty() && !out) return GCI_E_INVALID;
     if (cap < sites.size()) return GCI_E_CAPACITY;
@@ -698,6 +710,58 @@ int bg_window_bytes(gci_ctx* ctx, const gci_depth_run* runs, const uint64_t* win
         bytes[w] = s;
     });
     return GCI_OK;
+}
+
+// mismatch_sites.py, allele_sites.py: the records of gci_bam_mismatch_size, a base at a time (include/gci_hip.h) -- event(contig, p, nib)
+// for every compared pair whose codes differ, nib the read's; the status word, the records counted and the pairs compared
+template <typename F>
+void mismatch_records(const gci_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, const uint64_t* rec_off, uint32_t n_rec, const int32_t* ref_sel,
+                      int32_t n_ref, uint32_t excl_flags, int min_mapq, const uint8_t* codes, uint64_t& st, uint64_t& counted, uint64_t& compared,
+                      F event)
+{
+    st = ~0ull; counted = 0; compared = 0;
+    for (uint32_t i = 0; i < n_rec; i++) {
+        const uint64_t word = ((uint64_t)i << 8) | (uint64_t)(uint8_t)(-GCI_E_MALFORMED);
+        gci_ctx::CoverRec r;
+        SeqAt sq;
+        if (cover_parse(bam, n_bytes, rec_off[i], true, ref_sel, n_ref, excl_flags, min_mapq, r, &sq) != GCI_OK) { st = std::min(st, word); continue; }
+        if (r.contig < 0) continue;                                         // skipped
+        counted++;
+        const uint8_t* ops = bam + r.ops_off;
+        const uint8_t* seq = bam + sq.seq_off;
+        const uint64_t n = r.n_ops;
+        const uint32_t l_seq = sq.l_seq;
+        // first pass: codes 9 - 15 and the query length
+        bool bad = false;
+        uint64_t qlen = 0;
+        for (uint64_t k = 0; k < n; k++) {
+            const uint32_t w = rd32(ops + 4 * k), op = w & 0xFu;
+            if (op >= 9u) bad = true;
+            if (op == 0u || op == 1u || op == 4u || op == 7u || op == 8u) qlen += w >> 4;          // M I S = X
+        }
+        if (l_seq > 0 && qlen != (uint64_t)l_seq) bad = true;
+        if (bad) st = std::min(st, word);
+        if (l_seq == 0 || qlen != (uint64_t)l_seq) continue;                    // nothing of it is compared
+        const int32_t contig = r.contig, pos = r.pos;
+        const uint64_t L = contig < ctx->n_contigs ? std::min<uint64_t>((uint64_t)ctx->len[(size_t)contig], 0x7FFFFFFEull) : 0;
+        const uint8_t* ref = L ? codes + ctx->off[(size_t)contig] : codes;
+        uint64_t at = (uint64_t)pos, q = 0;
+        for (uint64_t k = 0; k < n && at < L; k++) {
+            const uint32_t w = rd32(ops + 4 * k), op = w & 0xFu;
+            const uint64_t len = w >> 4;
+            if (op == 0u || op == 7u || op == 8u) {
+                for (uint64_t j = 0; j < len && at + j < L; j++) {
+                    const uint32_t sb = seq[(q + j) >> 1], nib = ((q + j) & 1u) ? (sb & 15u) : (sb >> 4), rc = ref[at + j];
+                    const bool rb = rc == 1 || rc == 2 || rc == 4 || rc == 8, qb = nib == 1 || nib == 2 || nib == 4 || nib == 8;
+                    if (!rb || !qb) continue;
+                    compared++;
+                    if (rc != nib) event(contig, (int32_t)(at + j), nib);
+                }
+            }
+            if (op == 0u || op == 2u || op == 3u || op == 7u || op == 8u) at += len;              // M D N = X
+            if (op == 0u || op == 1u || op == 4u || op == 7u || op == 8u) q += len;               // M I S = X
+        }
+    }
 }
 
 }  // namespace
@@ -1397,49 +1461,9 @@ int gci_bam_mismatch_size(gci_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, co
     if (lst) return lst;
     ctx->mm_valid = false;
     ctx->mm_events.clear();
-    uint64_t st = ~0ull, counted = 0, compared = 0;
-    for (uint32_t i = 0; i < n_rec; i++) {
-        const uint64_t word = ((uint64_t)i << 8) | (uint64_t)(uint8_t)(-GCI_E_MALFORMED);
-        gci_ctx::CoverRec r;
-        SeqAt sq;
-        if (cover_parse(bam, n_bytes, rec_off[i], true, ref_sel, n_ref, excl_flags, min_mapq, r, &sq) != GCI_OK) { st = std::min(st, word); continue; }
-        if (r.contig < 0) continue;                                         // skipped
-        counted++;
-        const uint8_t* ops = bam + r.ops_off;
-        const uint8_t* seq = bam + sq.seq_off;
-        const uint64_t n = r.n_ops;
-        const uint32_t l_seq = sq.l_seq;
-        // first pass: codes 9 - 15 and the query length
-        bool bad = false;
-        uint64_t qlen = 0;
-        for (uint64_t k = 0; k < n; k++) {
-            const uint32_t w = rd32(ops + 4 * k), op = w & 0xFu;
-            if (op >= 9u) bad = true;
-            if (op == 0u || op == 1u || op == 4u || op == 7u || op == 8u) qlen += w >> 4;          // M I S = X
-        }
-        if (l_seq > 0 && qlen != (uint64_t)l_seq) bad = true;
-        if (bad) st = std::min(st, word);
-        if (l_seq == 0 || qlen != (uint64_t)l_seq) continue;                    // nothing of it is compared
-        const int32_t contig = r.contig, pos = r.pos;
-        const uint64_t L = contig < ctx->n_contigs ? std::min<uint64_t>((uint64_t)ctx->len[(size_t)contig], 0x7FFFFFFEull) : 0;
-        const uint8_t* ref = L ? codes + ctx->off[(size_t)contig] : codes;
-        uint64_t at = (uint64_t)pos, q = 0;
-        for (uint64_t k = 0; k < n && at < L; k++) {
-            const uint32_t w = rd32(ops + 4 * k), op = w & 0xFu;
-            const uint64_t len = w >> 4;
-            if (op == 0u || op == 7u || op == 8u) {
-                for (uint64_t j = 0; j < len && at + j < L; j++) {
-                    const uint32_t sb = seq[(q + j) >> 1], nib = ((q + j) & 1u) ? (sb & 15u) : (sb >> 4), rc = ref[at + j];
-                    const bool rb = rc == 1 || rc == 2 || rc == 4 || rc == 8, qb = nib == 1 || nib == 2 || nib == 4 || nib == 8;
-                    if (!rb || !qb) continue;
-                    compared++;
-                    if (rc != nib) ctx->mm_events.push_back(gci_ivl{contig, (int32_t)(at + j), (int32_t)(at + j), 0});
-                }
-            }
-            if (op == 0u || op == 2u || op == 3u || op == 7u || op == 8u) at += len;              // M D N = X
-            if (op == 0u || op == 1u || op == 4u || op == 7u || op == 8u) q += len;               // M I S = X
-        }
-    }
+    uint64_t st, counted, compared;
+    mismatch_records(ctx, bam, n_bytes, rec_off, n_rec, ref_sel, n_ref, excl_flags, min_mapq, codes, st, counted, compared,
+                     [&](int32_t contig, int32_t p, uint32_t) { ctx->mm_events.push_back(gci_ivl{contig, p, p, 0}); });
     ctx->mm_status = st;
     ctx->mm_valid = true; ctx->mm_n_rec = n_rec; ctx->mm_n_bytes = n_bytes; ctx->mm_stream = bam; ctx->mm_off = rec_off; ctx->mm_codes = codes;
     h_counts[0] = counted; h_counts[1] = ctx->mm_events.size(); h_counts[2] = compared;
@@ -1504,6 +1528,93 @@ int gci_mismatch_sites_write(gci_ctx* ctx, const int32_t* mm, const int32_t* dep
     const int lst = need_layout(ctx);
     if (lst) return lst;
     return sites_write(ctx->msites_ask, site_ask(mm, depth, nullptr, min_reads, frac_ppm, n_windows), ctx->msites, out, cap);
+}
+
+/* ---- allele_sites.py: which base the reads carry where they disagree (the twins of k_mismatch.hip's allele calls, from the text of
+ * include/gci_hip.h: a record, a base, an element at a time) ---- */
+int gci_bam_allele_size(gci_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, const uint64_t* rec_off, uint32_t n_rec, int has_seq, const int32_t* ref_sel,
+                        int32_t n_ref, uint32_t excl_flags, int min_mapq, const uint8_t* codes, uint64_t* h_counts, uint64_t* status)
+{
+    if (!ctx || !h_counts || !status || !codes || n_ref < 0 || has_seq != 1 || (n_rec && (!bam || !rec_off || !ref_sel))) return GCI_E_INVALID;
+    const int lst = need_layout(ctx);
+    if (lst) return lst;
+    ctx->al_valid = false;
+    for (auto& list : ctx->al_events) list.clear();
+    uint64_t st, counted, compared;
+    mismatch_records(ctx, bam, n_bytes, rec_off, n_rec, ref_sel, n_ref, excl_flags, min_mapq, codes, st, counted, compared,
+                     [&](int32_t contig, int32_t p, uint32_t nib) {          // nib is 1, 2, 4 or 8: A, C, G, T
+                         ctx->al_events[nib == 1 ? 0 : nib == 2 ? 1 : nib == 4 ? 2 : 3].push_back(gci_ivl{contig, p, p, 0});
+                     });
+    ctx->al_status = st;
+    ctx->al_valid = true; ctx->al_n_rec = n_rec; ctx->al_n_bytes = n_bytes; ctx->al_stream = bam; ctx->al_off = rec_off; ctx->al_codes = codes;
+    h_counts[0] = counted; h_counts[5] = compared;
+    for (int k = 0; k < 4; k++) h_counts[1 + k] = ctx->al_events[k].size();
+    *status = st;
+    return GCI_OK;
+}
+
+int gci_bam_allele_write(gci_ctx* ctx, const uint8_t* bam, uint64_t n_bytes, const uint64_t* rec_off, uint32_t n_rec, int has_seq, const uint8_t* codes,
+                         gci_ivl* out, uint64_t cap, uint64_t* status)
+{
+    if (!ctx || !status || !codes || has_seq != 1 || (n_rec && (!bam || !rec_off))) return GCI_E_INVALID;
+    const int lst = need_layout(ctx);
+    if (lst) return lst;
+    if (!ctx->al_valid || ctx->al_n_rec != n_rec || ctx->al_n_bytes != n_bytes || bam != ctx->al_stream || rec_off != ctx->al_off || codes != ctx->al_codes)
+        return GCI_E_INVALID;
+    uint64_t total = 0;
+    for (const auto& list : ctx->al_events) total += list.size();
+    if (total && !out) return GCI_E_INVALID;
+    if (cap < total) return GCI_E_CAPACITY;
+    for (const auto& list : ctx->al_events) out = std::copy(list.begin(), list.end(), out);      // A, then C, then G, then T
+    *status = ctx->al_status;
+    return GCI_OK;
+}
+
+static gci_ctx::SiteAsk allele_ask(const int32_t* a, const int32_t* c, const int32_t* g, const int32_t* t, const int32_t* depth, const uint8_t* codes,
+                                   int32_t min_reads, int32_t frac_ppm, uint32_t n_windows)
+{
+    gci_ctx::SiteAsk m = site_ask(a, c, g, min_reads, frac_ppm, n_windows);
+    m.track[3] = t; m.track[4] = depth; m.track[5] = codes;
+    return m;
+}
+
+int gci_allele_sites_size(gci_ctx* ctx, const int32_t* a, const int32_t* c, const int32_t* g, const int32_t* t, const int32_t* depth, const uint8_t* codes,
+                          int32_t min_reads, int32_t frac_ppm, const gci_window* h_windows, uint32_t n_windows, uint64_t* h_n_sites)
+{
+    if (!ctx || !a || !c || !g || !t || !depth || !codes || !h_n_sites || min_reads < 1 || frac_ppm < 0 || frac_ppm > 1000000 || (n_windows && !h_windows))
+        return GCI_E_INVALID;
+    const int lst = need_layout(ctx);
+    if (lst) return lst;
+    if ((((uintptr_t)a) | ((uintptr_t)c) | ((uintptr_t)g) | ((uintptr_t)t) | ((uintptr_t)depth)) & 15u) return GCI_E_INVALID;
+    ctx->asites_ask.valid = false;
+    *h_n_sites = 0;
+    std::vector<gci_window> ws;
+    if (!site_windows(ctx, h_windows, n_windows, ws)) return GCI_E_INVALID;   // not sorted and disjoint
+    ctx->asites.clear();
+    for (const gci_window& w : ws) {
+        for (int64_t p = w.begin; p < w.end; p++) {
+            const int32_t n[4] = {a[p], c[p], g[p], t[p]};
+            int k = 0;                                                      // the first that reaches the largest: a tie goes to the earlier letter
+            for (int j = 1; j < 4; j++) if (n[j] > n[k]) k = j;
+            if (n[k] < min_reads || (int64_t)n[k] * 1000000ll < (int64_t)frac_ppm * (int64_t)depth[p]) continue;
+            const int32_t contig = (int32_t)(std::upper_bound(ctx->off.begin(), ctx->off.end(), p) - ctx->off.begin()) - 1;
+            const int64_t pos = p - ctx->off[(size_t)contig];
+            if (pos >= ctx->len[(size_t)contig]) continue;                  // padding
+            ctx->asites.push_back(gci_allele_site{contig, (int32_t)pos, (int32_t)codes[p], 1 << k, {n[0], n[1], n[2], n[3]}, depth[p]});
+        }
+    }
+    ctx->asites_ask = allele_ask(a, c, g, t, depth, codes, min_reads, frac_ppm, n_windows);
+    *h_n_sites = ctx->asites.size();
+    return GCI_OK;
+}
+
+int gci_allele_sites_write(gci_ctx* ctx, const int32_t* a, const int32_t* c, const int32_t* g, const int32_t* t, const int32_t* depth, const uint8_t* codes,
+                           int32_t min_reads, int32_t frac_ppm, const gci_window* h_windows, uint32_t n_windows, gci_allele_site* out, uint64_t cap)
+{
+    if (!ctx || !a || !c || !g || !t || !depth || !codes || min_reads < 1 || (n_windows && !h_windows)) return GCI_E_INVALID;
+    const int lst = need_layout(ctx);
+    if (lst) return lst;
+    return sites_write(ctx->asites_ask, allele_ask(a, c, g, t, depth, codes, min_reads, frac_ppm, n_windows), ctx->asites, out, cap);
 }
 
 /* ---- filter_reads.py: the records of chosen classes over a set of regions as rows of text (k_reads.hip's twins: a record at a time) ---- */

@@ -37,9 +37,9 @@ static inline dim3 wave_grid(unsigned long long n) { return dim3((uint32_t)((n +
 
 // gci_site_tiles.hpp: what the last *_sites_size call of any lister measured, for the *_sites_write call that follows it
 struct SiteMemo {
-    int lister = 0;                         // the Emit type's LISTER: 1 clips, 2 indels, 3 mismatch
+    int lister = 0;                         // the Emit type's LISTER: 1 clips, 2 indels, 3 mismatch, 4 alleles
     uint64_t epoch = 0, total = 0;          // ctx->win_epoch of its windows (0: no size call yet), its sites
-    const void* track[3] = {nullptr, nullptr, nullptr};
+    const void* track[6] = {};              // the arrays the call was given (alleles: A, C, G, T, depth, codes); the rest stay null
     int32_t min_reads = 0, frac = 0;
     uint32_t n_windows = 0;
 };
@@ -190,7 +190,15 @@ struct gci_ctx {
     const void* mm_stream = nullptr;
     const void* mm_off = nullptr;
     const void* mm_codes = nullptr;
-    // gci_site_tiles.hpp: what gci_{clip,indel,mismatch}_sites_size keeps for the _write call -- per window tile its sites or run starts
+    // ... and what gci_bam_allele_size keeps for gci_bam_allele_write: the same scratch with four counts a chunk, and a memo of its own
+    DevBuf al_rec, al_chunk;
+    bool al_valid = false;
+    uint32_t al_n_rec = 0;
+    uint64_t al_n_bytes = 0, al_n_chunks = 0, al_total = 0;
+    const void* al_stream = nullptr;
+    const void* al_off = nullptr;
+    const void* al_codes = nullptr;
+    // gci_site_tiles.hpp: what gci_{clip,indel,mismatch,allele}_sites_size keeps for the _write call -- per window tile its sites or run starts
     // and their scan, and the one memo.  Every size call runs gci_set_windows, so what another lister left here is dead by then
     DevBuf site_tiles;
     SiteMemo site_memo;

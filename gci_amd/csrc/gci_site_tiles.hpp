@@ -1,6 +1,6 @@
 // gci_site_tiles.hpp -- the site lister of k_clips.hip, k_indels.hip and k_mismatch.hip: K8's windows cut into 4096-element tiles, one
 // workgroup each; which of a tile's elements lie inside the window and inside their contig; which of them are HOT (a predicate); the
-// hot elements (clips) or the starts of the runs of hot elements (indels, mismatch) counted per tile, scanned, and written by rank; a
+// hot elements (clips, alleles) or the starts of the runs of hot elements (indels, mismatch) counted per tile, scanned, and written by rank; a
 // wave per run that walks to its end and reduces what the site reports; and the host frame of a *_sites_size / _write pair.
 //
 //   k_sites_count<Hot, RUNS>        one workgroup per window tile, the coalesced mapping: lane t of round j takes the four elements at
@@ -228,8 +228,8 @@ static inline SiteGrid site_grid(const gci_ctx* ctx)
 
 static inline bool site_memo_same(const SiteMemo& a, const SiteMemo& b)
 {
-    return a.lister == b.lister && a.track[0] == b.track[0] && a.track[1] == b.track[1] && a.track[2] == b.track[2] &&
-           a.min_reads == b.min_reads && a.frac == b.frac && a.n_windows == b.n_windows;
+    for (int k = 0; k < 6; k++) if (a.track[k] != b.track[k]) return false;
+    return a.lister == b.lister && a.min_reads == b.min_reads && a.frac == b.frac && a.n_windows == b.n_windows;
 }
 
 // What a *_sites_size export does once its own arguments are checked: the windows (none: every contig) become the context's -- which

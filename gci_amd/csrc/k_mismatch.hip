@@ -2,7 +2,9 @@
 // bytes into one 4-bit code per base in the track layout; gci_bam_mismatch_size / _write walk every counted record's CIGAR with a
 // reference AND a query position, compare the SEQ nibble with the assembly's code under M / = / X and turn every mismatch into an
 // EVENT of one base for the depth build; gci_mismatch_sites_size / _write list the RUNS of bases where the built track is hot
-// against the depth track (include/gci_hip.h states all three).
+// against the depth track (include/gci_hip.h states all three).  allele_sites.py is the same walk with the read's base kept:
+// gci_bam_allele_size / _write rank the events by that base into four lists, gci_allele_sites_size / _write list the single bases
+// where one allele's track is hot.
 //
 // The FASTA side.  Tiles of 4096 bytes, a lane 16 consecutive bytes (gci_text_tiles.hpp); a sequence byte is gci_fasta_n_scan's.
 //   k_fasta_rec_rank  one lane per record: the sequence bytes of the file in front of its body -- the scanned count of its tile plus
@@ -21,12 +23,18 @@
 //   k_rec_finish  one lane per record: codes 9 - 15 and S + M + I != l_seq into the status word, whether the record is counted
 //   k_mm_write    the same walk; a lane's slot is its chunk's offset + the mismatches of earlier steps + those of the lanes below it
 //                 (ballots and popcounts), so events come in (record, reference position) order
+//   k_al_count    the walk with a count per class of the read's base (A, C, G, T): cnt[class * n_chunks + chunk], so ONE scan over the
+//                 4 * n_chunks entries is the slot of every (class, chunk) in the concatenated output and the four list ends
+//   k_al_write    the walk; a lane packs its four counts of a step into 4 x 16 bits of one word (a step holds at most 64 * MM_BASES
+//                 events), one wave scan of the word ranks the lanes in all four classes; inside a lane base order decides
 // A record whose S + M + I is not l_seq is never walked: no SEQ byte beyond (l_seq + 1) / 2 is ever read.  The only global atomic
 // is the status word's atomicMin.
 //
 // The track side.  gci_site_tiles.hpp's lister, as k_indels.hip: the RUNS of hot elements, hot = mismatch >= min_reads and
 // mismatch * 1000000 >= frac_ppm * depth in 64 bits (HotMismatch); the depth track is read in every pass.  A site keeps the largest
-// mismatch count of its run and the depth at the FIRST base that reaches it (MmBest).
+// mismatch count of its run and the depth at the FIRST base that reaches it (MmBest).  The allele lister lists single elements, as
+// k_clips.hip's: hot = the largest of the four allele tracks passes the two tests (HotAllele), five tracks read in every pass; the
+// code array is read by the Emit only, for the sites it stores.
 #include "gci_cigar_sums.hpp"
 #include "gci_site_tiles.hpp"
 #include "gci_text_tiles.hpp"
@@ -153,22 +161,23 @@ struct MmChunkScratch {                  // carved out of ctx->mm_chunk
     unsigned long long* ref0;            // n_chunks + 1 each: the exclusive scans
     unsigned long long* qry0;
     unsigned long long* cmp0;
-    unsigned long long* mm0;
+    unsigned long long* mm0;             // classes * n_chunks + 1
     unsigned long long* blk;
-    uint32_t* n_mm;                      // mismatches of a chunk
+    uint32_t* n_mm;                      // mismatches of a chunk: [class * n_chunks + chunk]
 };
 
-static inline size_t mm_chunk_bytes(uint64_t n_chunks)
+// classes: 1 (gci_bam_mismatch_*: ctx->mm_chunk) or 4, the read's base A, C, G, T (gci_bam_allele_*: ctx->al_chunk)
+static inline size_t mm_chunk_bytes(uint64_t n_chunks, int classes)
 {
-    const size_t n = (size_t)n_chunks;
-    return sizeof(CigarSums) * n + 3 * 8 * n + 4 * 8 * (n + 1) + 8 * (scan_blocks(n) + 2) + 4 * n;
+    const size_t n = (size_t)n_chunks, m = (size_t)classes * n;
+    return sizeof(CigarSums) * n + 3 * 8 * n + 3 * 8 * (n + 1) + 8 * (m + 1) + 8 * (scan_blocks(m) + 2) + 4 * m;
 }
 
-static inline MmChunkScratch mm_chunk_scratch(gci_ctx* ctx, uint64_t n_chunks)
+static inline MmChunkScratch mm_chunk_scratch(const DevBuf& buf, uint64_t n_chunks, int classes)
 {
-    const size_t n = (size_t)n_chunks;
+    const size_t n = (size_t)n_chunks, m = (size_t)classes * n;
     MmChunkScratch s;
-    uint8_t* p = (uint8_t*)ctx->mm_chunk.p;
+    uint8_t* p = (uint8_t*)buf.p;
     s.sums = (CigarSums*)p; p += sizeof(CigarSums) * n;
     s.ref = (unsigned long long*)p; p += 8 * n;
     s.qry = (unsigned long long*)p; p += 8 * n;
@@ -176,8 +185,8 @@ static inline MmChunkScratch mm_chunk_scratch(gci_ctx* ctx, uint64_t n_chunks)
     s.ref0 = (unsigned long long*)p; p += 8 * (n + 1);
     s.qry0 = (unsigned long long*)p; p += 8 * (n + 1);
     s.cmp0 = (unsigned long long*)p; p += 8 * (n + 1);
-    s.mm0 = (unsigned long long*)p; p += 8 * (n + 1);
-    s.blk = (unsigned long long*)p; p += 8 * (scan_blocks(n) + 2);
+    s.mm0 = (unsigned long long*)p; p += 8 * (m + 1);
+    s.blk = (unsigned long long*)p; p += 8 * (scan_blocks(m) + 2);
     s.n_mm = (uint32_t*)p;
     return s;
 }
@@ -222,10 +231,14 @@ struct MmWalkArgs {
     const uint8_t* codes;
 };
 
-template <bool WRITE>
+// ALLELES: a mismatch is an event of the class of the read's base (A, C, G, T = 0 .. 3); chunk_mm and chunk_mm0 hold four entries a
+// chunk, [class * n_chunks + chunk], and chunk_mm0 is the scan over all of them: the slot in the concatenated lists
+template <bool WRITE, bool ALLELES>
 __device__ __forceinline__ void mm_walk(const MmWalkArgs& A, uint32_t* __restrict__ chunk_mm, unsigned long long* __restrict__ chunk_cmp,
                                         const unsigned long long* __restrict__ chunk_mm0, unsigned long long total, gci_ivl* __restrict__ out)
 {
+    static_assert(MM_BASES <= 8, "a step's events of one class must fit 16 bits, a lane's bases and classes 8 and 16");
+    constexpr int CLASSES = ALLELES ? 4 : 1;
     // of the round's 64 operations: the inclusive scan of the match lengths, and where each begins on the reference and in the read
     __shared__ unsigned long long s_inc[BLOCK / 64][64], s_ref[BLOCK / 64][64], s_qry[BLOCK / 64][64];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -235,7 +248,7 @@ __device__ __forceinline__ void mm_walk(const MmWalkArgs& A, uint32_t* __restric
     const CoverRec r = A.recs[rec];
     const CvSeq sq = A.seqs[rec];
     const unsigned long long ch_first = A.chunk0[rec], ch_last = A.chunk0[rec + 1];
-    uint32_t mms = 0;
+    uint32_t mms[CLASSES] = {0};                       // (constant indices only: registers)
     unsigned long long cmps = 0;
     // SEQ `*`, or a record whose operations do not add up to l_seq (k_rec_finish reports it): nothing is compared, no SEQ byte is read
     const bool walk = sq.l_seq != 0 && A.qry0[ch_last] - A.qry0[ch_first] == (unsigned long long)sq.l_seq;
@@ -248,7 +261,9 @@ __device__ __forceinline__ void mm_walk(const MmWalkArgs& A, uint32_t* __restric
         const unsigned long long L = (unsigned long long)(len < 0x7FFFFFFEll ? (len < 0 ? 0 : len) : 0x7FFFFFFEll);
         const uint8_t* __restrict__ ref = A.codes + (L ? A.contig_off[r.contig] : 0);
         const uint8_t* __restrict__ seq = A.bam + sq.seq_off;
-        unsigned long long o_mm = WRITE ? chunk_mm0[ch] : 0ull;                         // where the chunk's next mismatch goes
+        unsigned long long o_mm[CLASSES];                                               // where the chunk's next mismatch (of a class) goes
+#pragma unroll
+        for (int k = 0; k < CLASSES; k++) o_mm[k] = WRITE ? chunk_mm0[(unsigned long long)k * A.n_chunks + ch] : 0ull;
         for (uint32_t k0 = 0; k0 < c.n && at < L; k0 += 64) {                           // (behind the contig's end nothing is compared)
             const uint32_t k = k0 + lane;
             const bool valid = k < c.n;
@@ -273,7 +288,7 @@ __device__ __forceinline__ void mm_walk(const MmWalkArgs& A, uint32_t* __restric
 #pragma unroll
                     for (uint32_t step = 32; step >= 1; step >>= 1) if (s_inc[w][o + step - 1] <= j0) o += step;
                 }
-                uint32_t cmp = 0, mis = 0;
+                uint32_t cmp = 0, mis = 0, cls = 0;    // (cls: two bits a base, the class of its mismatch)
                 unsigned long long p_first = ~0ull;
 #pragma unroll
                 for (int b = 0; b < MM_BASES; b++) {
@@ -289,17 +304,31 @@ __device__ __forceinline__ void mm_walk(const MmWalkArgs& A, uint32_t* __restric
                         const bool both = ((0x116u >> rc) & 1u) && ((0x116u >> nib) & 1u);    // both one of 1 2 4 8 (rc, nib < 16)
                         cmp |= both ? (1u << b) : 0u;
                         mis |= (both && rc != nib) ? (1u << b) : 0u;
+                        if (ALLELES) cls |= (both && rc != nib) ? (((nib >> 1) - (nib >> 3)) << (2 * b)) : 0u;      // 1 2 4 8 -> 0 1 2 3
                     }
+                }
+                // ALLELES: the lane's events of the step per class, 16 bits each
+                unsigned long long word = 0;
+                if (ALLELES) {
+#pragma unroll
+                    for (int b = 0; b < MM_BASES; b++) word += ((mis >> b) & 1u) ? 1ull << (16u * ((cls >> (2 * b)) & 3u)) : 0ull;
                 }
                 if (WRITE) {
                     // base order is lane order, then the order inside the lane: the lanes below, then the lane's own lower bits
-                    unsigned long long slot = o_mm;
-                    uint32_t step_total = 0;
+                    unsigned long long slot = o_mm[0], below = 0, all = 0;
+                    if (ALLELES) {
+                        const unsigned long long inc = wave_inclusive<unsigned long long>(word, lane);
+                        below = inc - word;            // per class: the events of the lanes below, then of the lane's own lower bases too
+                        all = __shfl(inc, 63, 64);     // ... and of the whole step
+                    } else {
+                        uint32_t step_total = 0;
 #pragma unroll
-                    for (int b = 0; b < MM_BASES; b++) {
-                        const unsigned long long m = __ballot((mis >> b) & 1u);
-                        slot += (unsigned long long)__builtin_popcountll(m & lanes_below(lane));
-                        step_total += (uint32_t)__builtin_popcountll(m);
+                        for (int b = 0; b < MM_BASES; b++) {
+                            const unsigned long long m = __ballot((mis >> b) & 1u);
+                            slot += (unsigned long long)__builtin_popcountll(m & lanes_below(lane));
+                            step_total += (uint32_t)__builtin_popcountll(m);
+                        }
+                        o_mm[0] += step_total;
                     }
                     uint32_t bits = mis;
                     while (bits) {
@@ -312,12 +341,28 @@ __device__ __forceinline__ void mm_walk(const MmWalkArgs& A, uint32_t* __restric
                         const unsigned long long p = s_ref[w][oo] + (j - (oo ? s_inc[w][oo - 1] : 0ull));
                         gci_ivl e;
                         e.contig = r.contig; e.start = (int32_t)p; e.end = (int32_t)p; e.pad = 0;
+                        if (ALLELES) {
+                            const uint32_t k = (cls >> (2 * b)) & 3u;
+                            // (selects, not an index: o_mm stays in registers)
+                            const unsigned long long o_k = k == 0 ? o_mm[0] : k == 1 ? o_mm[CLASSES > 1 ? 1 : 0] : k == 2 ? o_mm[CLASSES > 2 ? 2 : 0]
+                                                                                                                        : o_mm[CLASSES > 3 ? 3 : 0];
+                            slot = o_k + ((below >> (16u * k)) & 0xFFFFull);
+                            below += 1ull << (16u * k);
+                        }
                         if (slot < total) out[slot] = e;
                         slot++;
                     }
-                    o_mm += step_total;
+                    if (ALLELES) {
+#pragma unroll
+                        for (int k = 0; k < CLASSES; k++) o_mm[k] += (all >> (16 * k)) & 0xFFFFull;
+                    }
                 } else {
-                    mms += (uint32_t)__builtin_popcount(mis);
+                    if (ALLELES) {
+#pragma unroll
+                        for (int k = 0; k < CLASSES; k++) mms[k] += (uint32_t)(word >> (16 * k)) & 0xFFFFu;
+                    } else {
+                        mms[0] += (uint32_t)__builtin_popcount(mis);
+                    }
                     cmps += (unsigned long long)__builtin_popcount(cmp);
                 }
                 if (__shfl(p_first, 0, 64) >= L) break;                  // (positions ascend with the base index: the rest is outside)
@@ -327,21 +372,37 @@ __device__ __forceinline__ void mm_walk(const MmWalkArgs& A, uint32_t* __restric
         }
     }
     if (!WRITE) {
-        mms = wave_sum<uint32_t>(mms);
+#pragma unroll
+        for (int k = 0; k < CLASSES; k++) mms[k] = wave_sum<uint32_t>(mms[k]);
         cmps = wave_sum<unsigned long long>(cmps);
-        if (lane == 0) { chunk_mm[ch] = mms; chunk_cmp[ch] = cmps; }
+        if (lane == 0) {
+#pragma unroll
+            for (int k = 0; k < CLASSES; k++) chunk_mm[(unsigned long long)k * A.n_chunks + ch] = mms[k];
+            chunk_cmp[ch] = cmps;
+        }
     }
 }
 
 __global__ __launch_bounds__(BLOCK) void k_mm_count(MmWalkArgs A, uint32_t* __restrict__ chunk_mm, unsigned long long* __restrict__ chunk_cmp)
 {
-    mm_walk<false>(A, chunk_mm, chunk_cmp, nullptr, 0, nullptr);
+    mm_walk<false, false>(A, chunk_mm, chunk_cmp, nullptr, 0, nullptr);
 }
 
 __global__ __launch_bounds__(BLOCK) void k_mm_write(MmWalkArgs A, const unsigned long long* __restrict__ chunk_mm0, unsigned long long total,
                                                     gci_ivl* __restrict__ out)
 {
-    mm_walk<true>(A, nullptr, nullptr, chunk_mm0, total, out);
+    mm_walk<true, false>(A, nullptr, nullptr, chunk_mm0, total, out);
+}
+
+__global__ __launch_bounds__(BLOCK) void k_al_count(MmWalkArgs A, uint32_t* __restrict__ chunk_al, unsigned long long* __restrict__ chunk_cmp)
+{
+    mm_walk<false, true>(A, chunk_al, chunk_cmp, nullptr, 0, nullptr);
+}
+
+__global__ __launch_bounds__(BLOCK) void k_al_write(MmWalkArgs A, const unsigned long long* __restrict__ chunk_al0, unsigned long long total,
+                                                    gci_ivl* __restrict__ out)
+{
+    mm_walk<true, true>(A, nullptr, nullptr, chunk_al0, total, out);
 }
 
 static inline MmWalkArgs mm_walk_args(gci_ctx* ctx, const uint8_t* d_stream, uint64_t n_bytes, uint32_t n_rec, unsigned long long n_chunks,
@@ -354,19 +415,23 @@ static inline MmWalkArgs mm_walk_args(gci_ctx* ctx, const uint8_t* d_stream, uin
     return A;
 }
 
-extern "C" int gci_bam_mismatch_size(gci_ctx* ctx, const uint8_t* d_stream, uint64_t n_bytes, const uint64_t* d_rec_off, uint32_t n_rec, int has_seq,
-                                     const int32_t* d_ref_sel, int32_t n_ref, uint32_t excl_flags, int min_mapq, const uint8_t* d_codes,
-                                     uint64_t* h_counts, uint64_t* d_status)
+struct MmMeasured {                      // on the host, after the synchronise
+    unsigned long long n_chunks = 0, n_counted = 0, n_cmp = 0;
+    unsigned long long end[4] = {0, 0, 0, 0};      // where the list of class k ends in the output: the events of classes 0 .. k
+};
+
+// what gci_bam_mismatch_size and gci_bam_allele_size do behind their argument checks, up to the synchronise: the parse, the chunks,
+// the two axes, the count pass (one class, or four with ALLELES) and its scan, the records counted, the status word
+template <bool ALLELES>
+static int mm_measure(gci_ctx* ctx, DevBuf& rec_buf, DevBuf& chunk_buf, const uint8_t* d_stream, uint64_t n_bytes, const uint64_t* d_rec_off,
+                      uint32_t n_rec, const int32_t* d_ref_sel, int32_t n_ref, uint32_t excl_flags, int min_mapq, const uint8_t* d_codes,
+                      uint64_t* d_status, MmMeasured& m)
 {
-    if (!ctx || !h_counts || !d_status || !d_codes || n_ref < 0 || has_seq != 1 || (n_rec && (!d_stream || !d_rec_off || !d_ref_sel)))
-        return GCI_E_INVALID;
-    if (!ctx->n_contigs) return GCI_E_NO_LAYOUT;
-    ctx->mm_valid = false;
-    h_counts[0] = h_counts[1] = h_counts[2] = 0;
+    constexpr int CLASSES = ALLELES ? 4 : 1;
     RecFrame F;
-    GCI_TRY(rec_frame_open(ctx, ctx->mm_rec, sizeof(CvSeq) * (size_t)n_rec, n_rec, F));
+    GCI_TRY(rec_frame_open(ctx, rec_buf, sizeof(CvSeq) * (size_t)n_rec, n_rec, F));
     const MmRecScratch R = mm_rec_scratch(F);
-    unsigned long long n_chunks = 0, n_mm = 0, n_cmp = 0, n_counted = 0;
+    unsigned long long n_chunks = 0, n_cmp = 0, n_counted = 0;
     if (n_rec) {
         const uint32_t groups = (n_rec + BLOCK - 1) / BLOCK;
         hipLaunchKernelGGL(k_mm_parse, dim3(groups), dim3(BLOCK), 0, ctx->stream, d_stream, n_bytes, d_rec_off, n_rec, d_ref_sel, n_ref, excl_flags,
@@ -376,8 +441,8 @@ extern "C" int gci_bam_mismatch_size(gci_ctx* ctx, const uint8_t* d_stream, uint
         const CigarSums* sums = nullptr;
         const unsigned long long* qry0 = nullptr;
         if (n_chunks) {
-            GCI_TRY(gci_ensure(ctx, ctx->mm_chunk, mm_chunk_bytes(n_chunks)));
-            const MmChunkScratch C = mm_chunk_scratch(ctx, n_chunks);
+            GCI_TRY(gci_ensure(ctx, chunk_buf, mm_chunk_bytes(n_chunks, CLASSES)));
+            const MmChunkScratch C = mm_chunk_scratch(chunk_buf, n_chunks, CLASSES);
             sums = C.sums; qry0 = C.qry0;
             hipLaunchKernelGGL(k_cigar_sums, cigar_sums_grid(n_chunks), dim3(BLOCK), 0, ctx->stream, d_stream, n_bytes, R.recs, R.chunk0, n_rec, n_chunks,
                                C.sums);
@@ -386,12 +451,14 @@ extern "C" int gci_bam_mismatch_size(gci_ctx* ctx, const uint8_t* d_stream, uint
             LAUNCHCHK("k_chunk_lens");
             GCI_TRY((device_exclusive_scan<unsigned long long, unsigned long long>(ctx, C.ref, C.ref0, C.blk, (int64_t)n_chunks, true)));
             GCI_TRY((device_exclusive_scan<unsigned long long, unsigned long long>(ctx, C.qry, C.qry0, C.blk, (int64_t)n_chunks, true)));
-            hipLaunchKernelGGL(k_mm_count, wave_grid(n_chunks), dim3(BLOCK), 0, ctx->stream,
+            hipLaunchKernelGGL(ALLELES ? k_al_count : k_mm_count, wave_grid(n_chunks), dim3(BLOCK), 0, ctx->stream,
                                mm_walk_args(ctx, d_stream, n_bytes, n_rec, n_chunks, R, C, d_codes), C.n_mm, C.cmp);
-            LAUNCHCHK("k_mm_count");
-            GCI_TRY((device_exclusive_scan<uint32_t, unsigned long long>(ctx, C.n_mm, C.mm0, C.blk, (int64_t)n_chunks, true)));
+            LAUNCHCHK(ALLELES ? "k_al_count" : "k_mm_count");
+            // ONE scan over the classes' counts, class by class: the slot of every (class, chunk), and at (k + 1) * n_chunks list k's end
+            GCI_TRY((device_exclusive_scan<uint32_t, unsigned long long>(ctx, C.n_mm, C.mm0, C.blk, (int64_t)(CLASSES * n_chunks), true)));
             GCI_TRY((device_exclusive_scan<unsigned long long, unsigned long long>(ctx, C.cmp, C.cmp0, C.blk, (int64_t)n_chunks, true)));
-            HIPCHK(hipMemcpyAsync(&n_mm, C.mm0 + n_chunks, 8, hipMemcpyDeviceToHost, ctx->stream));
+            for (int k = 0; k < CLASSES; k++)
+                HIPCHK(hipMemcpyAsync(&m.end[k], C.mm0 + (size_t)(k + 1) * n_chunks, 8, hipMemcpyDeviceToHost, ctx->stream));
             HIPCHK(hipMemcpyAsync(&n_cmp, C.cmp0 + n_chunks, 8, hipMemcpyDeviceToHost, ctx->stream));
         }
         launch_rec_finish(ctx, n_rec, R.recs, R.chunk0, sums, R.seqs, qry0, R.counted, R.status);
@@ -401,10 +468,26 @@ extern "C" int gci_bam_mismatch_size(gci_ctx* ctx, const uint8_t* d_stream, uint
     }
     HIPCHK(hipMemcpyAsync(d_status, R.status, 8, hipMemcpyDeviceToDevice, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
+    m.n_chunks = n_chunks; m.n_counted = n_counted; m.n_cmp = n_cmp;
+    return GCI_OK;
+}
+
+extern "C" int gci_bam_mismatch_size(gci_ctx* ctx, const uint8_t* d_stream, uint64_t n_bytes, const uint64_t* d_rec_off, uint32_t n_rec, int has_seq,
+                                     const int32_t* d_ref_sel, int32_t n_ref, uint32_t excl_flags, int min_mapq, const uint8_t* d_codes,
+                                     uint64_t* h_counts, uint64_t* d_status)
+{
+    if (!ctx || !h_counts || !d_status || !d_codes || n_ref < 0 || has_seq != 1 || (n_rec && (!d_stream || !d_rec_off || !d_ref_sel)))
+        return GCI_E_INVALID;
+    if (!ctx->n_contigs) return GCI_E_NO_LAYOUT;
+    ctx->mm_valid = false;
+    h_counts[0] = h_counts[1] = h_counts[2] = 0;
+    MmMeasured m;
+    GCI_TRY(mm_measure<false>(ctx, ctx->mm_rec, ctx->mm_chunk, d_stream, n_bytes, d_rec_off, n_rec, d_ref_sel, n_ref, excl_flags, min_mapq, d_codes,
+                              d_status, m));
     ctx->mm_valid = true;
-    ctx->mm_n_rec = n_rec; ctx->mm_n_bytes = n_bytes; ctx->mm_n_chunks = n_chunks; ctx->mm_n_mm = n_mm;
+    ctx->mm_n_rec = n_rec; ctx->mm_n_bytes = n_bytes; ctx->mm_n_chunks = m.n_chunks; ctx->mm_n_mm = m.end[0];
     ctx->mm_stream = d_stream; ctx->mm_off = d_rec_off; ctx->mm_codes = d_codes;
-    h_counts[0] = n_counted; h_counts[1] = n_mm; h_counts[2] = n_cmp;
+    h_counts[0] = m.n_counted; h_counts[1] = m.end[0]; h_counts[2] = m.n_cmp;
     return GCI_OK;
 }
 
@@ -423,10 +506,56 @@ extern "C" int gci_bam_mismatch_write(gci_ctx* ctx, const uint8_t* d_stream, uin
     const MmRecScratch R = mm_rec_scratch(rec_frame(ctx->mm_rec, n_rec));
     const unsigned long long n_chunks = ctx->mm_n_chunks;
     if (n_chunks && total) {
-        const MmChunkScratch C = mm_chunk_scratch(ctx, n_chunks);
+        const MmChunkScratch C = mm_chunk_scratch(ctx->mm_chunk, n_chunks, 1);
         hipLaunchKernelGGL(k_mm_write, wave_grid(n_chunks), dim3(BLOCK), 0, ctx->stream,
                            mm_walk_args(ctx, d_stream, n_bytes, n_rec, n_chunks, R, C, d_codes), C.mm0, total, d_out);
         LAUNCHCHK("k_mm_write");
+    }
+    HIPCHK(hipMemcpyAsync(d_status, R.status, 8, hipMemcpyDeviceToDevice, ctx->stream));
+    return GCI_OK;
+}
+
+// allele_sites.py: the same two calls with the events ranked by the read's base; a scratch and a memo of their own (ctx->al_*), so a
+// mismatch pair and an allele pair on one context do not end each other
+extern "C" int gci_bam_allele_size(gci_ctx* ctx, const uint8_t* d_stream, uint64_t n_bytes, const uint64_t* d_rec_off, uint32_t n_rec, int has_seq,
+                                   const int32_t* d_ref_sel, int32_t n_ref, uint32_t excl_flags, int min_mapq, const uint8_t* d_codes,
+                                   uint64_t* h_counts, uint64_t* d_status)
+{
+    if (!ctx || !h_counts || !d_status || !d_codes || n_ref < 0 || has_seq != 1 || (n_rec && (!d_stream || !d_rec_off || !d_ref_sel)))
+        return GCI_E_INVALID;
+    if (!ctx->n_contigs) return GCI_E_NO_LAYOUT;
+    ctx->al_valid = false;
+    for (int k = 0; k < 6; k++) h_counts[k] = 0;
+    MmMeasured m;
+    GCI_TRY(mm_measure<true>(ctx, ctx->al_rec, ctx->al_chunk, d_stream, n_bytes, d_rec_off, n_rec, d_ref_sel, n_ref, excl_flags, min_mapq, d_codes,
+                             d_status, m));
+    ctx->al_valid = true;
+    ctx->al_n_rec = n_rec; ctx->al_n_bytes = n_bytes; ctx->al_n_chunks = m.n_chunks; ctx->al_total = m.end[3];
+    ctx->al_stream = d_stream; ctx->al_off = d_rec_off; ctx->al_codes = d_codes;
+    h_counts[0] = m.n_counted; h_counts[5] = m.n_cmp;
+    for (int k = 0; k < 4; k++) h_counts[1 + k] = m.end[k] - (k ? m.end[k - 1] : 0ull);
+    return GCI_OK;
+}
+
+extern "C" int gci_bam_allele_write(gci_ctx* ctx, const uint8_t* d_stream, uint64_t n_bytes, const uint64_t* d_rec_off, uint32_t n_rec, int has_seq,
+                                    const uint8_t* d_codes, gci_ivl* d_out, uint64_t cap, uint64_t* d_status)
+{
+    if (!ctx || !d_status || !d_codes || has_seq != 1 || (n_rec && (!d_stream || !d_rec_off))) return GCI_E_INVALID;
+    if (!ctx->n_contigs) return GCI_E_NO_LAYOUT;
+    // not the input gci_bam_allele_size measured last on this context
+    if (!ctx->al_valid || n_rec != ctx->al_n_rec || n_bytes != ctx->al_n_bytes || d_stream != ctx->al_stream || d_rec_off != ctx->al_off ||
+        d_codes != ctx->al_codes)
+        return GCI_E_INVALID;
+    const unsigned long long total = ctx->al_total;
+    if (total && !d_out) return GCI_E_INVALID;
+    if (cap < total) return GCI_E_CAPACITY;
+    const MmRecScratch R = mm_rec_scratch(rec_frame(ctx->al_rec, n_rec));
+    const unsigned long long n_chunks = ctx->al_n_chunks;
+    if (n_chunks && total) {
+        const MmChunkScratch C = mm_chunk_scratch(ctx->al_chunk, n_chunks, 4);
+        hipLaunchKernelGGL(k_al_write, wave_grid(n_chunks), dim3(BLOCK), 0, ctx->stream,
+                           mm_walk_args(ctx, d_stream, n_bytes, n_rec, n_chunks, R, C, d_codes), C.mm0, total, d_out);
+        LAUNCHCHK("k_al_write");
     }
     HIPCHK(hipMemcpyAsync(d_status, R.status, 8, hipMemcpyDeviceToDevice, ctx->stream));
     return GCI_OK;
@@ -499,4 +628,79 @@ extern "C" int gci_mismatch_sites_write(gci_ctx* ctx, const int32_t* d_mismatch,
                        MmBest{d_depth}, (const int64_t*)ctx->d_off.p, d_out, total);
     LAUNCHCHK("k_site_runs_finish (mismatch)");
     return GCI_OK;
+}
+
+// ---- the track side of allele_sites.py ----------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int32_t al_best(int32_t a, int32_t c, int32_t g, int32_t t) { return max(max(a, c), max(g, t)); }
+
+struct HotAllele {                       // the LARGEST of the four allele tracks >= min_reads and / depth >= frac_ppm / 10^6, in 64 bits
+    const int32_t* a;
+    const int32_t* c;
+    const int32_t* g;
+    const int32_t* t;
+    const int32_t* depth;
+    int32_t min_reads;
+    int64_t frac_ppm;
+    __device__ __forceinline__ bool hot(int32_t best, int32_t d) const { return best >= min_reads && (int64_t)best * 1000000ll >= frac_ppm * (int64_t)d; }
+    __device__ __forceinline__ uint32_t four(int64_t p) const
+    {
+        const int4 va = *reinterpret_cast<const int4*>(a + p), vc = *reinterpret_cast<const int4*>(c + p);
+        const int4 vg = *reinterpret_cast<const int4*>(g + p), vt = *reinterpret_cast<const int4*>(t + p);
+        const int4 d = *reinterpret_cast<const int4*>(depth + p);
+        return (hot(al_best(va.x, vc.x, vg.x, vt.x), d.x) ? 1u : 0u) | (hot(al_best(va.y, vc.y, vg.y, vt.y), d.y) ? 2u : 0u) |
+               (hot(al_best(va.z, vc.z, vg.z, vt.z), d.z) ? 4u : 0u) | (hot(al_best(va.w, vc.w, vg.w, vt.w), d.w) ? 8u : 0u);
+    }
+    typedef int2 Val;                    // (best, depth)
+    __device__ __forceinline__ Val load(int64_t q) const { return make_int2(al_best(a[q], c[q], g[q], t[q]), depth[q]); }
+    __device__ __forceinline__ bool is(Val v) const { return hot(v.x, v.y); }
+    __device__ __forceinline__ bool one(int64_t q) const { return is(load(q)); }
+};
+
+struct AlleleEmit {                      // single elements, as ClipEmit: adjacent hot bases are adjacent sites
+    static constexpr int LISTER = 4;
+    static constexpr bool RUNS = false;
+    HotAllele h;
+    const uint8_t* codes;
+    gci_allele_site* out;
+    __device__ __forceinline__ void operator()(unsigned long long slot, const SiteTile& x, int64_t q) const
+    {
+        gci_allele_site s;
+        s.contig = x.contig; s.pos = (int32_t)(q - x.contig_off);
+        s.n[0] = h.a[q]; s.n[1] = h.c[q]; s.n[2] = h.g[q]; s.n[3] = h.t[q];
+        const int32_t best = al_best(s.n[0], s.n[1], s.n[2], s.n[3]);
+        s.alt = s.n[0] == best ? 1 : s.n[1] == best ? 2 : s.n[2] == best ? 4 : 8;          // a tie goes to the earlier letter
+        s.ref = codes[q]; s.depth = h.depth[q];
+        out[slot] = s;
+    }
+};
+
+static inline SiteMemo al_site_ask(const HotAllele& h, const uint8_t* d_codes, uint32_t n_windows)
+{
+    SiteMemo m;
+    m.track[0] = h.a; m.track[1] = h.c; m.track[2] = h.g; m.track[3] = h.t; m.track[4] = h.depth; m.track[5] = d_codes;
+    m.min_reads = h.min_reads; m.frac = (int32_t)h.frac_ppm; m.n_windows = n_windows;
+    return m;
+}
+
+extern "C" int gci_allele_sites_size(gci_ctx* ctx, const int32_t* d_a, const int32_t* d_c, const int32_t* d_g, const int32_t* d_t, const int32_t* d_depth,
+                                     const uint8_t* d_codes, int32_t min_reads, int32_t frac_ppm, const gci_window* h_windows, uint32_t n_windows,
+                                     uint64_t* h_n_sites)
+{
+    if (!ctx || !d_a || !d_c || !d_g || !d_t || !d_depth || !d_codes || !h_n_sites || min_reads < 1 || frac_ppm < 0 || frac_ppm > 1000000 ||
+        (n_windows && !h_windows))
+        return GCI_E_INVALID;
+    if (!ctx->n_contigs) return GCI_E_NO_LAYOUT;
+    if ((((uintptr_t)d_a) | ((uintptr_t)d_c) | ((uintptr_t)d_g) | ((uintptr_t)d_t) | ((uintptr_t)d_depth)) & 15u) return GCI_E_INVALID;      // whole tracks
+    const HotAllele hot{d_a, d_c, d_g, d_t, d_depth, min_reads, (int64_t)frac_ppm};
+    return site_size<AlleleEmit>(ctx, hot, al_site_ask(hot, d_codes, n_windows), h_windows, h_n_sites, "k_sites_count (alleles)");
+}
+
+extern "C" int gci_allele_sites_write(gci_ctx* ctx, const int32_t* d_a, const int32_t* d_c, const int32_t* d_g, const int32_t* d_t, const int32_t* d_depth,
+                                      const uint8_t* d_codes, int32_t min_reads, int32_t frac_ppm, const gci_window* h_windows, uint32_t n_windows,
+                                      gci_allele_site* d_out, uint64_t cap)
+{
+    if (!ctx || !d_a || !d_c || !d_g || !d_t || !d_depth || !d_codes || min_reads < 1 || (n_windows && !h_windows)) return GCI_E_INVALID;
+    if (!ctx->n_contigs) return GCI_E_NO_LAYOUT;
+    const HotAllele hot{d_a, d_c, d_g, d_t, d_depth, min_reads, (int64_t)frac_ppm};
+    return site_write(ctx, hot, al_site_ask(hot, d_codes, n_windows), AlleleEmit{hot, d_codes, d_out}, d_out, cap, "k_sites_write (alleles)");
 }

@@ -28,6 +28,7 @@ RUN_DTYPE = np.dtype([("start", "<u4"), ("depth", "<i4")])          # gci_depth_
 SITE_DTYPE = np.dtype([("contig", "<i4"), ("pos", "<i4"), ("left", "<i4"), ("right", "<i4"), ("depth", "<i4"), ("pad", "<i4")])      # gci_clip_site
 INDEL_SITE_DTYPE = np.dtype([("contig", "<i4"), ("start", "<i4"), ("end", "<i4"), ("del", "<i4"), ("ins", "<i4"), ("depth", "<i4")])      # gci_indel_site
 MISMATCH_SITE_DTYPE = np.dtype([("contig", "<i4"), ("start", "<i4"), ("end", "<i4"), ("mismatch", "<i4"), ("depth", "<i4")])      # gci_mismatch_site
+ALLELE_SITE_DTYPE = np.dtype([("contig", "<i4"), ("pos", "<i4"), ("ref", "<i4"), ("alt", "<i4"), ("n", "<i4", (4,)), ("depth", "<i4")])      # gci_allele_site
 
 _M64 = (1 << 64) - 1
 Buffer = Any                  # a device buffer of the engine's provider: hbm.Buf or Buffer
@@ -562,6 +563,44 @@ class Engine:
         out = self.T.empty((total, 5), self.T.int32, self.device)
         self._chk(self.lib.gci_mismatch_sites_write(*head, self._p(out), total), "gci_mismatch_sites_write")
         return np.ascontiguousarray(out.cpu().numpy()).view(MISMATCH_SITE_DTYPE).reshape(-1)[:total]
+
+    # ---- allele_sites.py: which base the reads carry where they disagree (include/gci_hip.h: gci_bam_allele_*, gci_allele_sites_*;
+    # k_mismatch.hip) ----
+    def bam_allele(self, d_stream: Buffer, d_rec_off: Buffer, has_seq: bool, d_ref_sel: Buffer, d_codes: Buffer, excl_flags: int = 0x704,
+                   min_mapq: int = 0, check: bool = True, rec_idx_base: int = 0) -> Tuple[Buffer, Buffer, Buffer, Buffer, List[int]]:
+        """-> (the A events, the C, the G, the T events, [records counted, A, C, G, T events, pairs compared]): four views of one buffer
+        of intervals int32 [n, 4] -- bam_mismatch's events, each in the list of the READ's base, inside a list in (record, reference
+        position) order, for depth_build with flank 0."""
+        n = int(d_rec_off.shape[0])
+        counts = (ctypes.c_uint64 * 6)()
+        self._chk(self.lib.gci_bam_allele_size(self.ctx, self._p(d_stream), int(d_stream.shape[0]), self._p(d_rec_off), n, int(has_seq),
+                                               self._p(d_ref_sel), int(d_ref_sel.shape[0]), int(excl_flags), int(min_mapq), self._p(d_codes), counts,
+                                               self._p(self._status)), "gci_bam_allele_size")
+        if check:
+            self._raise_status(self._status.item(), "gci_bam_allele_size", rec_idx_base)
+        ends = np.cumsum([0] + [int(c) for c in counts[1:5]]).tolist()
+        out = self.T.empty((max(ends[4], 1), 4), self.T.int32, self.device)
+        self._chk(self.lib.gci_bam_allele_write(self.ctx, self._p(d_stream), int(d_stream.shape[0]), self._p(d_rec_off), n, int(has_seq),
+                                                self._p(d_codes), self._p(out), ends[4], self._p(self._status)), "gci_bam_allele_write")
+        return (*(out[ends[k]:ends[k + 1]] for k in range(4)), [int(c) for c in counts])
+
+    def allele_sites(self, a: Buffer, c: Buffer, g: Buffer, t: Buffer, depth: Buffer, codes: Buffer, min_reads: int, frac_ppm: int,
+                     windows: Sequence[Tuple[int, int]] = ()) -> np.ndarray:
+        """-> ALLELE_SITE_DTYPE [n]: the single elements where the largest of the four allele tracks is >= min_reads and * 1000000 >=
+        frac_ppm * depth, inside the sorted, disjoint [begin, end) windows of track elements (none: every contig), in ascending order:
+        contig, pos, ref (the code in `codes` there), alt (1, 2, 4 or 8: the first of A, C, G, T that reaches the largest), the four
+        counts and the depth."""
+        nw = len(windows)
+        arr = self._window_array(windows)
+        n = ctypes.c_uint64(0)
+        head = (self.ctx, self._p(a), self._p(c), self._p(g), self._p(t), self._p(depth), self._p(codes), int(min_reads), int(frac_ppm), arr, nw)
+        self._chk(self.lib.gci_allele_sites_size(*head, ctypes.byref(n)), "gci_allele_sites_size")
+        total = int(n.value)
+        if total == 0:
+            return np.zeros(0, dtype=ALLELE_SITE_DTYPE)
+        out = self.T.empty((total, 9), self.T.int32, self.device)
+        self._chk(self.lib.gci_allele_sites_write(*head, self._p(out), total), "gci_allele_sites_write")
+        return np.ascontiguousarray(out.cpu().numpy()).view(ALLELE_SITE_DTYPE).reshape(-1)[:total]
 
     def track_add(self, acc: Buffer, add: Buffer) -> Buffer:
         """acc += add over the layout."""

@@ -29,7 +29,7 @@ from typing import Dict, List, Optional, Sequence, Set, Tuple
 import numpy as np
 
 from . import hbm, hostio, phases, score
-from .device import Buffer, Engine, INDEL_SITE_DTYPE, JoinInput, MISMATCH_SITE_DTYPE, REC_DTYPE, SITE_DTYPE, name_hash_np
+from .device import ALLELE_SITE_DTYPE, Buffer, Engine, INDEL_SITE_DTYPE, JoinInput, MISMATCH_SITE_DTYPE, REC_DTYPE, SITE_DTYPE, name_hash_np
 from . import _lib
 from ._lib import GciError, REC_HQ, REC_PASS
 from .formats import bam as bamfmt
@@ -1411,7 +1411,7 @@ class _ClipVisitor(StreamVisitor):
 
 def _event_tracks(engine: Engine, bam_files: Sequence[str], chrs: Sequence[str], make_visitor, threads: int, wall: str,
                   regions: Optional[Sequence[Tuple[str, int, int]]], tracks: int = 3, bytes_per_base: int = 0):
-    """What bam_clip_sites, bam_indel_sites and bam_mismatch_sites share: the layout of the first file's contigs (restricted by `chrs`),
+    """What bam_clip_sites, bam_indel_sites, bam_mismatch_sites and bam_allele_sites share: the layout of the first file's contigs (restricted by `chrs`),
     the TracksDoNotFit check before anything is read, make_visitor(engine) behind that check and in front of the first file, every
     file once through the visitor's collectors (one per track), the files' tracks added up.  `tracks`: how many tracks the visitor
     builds; `bytes_per_base`: what the run keeps per layout element next to them (the code array of bam_mismatch_sites), as the
@@ -1702,6 +1702,123 @@ def mismatch_summary_text(bam_files: Sequence[str], counts: Sequence[Sequence[in
     for k, (path, c) in enumerate(zip(bam_files, counts), 1):
         lines.append(row(str(k), [int(x) for x in c], path))
     lines.append(row("total", [sum(int(c[j]) for c in counts) for j in range(3)], "."))
+    lines.append("sites\t%d" % n_sites)
+    lines += ["%s\t%s" % (name, value) for name, value in options]
+    return "\n".join(lines) + "\n"
+
+
+# ==============================================================================================
+# allele_sites.py: which base the reads carry where they disagree with the assembly
+# ==============================================================================================
+
+ALLELE_MIN_READS = 3
+ALLELE_MIN_FRAC = "0.5"                    # of the reads over the base, for ONE allele: a choice, not a measurement
+_ALLELE_TRACKS = ("A", "C", "G", "T", "depth")
+_CODE_LETTER = "=ACMGRSVTWYHKDBN"          # BAM's 4-bit codes, as gci_fasta_codes writes them
+
+
+class AlleleSites:
+    """What bam_allele_sites returns: tracks = the five DepthTracks by name ("A", "C", "G", "T": per base the counted records that
+    carry that base where the assembly holds another of A, C, G, T; "depth": the read-mapping depth), sites =
+    device.ALLELE_SITE_DTYPE [n] in contig order and then by position, counts[k] = [records counted, A, C, G, T events, pairs compared]
+    of file k, flushes as in ClipSites."""
+
+    def __init__(self, tracks: Dict[str, DepthTracks], sites: np.ndarray, counts: List[List[int]], flushes: int):
+        self.tracks, self.sites, self.counts, self.flushes = tracks, sites, counts, flushes
+        self.depth = tracks["depth"]
+
+
+class _AlleleVisitor(_ClipVisitor):
+    """_ClipVisitor with gci_bam_allele_* as the event call: four event tracks next to the cover, six counts."""
+
+    TRACKS = _ALLELE_TRACKS
+    NEED_SEQ = True
+    PHASE, CALL = "record alleles", "gci_bam_allele_size"
+
+    def __init__(self, main: Engine, opts: CoverOpts, codes: Buffer, budget: int):
+        super().__init__(main, opts, 1, budget)
+        self.codes = codes
+        self.counts = [0] * 6
+
+    def begin_file(self) -> None:
+        super().begin_file()
+        self.counts = [0] * 6
+
+    abort_file = begin_file
+
+    def events(self, engine, d_stream, d_off, has_seq, ref_sel):
+        return engine.bam_allele(d_stream, d_off, has_seq, ref_sel, self.codes, self.opts.excl, self.opts.min_mapq)
+
+
+def bam_allele_sites(engine: Engine, reference: str, bam_files: Sequence[str], chrs: Sequence[str] = (), cover_opts: Optional[CoverOpts] = None,
+                     threads: int = 1, min_reads: int = ALLELE_MIN_READS, min_frac: str = ALLELE_MIN_FRAC,
+                     regions: Optional[Sequence[Tuple[str, int, int]]] = None, ivl_budget: Optional[int] = None) -> AlleleSites:
+    """Which base the reads of `bam_files` carry where they disagree with the assembly `reference` (include/gci_hip.h: gci_fasta_codes,
+    gci_bam_allele_size, gci_allele_sites_size): bam_mismatch_sites' events dealt to four tracks by the read's base, the read-mapping
+    depth, and the single bases where ONE allele reaches `min_reads` and the share `min_frac` of the depth (a decimal text, or parts per
+    million as an int) -- two alleles at 30 % each are a mismatch site at 0.5 and no site here.  Files, contigs, regions, TracksDoNotFit,
+    the check of the assembly and SeqNeeded as in bam_mismatch_sites.  The code array stays on the device until the sites are listed:
+    they carry the assembly's base."""
+    opts = cover_opts or CoverOpts()
+    frac_ppm = int(min_frac) if isinstance(min_frac, (int, np.integer)) else parse_fraction_ppm(str(min_frac))
+    if int(min_reads) < 1 or not 0 <= frac_ppm <= 1000000:
+        raise ValueError("min_reads is at least 1, min_frac between 0 and 1")
+    if _ingest_mode() == "heads":
+        raise SeqNeeded("the reads' bases are needed and the `heads` ingest drops them: use GCI_BAM_INGEST=gpu or full")
+    budget = COVER_IVL_BUDGET if ivl_budget is None else ivl_budget
+    first = same_sq_table(bam_files)
+
+    def make_visitor(e):
+        return _AlleleVisitor(e, opts, reference_codes(e, reference, _targets_of(first, list(chrs))), budget)
+
+    targets_length, totals, counts, visitor, windows = _event_tracks(engine, bam_files, chrs, make_visitor, threads, "bam_allele", regions,
+                                                                     tracks=5, bytes_per_base=1)
+    with phases.gpu("allele sites"):
+        if windows is None:
+            sites = np.zeros(0, dtype=ALLELE_SITE_DTYPE)
+        else:
+            sites = engine.allele_sites(*(totals[name] for name in _ALLELE_TRACKS), visitor.codes, int(min_reads), frac_ppm, windows)
+    return AlleleSites({name: DepthTracks(engine, targets_length, totals[name]) for name in _ALLELE_TRACKS}, sites, counts, visitor.flushes)
+
+
+def _site_columns(sites: np.ndarray):
+    """-> per site (contig, pos, REF letter, ALT letter, the count of ALT, the four counts, depth)."""
+    n = sites["n"].reshape(-1, 4).tolist()
+    for c, p, r, a, row, d in zip(sites["contig"].tolist(), sites["pos"].tolist(), sites["ref"].tolist(), sites["alt"].tolist(), n,
+                                  sites["depth"].tolist()):
+        yield c, p, _CODE_LETTER[r & 15], _CODE_LETTER[a & 15], row[(1, 2, 4, 8).index(a)], row, d
+
+
+def allele_sites_vcf(sites: np.ndarray, targets_length: Dict[str, int], reference_path: str) -> str:
+    """The text of {PREFIX}.allele.sites.vcf: a sites-only VCF 4.2, one line per site with one ALT, in contig order and then by position.
+    REF is the assembly's base as the code array holds it (an upper-case IUPAC letter), ALT the listed allele; DP the read-mapping
+    depth, AO the records that carry ALT, BC the A, C, G, T counts.  No genotypes, no qualities."""
+    targets = list(targets_length)
+    lines = ["##fileformat=VCFv4.2", "##source=allele_sites.py", "##reference=%s" % reference_path]
+    lines += ["##contig=<ID=%s,length=%d>" % (t, int(targets_length[t])) for t in targets]
+    lines += ['##INFO=<ID=DP,Number=1,Type=Integer,Description="Read-mapping depth at the base, as bam_depth.py counts it">',
+              '##INFO=<ID=AO,Number=1,Type=Integer,Description="Counted records that carry ALT at the base">',
+              '##INFO=<ID=BC,Number=4,Type=Integer,Description="Counted records that carry A, C, G, T at the base where the assembly holds another">',
+              "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO"]
+    lines += ["%s\t%d\t.\t%s\t%s\t.\t.\tDP=%d;AO=%d;BC=%d,%d,%d,%d" % (targets[c], p + 1, r, a, d, ao, *row)
+              for c, p, r, a, ao, row, d in _site_columns(sites)]
+    return "\n".join(lines) + "\n"
+
+
+def allele_sites_bed(sites: np.ndarray, targets: Sequence[str]) -> str:
+    """`contig\\tpos\\tpos+1\\tREF\\tALT\\tAO\\tDP\\n` per site, no header line: a BED file bedgraph_cli.parse_regions reads."""
+    return "".join("%s\t%d\t%d\t%s\t%s\t%d\t%d\n" % (targets[c], p, p + 1, r, a, ao, d) for c, p, r, a, ao, _, d in _site_columns(sites))
+
+
+def allele_summary_text(bam_files: Sequence[str], counts: Sequence[Sequence[int]], n_sites: int, options: Sequence[Tuple[str, object]]) -> str:
+    """The text of {PREFIX}.allele.txt: per file and in total the records counted, the pairs compared and the events per read base; the
+    sites; the options."""
+    def row(head, c, path):
+        return "%s\t%d\t%d\t%d\t%d\t%d\t%d\t%s" % (head, c[0], c[5], c[1], c[2], c[3], c[4], path)
+    lines = ["#file\trecords\tcompared\tA\tC\tG\tT\tpath"]
+    for k, (path, c) in enumerate(zip(bam_files, counts), 1):
+        lines.append(row(str(k), [int(x) for x in c], path))
+    lines.append(row("total", [sum(int(c[j]) for c in counts) for j in range(6)], "."))
     lines.append("sites\t%d" % n_sites)
     lines += ["%s\t%s" % (name, value) for name, value in options]
     return "\n".join(lines) + "\n"

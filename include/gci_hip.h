@@ -645,6 +645,58 @@ int gci_mismatch_sites_size(gci_ctx* ctx, const int32_t* d_mismatch, const int32
 int gci_mismatch_sites_write(gci_ctx* ctx, const int32_t* d_mismatch, const int32_t* d_depth, int32_t min_reads, int32_t frac_ppm,
                              const gci_window* h_windows, uint32_t n_windows, gci_mismatch_site* d_out, uint64_t cap);
 
+/* ---- allele_sites.py: WHICH base the reads carry where they disagree with the assembly (k_mismatch.hip) ----------------------------------
+ * gci_bam_allele_size / _write: the input of gci_bam_mismatch_size / _write, and its rules word for word -- which records count, which
+ * pairs are compared, the contig's end, l_seq, what is malformed and the status word.  The one difference: a mismatch is an event of the
+ * CLASS of the read's base, A, C, G or T (the SEQ nibble 1, 2, 4 or 8).
+ *   h_counts   host, 6 entries: the records counted; the events whose read base is A; C; G; T; the pairs compared.  Entries 1 - 4 add up
+ *              to gci_bam_mismatch_size's h_counts[1] for the same input, entries 0 and 5 are its h_counts[0] and [2].  The size call
+ *              synchronises.
+ *   write      d_out[0 .. nA + nC + nG + nT): the A list, then the C list, then G, then T (as gci_bam_indel_write lays out "deletions,
+ *              then insertions"), every event gci_ivl{contig, p, p, 0}, inside a list in (record, reference position) order.  The ranks
+ *              come from exclusive scans and wave scans, no atomics: two runs give the same bytes.  cap below the total:
+ *              GCI_E_CAPACITY, nothing is written.  Another stream, n_bytes, offsets, n_rec or d_codes than gci_bam_allele_size measured
+ *              last on this context: GCI_E_INVALID.  The pair keeps a memo of its own: a gci_bam_mismatch_size call between the two
+ *              changes nothing.
+ * gci_depth_build with flank 0 over list X gives track X: per base the counted records that carry X there where the assembly holds
+ * another of A, C, G, T.  The four tracks add up to the mismatch track of gci_bam_mismatch_write.
+ *
+ * gci_allele_sites_size / _write: the SINGLE elements where one allele is hot -- not runs: two adjacent hot bases are two sites.
+ *   input      the four allele tracks and the depth track, whole tracks of gci_layout_total() elements, 16-byte aligned (else
+ *              GCI_E_INVALID), and d_codes, the gci_fasta_codes array; all six are needed.
+ *   windows    as gci_indel_sites_size takes them.
+ *   best       the largest of the four tracks at the element; alt is the first of A, C, G, T that reaches it: a tie goes to the earlier
+ *              letter.
+ *   hot        an element inside a window and inside its contig with best >= min_reads and best * 1000000 >= frac_ppm * depth in 64-bit
+ *              integers.  min_reads < 1, frac_ppm outside 0 .. 1000000: GCI_E_INVALID.  The test is PER ALLELE: two alleles at 30 % of
+ *              the depth each make gci_mismatch_sites_size hot at 500000 ppm (their sum is 60 %) and this lister cold.  That is meant:
+ *              a site names one replacement base.  d_codes is no part of the test.
+ *   a site     contig, pos (0-based on the contig); ref = d_codes[element] as it is (15, 0 and every other value are passed through);
+ *              alt = 1, 2, 4 or 8; n = the A, C, G, T tracks at the element; depth.  Sites come in ascending flat order.
+ *   write      the sites of the size call in front of it on this context (same six arrays, min_reads, frac_ppm and n_windows, nothing
+ *              between the two that sets windows: else GCI_E_INVALID).  cap too small: GCI_E_CAPACITY, nothing is written.
+ * The size pass reads the five tracks once, 16 bytes a lane and track (20 bytes a base); the write pass leaves a tile whose count is 0
+ * at once and reads the code array only for the sites it stores.  No global atomics. */
+typedef struct gci_allele_site {
+    int32_t contig;
+    int32_t pos;
+    int32_t ref;
+    int32_t alt;
+    int32_t n[4];
+    int32_t depth;
+} gci_allele_site;
+int gci_bam_allele_size(gci_ctx* ctx, const uint8_t* d_stream, uint64_t n_bytes, const uint64_t* d_rec_off, uint32_t n_rec, int has_seq,
+                        const int32_t* d_ref_sel, int32_t n_ref, uint32_t excl_flags, int min_mapq, const uint8_t* d_codes, uint64_t* h_counts,
+                        uint64_t* d_status);
+int gci_bam_allele_write(gci_ctx* ctx, const uint8_t* d_stream, uint64_t n_bytes, const uint64_t* d_rec_off, uint32_t n_rec, int has_seq,
+                         const uint8_t* d_codes, gci_ivl* d_out, uint64_t cap, uint64_t* d_status);
+int gci_allele_sites_size(gci_ctx* ctx, const int32_t* d_a, const int32_t* d_c, const int32_t* d_g, const int32_t* d_t, const int32_t* d_depth,
+                          const uint8_t* d_codes, int32_t min_reads, int32_t frac_ppm, const gci_window* h_windows, uint32_t n_windows,
+                          uint64_t* h_n_sites);
+int gci_allele_sites_write(gci_ctx* ctx, const int32_t* d_a, const int32_t* d_c, const int32_t* d_g, const int32_t* d_t, const int32_t* d_depth,
+                           const uint8_t* d_codes, int32_t min_reads, int32_t frac_ppm, const gci_window* h_windows, uint32_t n_windows,
+                           gci_allele_site* d_out, uint64_t cap);
+
 /* Cross-rank name check for contig-sharded runs (exact).  gci_hash_bucket sorts the 64-bit name hashes of the
  * passing records into n_parts buckets by (hash >> 33) % n_parts; a bucket is part_cap + 1 uint64 words:
  * [0] = number of hashes the sender had for it (> part_cap: overflow), [1..] = the hashes.  After ONE all-to-all of
